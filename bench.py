@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the MDQT hot path on MI355X (one JSON line on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c5] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c5] [--dump-outputs DIR]
+    python bench.py --full [...] [--no-cpu-baseline]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does what the headline figure needs: set-up, warm-up, the K timed steps, the outputs
+(--dump-outputs) and the result line.  --full adds everything else the benchmark measures: the other
+kernel's launch time, the CPU baselines, the pump-model, Monte-Carlo + MD, jobs-per-GPU, end-to-end,
+MD-only and sharded lines (each with its own --no-... / --...-config switch).
 
 A "step" is one MD step of the reference time loop (SpeedUp:1369-1377): forces() once, then
 plasmaToQuantumTimestepRatio (= 25 at density 2) x (step(); qstep()), all on the GPU, state
@@ -36,6 +42,8 @@ F32_TIERS = ("ufar32_uniform",)   # census classes whose pair terms run in f32 (
 
 METRIC = "particle-steps/sec (MD+QT) at N=3.5k and N=1M; 1/2/4/8-GPU scaling"
 LINE_MAX_BYTES = 8192      # the driver parses the last stdout line; VERDICT r04 item 1
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs: all files together (ions are sampled beyond it)
+DUMP_SEED = 20240            # the sample's seed: the same ions from run to run
 
 CONFIGS = {
     # name: (params, qt, description)
@@ -55,6 +63,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the other kernel's launch time, the CPU baselines and the "
+                         "secondary lines (pump models, MC + MD, jobs per GPU, end to end, MD-only, sharded); "
+                         "the --no-... and --...-config options below select among them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the state a caller of md_steps() would read back "
+                         "(get_state(): R, V, F, psi, tPart, t) as DIR/<name>.npy (float64; at most "
+                         f"{DUMP_MAX_BYTES >> 20} MB in all: a fixed seeded sample of the ions beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--sharded-config", default="c5", choices=["none", "c3", "c5", "c4", "c1m"])
@@ -359,6 +375,29 @@ def check_world(gpus, env):
     return world
 
 
+def dump_outputs(sim, path, rank=0):
+    """--dump-outputs: what the timed md_steps() left, as a caller reads it back (get_state()), one
+    float64 .npy per array (rank r > 0 of a replica run: <name>.rank<r>.npy).  Above DUMP_MAX_BYTES
+    in all, the same seeded sample of ions is taken from every per-ion array (ion_index.npy holds it)."""
+    import numpy as np
+    st = sim.get_state()
+    N = sim.N
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in st.items() if k != "t"}
+    arrays["t"] = np.array([st["t"]], dtype=np.float64)
+    per_ion = sum(a.nbytes for a in arrays.values()) / max(N, 1) + 8     # + ion_index
+    keep = int(DUMP_MAX_BYTES // per_ion)
+    if keep < N:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=keep, replace=False))
+        for k, a in arrays.items():
+            ax = [i for i, n in enumerate(a.shape) if n == N]
+            if ax:
+                arrays[k] = np.ascontiguousarray(np.take(a, idx, axis=ax[0]))
+        arrays["ion_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
 def main():
     t_start = time.perf_counter()
     args = parse()
@@ -416,14 +455,18 @@ def main():
     barrier()                                      # torch.cuda.synchronize: every stream of the device
     el = time.perf_counter() - t0
     f_ms, nf, s_ms, ns = sim.kernel_time_totals()
-    sim.enable_timing(4, 3 - dom)                  # the other kernel, outside the timed region
-    sim.md_steps(8)
-    f2, nf2, s2, ns2 = sim.kernel_time_totals()
     sim.enable_timing(False)
-    if dom == 2:
-        f_ms, nf = f2, nf2
-    else:
-        s_ms, ns = s2, ns2
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs, rank)
+    if args.full:
+        sim.enable_timing(4, 3 - dom)              # the other kernel, outside the timed region
+        sim.md_steps(8)
+        f2, nf2, s2, ns2 = sim.kernel_time_totals()
+        sim.enable_timing(False)
+        if dom == 2:
+            f_ms, nf = f2, nf2
+        else:
+            s_ms, ns = s2, ns2
 
     tt = torch.tensor([el, float(N), f_ms, s_ms], dtype=torch.float64, device="cuda")
     if world > 1:
@@ -504,18 +547,26 @@ def main():
                        "rng": "philox4x32-10", "kernel_ms": {"force_total": f_ms, "force_launches": nf,
                                                             "substeps_total": s_ms, "substep_launches": ns,
                                                             "timed_in_window": "substeps" if dom == 2 else "force",
-                                                            "other_kernel": "8 MD steps after the window"}},
+                                                            "other_kernel": "8 MD steps after the window" if args.full
+                                                            else "not timed (--full)"}},
             "roofline": roof,
             "cpu_baseline": None,
             "timed_region_s": el_max,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(params, qt, args.cpu_seconds, 12345 + job, job)
-        if world == 1 and not args.no_pump_lines:
+        if args.full and world == 1 and not args.no_pump_lines:
             out["pump_models"] = pump_lines(local)
-        if world == 1 and not args.no_mcmd_lines:
+        if args.full and world == 1 and not args.no_mcmd_lines:
             out["mcmd"] = mcmd_line(local, cpu=not args.no_cpu_baseline)
     sim.close()
+    if not args.full:                              # a plain run: the headline alone
+        if rank == 0:
+            emit(out, t_start)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # The secondary line items below run after the headline number is final.  A watchdog on every
     # rank bounds them: if one of them fails or does not finish in time, rank 0 prints the line
     # with what it has (and the reason) and every rank leaves, so the headline is never lost.

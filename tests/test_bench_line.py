@@ -81,6 +81,57 @@ def test_md_only_config_list():
         bench.md_only_configs("c5")                  # QT on: not an MD-only line
 
 
+def test_full_is_off_by_default_and_dump_outputs_takes_a_directory(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+class _FakeSim:
+    """get_state() of an N-ion system, as engine.Simulation returns it"""
+
+    def __init__(self, N):
+        import numpy as np
+        self.N = N
+        r = np.arange(3.0 * N).reshape(3, N)
+        self.st = dict(R=r, V=-r, F=2 * r, psi=np.arange(24.0 * N).reshape(N, 12, 2), tPart=np.arange(1.0 * N), t=0.25)
+
+    def get_state(self):
+        return self.st
+
+
+def test_dump_outputs_writes_the_state_whole(tmp_path):
+    import numpy as np
+    sim = _FakeSim(1000)
+    bench.dump_outputs(sim, str(tmp_path / "out"))
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert sorted(got) == ["F", "R", "V", "psi", "t", "tPart"]
+    for k, a in got.items():
+        assert a.dtype == np.float64
+        assert np.array_equal(a, np.atleast_1d(sim.st[k])), k
+
+
+def test_dump_outputs_samples_the_same_ions_above_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100000)
+    sim = _FakeSim(1000)                            # 272 B per ion: 272 kB > the limit
+    for d in ("a", "b"):
+        bench.dump_outputs(sim, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "ion_index.npy" in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 100000 + 128 * len(files)   # + .npy headers
+    idx = np.load(tmp_path / "a" / "ion_index.npy").astype(int)
+    assert 300 < len(idx) < 1000 and np.all(np.diff(idx) > 0)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    assert np.array_equal(np.load(tmp_path / "a" / "R.npy"), sim.st["R"][:, idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "psi.npy"), sim.st["psi"][idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "t.npy"), [0.25])
+
+
 def test_synthetic_world8_line_fits():
     """a W = 8 line — every large line sharded over 8 ranks with its force-call
     breakdown, load imbalance and Epotential timing, plus the large end-to-end lines — stays within the

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-A="--steps 5 --warmup 2 --no-cpu-baseline --million-config none --no-pump-lines --no-mcmd-lines --no-e2e-line --no-replicas-line"
+A="--full --steps 5 --warmup 2 --no-cpu-baseline --million-config none --no-pump-lines --no-mcmd-lines --no-e2e-line --no-replicas-line"
 for v in "$@"; do
   if [ "$v" = base ]; then lib=""; else lib="MDQT_LIB=expt/$v/lib/libmdqt.so"; fi
   timeout -k 10 300 env $lib python3 bench.py $A > gpurun_out/abl_$v.log 2>&1 || { echo "$v failed"; tail -5 gpurun_out/abl_$v.log; exit 1; }

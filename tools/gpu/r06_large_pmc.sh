@@ -11,7 +11,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 R="$GRAFT_REPO_ROOT"
-BASE="$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pump-lines --no-mcmd-lines --no-e2e-line --no-replicas-line --sharded-steps 1 --million-steps 1 --md-only-config none --sharded-config none --million-config none"
+BASE="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pump-lines --no-mcmd-lines --no-e2e-line --no-replicas-line --sharded-steps 1 --million-steps 1 --md-only-config none --sharded-config none --million-config none"
 W=/tmp/large_pmc_$$                         # the databases stay on the box (gpurun_out/ is capped at 64 MiB)
 mkdir -p $W
 db() { ls $W/$1/*/*.db $W/$1/*.db 2>/dev/null | head -1; }
