@@ -1,4 +1,5 @@
-"""ctypes binding of libmdqt.so (the C ABIs declared in include/mdqt.h and include/mdmc.h).
+"""ctypes binding of libmdqt.so (the C ABIs declared in include/mdqt.h, include/mdmc.h and
+include/mdlc.h).
 
 The library is built in-tree (``python -m mdqtplasmasims_amd.build`` or ``__graft_entry__.build()``)
 into ``mdqtplasmasims_amd/lib/libmdqt.so``.  There is no fallback: if the library is missing or
@@ -14,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDQT_LIB") or os.path.join(HERE, "lib", "libmdqt.so")
 CLI_PATH = os.path.join(HERE, "bin", "mdqt")
 MDMC_CLI_PATH = os.path.join(HERE, "bin", "mdmc")
+MDLC_CLI_PATH = os.path.join(HERE, "bin", "mdlc")
 
 _dp = C.POINTER(C.c_double)
 
@@ -49,7 +51,38 @@ class MdmcParams(C.Structure):
     ]
 
 
+class MdlcParams(C.Structure):
+    """mirror of ``struct mdlc_params`` (include/mdlc.h)."""
+    _fields_ = [
+        ("N0", C.c_int), ("detuning", C.c_double), ("Om", C.c_double), ("tmax", C.c_double),
+        ("applyForce", C.c_int), ("sampleFreq", C.c_int), ("temperature", C.c_double),
+        ("vKick", C.c_double), ("dt", C.c_double),
+        ("seed", C.c_uint32), ("job", C.c_uint32), ("device", C.c_int), ("njobs", C.c_int),
+        ("saveDirectory", C.c_char * 256),
+    ]
+
+
 _ip = C.POINTER(C.c_int)
+_u64p = C.POINTER(C.c_uint64)
+
+# include/mdlc.h
+MDLC_SIGNATURES = [
+    ("mdlc_default_params", None, [C.POINTER(MdlcParams)]),
+    ("mdlc_create", C.c_int, [C.POINTER(MdlcParams), C.POINTER(C.c_void_p)]),
+    ("mdlc_destroy", None, [C.c_void_p]),
+    ("mdlc_get_const", C.c_double, [C.c_void_p, C.c_char_p]),
+    ("mdlc_sample_velocities", C.c_int, [C.c_uint32, C.c_int, C.c_double, _dp]),
+    ("mdlc_format_directory", C.c_int, [C.POINTER(MdlcParams), C.c_uint32, C.c_char_p, C.c_size_t]),
+    ("mdlc_init", C.c_int, [C.c_void_p]),
+    ("mdlc_qsteps", C.c_int, [C.c_void_p, C.c_longlong]),
+    ("mdlc_get_state", C.c_int, [C.c_void_p, _dp, _dp, _dp, _u64p]),
+    ("mdlc_set_state", C.c_int, [C.c_void_p, _dp, _dp, _dp, _u64p]),
+    ("mdlc_ekin_x", C.c_int, [C.c_void_p, _dp]),
+    ("mdlc_setup_directories", C.c_int, [C.c_void_p]),
+    ("mdlc_save_directory", C.c_char_p, [C.c_void_p, C.c_int]),
+    ("mdlc_run", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdlc_time_qsteps", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp]),
+]
 
 # include/mdmc.h
 MDMC_SIGNATURES = [
@@ -170,7 +203,7 @@ def lib():
             raise MdqtError(f"{LIB_PATH} not built: run `python -m mdqtplasmasims_amd.build` "
                             "(the MDQT engine has no CPU fallback)")
         L = C.CDLL(LIB_PATH)
-        for name, res, args in SIGNATURES + MDMC_SIGNATURES:
+        for name, res, args in SIGNATURES + MDMC_SIGNATURES + MDLC_SIGNATURES:
             try:
                 f = getattr(L, name)
             except AttributeError:

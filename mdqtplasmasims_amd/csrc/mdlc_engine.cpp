@@ -1,0 +1,432 @@
+// Host engine of the three-level laser-cooling program (laserCoolNoPlasmaThreeState.cpp, "LC3"):
+// the C ABI of include/mdlc.h.  Owns the device-resident state of an ensemble of jobs (vx, psi,
+// tPart), draws init()'s velocities from the reference's std::mt19937 stream, drives the gfx950
+// kernels of mdlc_kernels.hip and reproduces main()'s loop, directories and energies.dat.
+#include <errno.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+
+#include <random>
+#include <string>
+#include <vector>
+
+#include "../../include/mdlc.h"
+#include "mdqt_internal.hpp"
+#include "mdqt_mt32.hpp"
+#include "mdqt_writer.hpp"
+
+using namespace mdqt;
+
+#define HIPCHK(expr)                                                                                        \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess)                                                                               \
+            return set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
+    } while (0)
+
+struct mdlc_ctx {
+    mdlc_params p;
+    int N0 = 0, J = 0, S = 0, B = 0;
+    int dev = 0;
+    hipStream_t st = nullptr;
+    double *dVx = nullptr, *dPsi = nullptr, *dTp = nullptr, *dPart = nullptr, *dEk = nullptr;
+    double* hEk = nullptr;             // pinned: a chunk of the run's EkinX values [kChunk][J]
+    std::vector<double> hVyz;          // [J][2][N0]: V[1], V[2] (drawn by init(), never read by qstep())
+    uint64_t qidx = 0;
+    std::vector<std::string> dirs;     // [J]
+};
+
+namespace {
+
+constexpr int kMaxLaunchSteps = 8192;  // steps per launch (a few ms): a launch's length never follows tmax
+constexpr int kChunk = 512;            // output intervals between two host synchronisations of mdlc_run
+
+int fail_free(mdlc_ctx* c, const char* what) {
+    mdlc_destroy(c);
+    return set_error("%s", what);
+}
+
+int check_params(const mdlc_params* p) {
+    if (p->N0 < 1) return set_error("N0 must be >= 1");
+    if (p->njobs < 1) return set_error("njobs must be >= 1");
+    if (!(p->dt > 0)) return set_error("dt must be positive");
+    if (p->sampleFreq < 1) return set_error("sampleFreq must be >= 1");
+    if (!(p->temperature >= 0)) return set_error("temperature must be >= 0");
+    const long long S = ((long long)p->N0 + kLCBlock - 1) / kLCBlock * kLCBlock;
+    if (S * p->njobs / kLCBlock > 0x7fffffffLL) return set_error("N0 x njobs is too large for one launch grid");
+    return 0;
+}
+
+LCArgs make_args(const mdlc_ctx* c, int nsteps) {
+    const mdlc_params& p = c->p;
+    LCArgs a;
+    memset(&a, 0, sizeof a);
+    a.vx = c->dVx; a.psi = c->dPsi; a.tPart = c->dTp; a.part = c->dPart;
+    a.N0 = c->N0; a.S = c->S; a.B = c->B; a.nsteps = nsteps;
+    a.q0 = c->qidx; a.seed = p.seed; a.job0 = p.job; a.applyForce = p.applyForce ? 1 : 0;
+    a.dt = p.dt;
+    a.mre = 1. - p.dt * 0.5;               // Re M11 = Re M22: 1 + dt Im(hamDecayTerm) (:203, :223)
+    a.mi0 = p.dt * p.detuning;             // Im M11, M22 at v = 0: -dt (-detuning) (:192-193)
+    a.cim = p.dt * (p.Om / 2);             // -i dt (-Om/2) (:194)
+    a.ks = 1 * p.vKick * p.Om * p.dt;      // :189
+    a.vKick = p.vKick;
+    return a;
+}
+
+// qstep() x n on the stream, in launches of at most kMaxLaunchSteps
+int qsteps_async(mdlc_ctx* c, long long n) {
+    while (n > 0) {
+        const int k = (int)(n < kMaxLaunchSteps ? n : kMaxLaunchSteps);
+        HIPCHK(launch_lc_steps(make_args(c, k), c->J, c->st));
+        c->qidx += (uint64_t)k;
+        n -= k;
+    }
+    return 0;
+}
+
+// EkinX of every job into dst[J] (device), from the last launch's workgroup partials
+int ekin_async(mdlc_ctx* c, double* dst, bool fresh) {
+    if (!fresh) HIPCHK(launch_lc_steps(make_args(c, 0), c->J, c->st));
+    HIPCHK(launch_lc_ekin(c->dPart, c->J, c->B, c->N0, dst, c->st));
+    return 0;
+}
+
+// main() :364-380: the directory levels of job `job`, innermost last
+void directory_levels(const mdlc_params* p, uint32_t job, std::string lv[4]) {
+    char sd[sizeof p->saveDirectory + 1];
+    memcpy(sd, p->saveDirectory, sizeof p->saveDirectory);
+    sd[sizeof p->saveDirectory] = 0;
+    char b[128];
+    lv[0] = sd;
+    snprintf(b, sizeof b, "Om%d/", ref_udcast(p->Om * 100));                                   // :371
+    lv[1] = lv[0] + b;
+    snprintf(b, sizeof b, "Det%dNumIons%dInitialTemp%duK", ref_udcast(p->detuning * 100),      // :374
+             ref_udcast((double)p->N0), ref_udcast(p->temperature * 1000000));
+    lv[2] = lv[1] + b;
+    snprintf(b, sizeof b, "/job%d/", (int)job);                                                // :378
+    lv[3] = lv[2] + b;
+}
+
+// main()'s loop (:392-407) without its body: the t of every output() and the number of qsteps
+void main_loop_counts(const mdlc_params& p, std::vector<double>* touts, long long* iterations) {
+    double t = 0;
+    long long c0 = 0;
+    while (t <= p.tmax) {
+        t += p.dt;                                                  // repeated addition, as the reference
+        if ((c0 + 1) % p.sampleFreq == 0 && touts) touts->push_back(t);
+        c0++;
+    }
+    *iterations = c0;
+}
+
+}  // namespace
+
+extern "C" void mdlc_default_params(mdlc_params* p) {                 // LC3:54-88, :393
+    memset(p, 0, sizeof *p);
+    p->N0 = 1000; p->detuning = -0.5; p->Om = 0.5; p->tmax = 45000; p->applyForce = 1;
+    p->sampleFreq = 1000; p->temperature = 0.01; p->vKick = 0.0012076; p->dt = 0.01;
+    p->seed = 12345; p->job = 1; p->device = -1; p->njobs = 1;
+    strcpy(p->saveDirectory, "dataLaserCoolTestDoppShift/");
+}
+
+extern "C" int mdlc_sample_velocities(uint32_t seed, int N0, double temperature, double* V) {
+    if (!V || N0 < 1) return set_error("mdlc_sample_velocities: bad argument");
+    Mt32 rng;
+    rng.seed(seed);                                                   // :46 (seed instead of random_device)
+    std::uniform_real_distribution<double> uni(0, 1);                 // :47
+    (void)uni(rng);                                                   // :48 auto random_double = uni(rng)
+    std::normal_distribution<double> velocityDistribution(0, 1.0508 * sqrt(temperature));   // :83
+    for (int i = 0; i < N0; ++i) {                                    // :119-124
+        V[i] = velocityDistribution(rng);
+        V[(size_t)N0 + i] = velocityDistribution(rng);
+        V[(size_t)2 * N0 + i] = velocityDistribution(rng);
+    }
+    return 0;
+}
+
+extern "C" int mdlc_format_directory(const mdlc_params* p, uint32_t job, char* out, size_t cap) {
+    if (!p || !out) return set_error("mdlc_format_directory: NULL argument");
+    std::string lv[4];
+    directory_levels(p, job, lv);
+    if (lv[3].size() + 1 > cap) return set_error("mdlc_format_directory: buffer holds %zu < %zu bytes", cap, lv[3].size() + 1);
+    memcpy(out, lv[3].c_str(), lv[3].size() + 1);
+    return 0;
+}
+
+extern "C" void mdlc_destroy(mdlc_ctx* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->dev);
+    if (c->st) (void)hipStreamSynchronize(c->st);
+    void* ps[] = {c->dVx, c->dPsi, c->dTp, c->dPart, c->dEk};
+    for (void* q : ps)
+        if (q) (void)hipFree(q);
+    if (c->hEk) (void)hipHostFree(c->hEk);
+    if (c->st) (void)hipStreamDestroy(c->st);
+    delete c;
+}
+
+extern "C" int mdlc_create(const mdlc_params* p, mdlc_ctx** out) {
+    if (!p || !out) return set_error("mdlc_create: NULL argument");
+    *out = nullptr;
+    if (check_params(p)) return -1;
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1) return set_error("no HIP device available (%s)", hipGetErrorString(e));
+    mdlc_ctx* c = new mdlc_ctx();
+    c->p = *p;
+    c->p.saveDirectory[sizeof(c->p.saveDirectory) - 1] = 0;
+    if (p->device >= 0) {
+        if (p->device >= ndev) { delete c; return set_error("device %d >= device count %d", p->device, ndev); }
+        c->dev = p->device;
+    } else {
+        (void)hipGetDevice(&c->dev);
+    }
+    if (hipSetDevice(c->dev) != hipSuccess || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess) {
+        delete c;
+        return set_error("cannot create a HIP stream on device %d", p->device);
+    }
+    c->N0 = p->N0;
+    c->J = p->njobs;
+    c->B = (p->N0 + kLCBlock - 1) / kLCBlock;
+    c->S = c->B * kLCBlock;
+    const size_t n = (size_t)c->J * c->S, sz = n * sizeof(double);
+    bool ok = hipMalloc(&c->dVx, sz) == hipSuccess && hipMalloc(&c->dPsi, 6 * sz) == hipSuccess &&
+              hipMalloc(&c->dTp, sz) == hipSuccess &&
+              hipMalloc(&c->dPart, (size_t)c->J * c->B * sizeof(double)) == hipSuccess &&
+              hipMalloc(&c->dEk, (size_t)kChunk * c->J * sizeof(double)) == hipSuccess;
+    if (!ok) return fail_free(c, "mdlc_create: device allocation failed");
+    // the reference's globals start at zero (V, tPart, LC3:84, :91); psi gets its value in init()
+    ok = hipMemsetAsync(c->dVx, 0, sz, c->st) == hipSuccess && hipMemsetAsync(c->dPsi, 0, 6 * sz, c->st) == hipSuccess &&
+         hipMemsetAsync(c->dTp, 0, sz, c->st) == hipSuccess && hipStreamSynchronize(c->st) == hipSuccess;
+    if (!ok) return fail_free(c, "mdlc_create: device initialisation failed");
+    if (hipHostMalloc((void**)&c->hEk, (size_t)kChunk * c->J * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        return fail_free(c, "mdlc_create: pinned allocation failed");
+    c->hVyz.assign((size_t)c->J * 2 * c->N0, 0.);
+    c->dirs.resize(c->J);
+    for (int k = 0; k < c->J; ++k) {
+        std::string lv[4];
+        directory_levels(&c->p, c->p.job + (uint32_t)k, lv);
+        c->dirs[k] = lv[3];
+    }
+    *out = c;
+    return 0;
+}
+
+extern "C" double mdlc_get_const(const mdlc_ctx* c, const char* n) {
+    if (!c || !n) return NAN;
+    if (!strcmp(n, "N0")) return c->N0;
+    if (!strcmp(n, "njobs")) return c->J;
+    if (!strcmp(n, "dt")) return c->p.dt;
+    if (!strcmp(n, "stride")) return c->S;
+    if (!strcmp(n, "qstep_index")) return (double)c->qidx;
+    if (!strcmp(n, "iterations") || !strcmp(n, "outputs")) {
+        long long it = 0;
+        main_loop_counts(c->p, nullptr, &it);
+        return !strcmp(n, "iterations") ? (double)it : (double)(it / c->p.sampleFreq);
+    }
+    return NAN;
+}
+
+extern "C" int mdlc_set_state(mdlc_ctx* c, const double* V, const double* psi, const double* tPart,
+                              const uint64_t* qstep) {
+    if (!c) return set_error("NULL context");
+    HIPCHK(hipSetDevice(c->dev));
+    const int N0 = c->N0, J = c->J;
+    const size_t S = c->S, n = (size_t)J * S;
+    std::vector<double> h;
+    if (V) {
+        h.assign(n, 0.);
+        for (int k = 0; k < J; ++k) {
+            const double* Vk = V + (size_t)k * 3 * N0;
+            memcpy(&h[k * S], Vk, N0 * sizeof(double));
+            memcpy(&c->hVyz[(size_t)k * 2 * N0], Vk + N0, (size_t)2 * N0 * sizeof(double));
+        }
+        HIPCHK(hipMemcpyAsync(c->dVx, h.data(), n * sizeof(double), hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    if (psi) {
+        h.assign(6 * n, 0.);
+        for (int k = 0; k < J; ++k)
+            for (int i = 0; i < N0; ++i)
+                for (int q = 0; q < 6; ++q) h[q * n + k * S + i] = psi[((size_t)k * N0 + i) * 6 + q];
+        HIPCHK(hipMemcpyAsync(c->dPsi, h.data(), 6 * n * sizeof(double), hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    if (tPart) {
+        h.assign(n, 0.);
+        for (int k = 0; k < J; ++k) memcpy(&h[k * S], tPart + (size_t)k * N0, N0 * sizeof(double));
+        HIPCHK(hipMemcpyAsync(c->dTp, h.data(), n * sizeof(double), hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    if (qstep) c->qidx = *qstep;
+    return 0;
+}
+
+extern "C" int mdlc_get_state(mdlc_ctx* c, double* V, double* psi, double* tPart, uint64_t* qstep) {
+    if (!c) return set_error("NULL context");
+    HIPCHK(hipSetDevice(c->dev));
+    const int N0 = c->N0, J = c->J;
+    const size_t S = c->S, n = (size_t)J * S;
+    std::vector<double> h;
+    if (V) {
+        h.resize(n);
+        HIPCHK(hipMemcpyAsync(h.data(), c->dVx, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        for (int k = 0; k < J; ++k) {
+            double* Vk = V + (size_t)k * 3 * N0;
+            memcpy(Vk, &h[k * S], N0 * sizeof(double));
+            memcpy(Vk + N0, &c->hVyz[(size_t)k * 2 * N0], (size_t)2 * N0 * sizeof(double));
+        }
+    }
+    if (psi) {
+        h.resize(6 * n);
+        HIPCHK(hipMemcpyAsync(h.data(), c->dPsi, 6 * n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        for (int k = 0; k < J; ++k)
+            for (int i = 0; i < N0; ++i)
+                for (int q = 0; q < 6; ++q) psi[((size_t)k * N0 + i) * 6 + q] = h[q * n + k * S + i];
+    }
+    if (tPart) {
+        h.resize(n);
+        HIPCHK(hipMemcpyAsync(h.data(), c->dTp, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        for (int k = 0; k < J; ++k) memcpy(tPart + (size_t)k * N0, &h[k * S], N0 * sizeof(double));
+    }
+    if (qstep) *qstep = c->qidx;
+    return 0;
+}
+
+// init() :115-131 for every job: job number j's velocities from mt19937(seed + j), psi = (1, 0, 0), tPart = 0
+extern "C" int mdlc_init(mdlc_ctx* c) {
+    if (!c) return set_error("NULL context");
+    const int N0 = c->N0, J = c->J;
+    std::vector<double> V((size_t)J * 3 * N0), psi((size_t)J * N0 * 6, 0.), tp((size_t)J * N0, 0.);
+    for (int k = 0; k < J; ++k)
+        if (mdlc_sample_velocities(c->p.seed + (c->p.job + (uint32_t)k), N0, c->p.temperature, &V[(size_t)k * 3 * N0])) return -1;
+    for (size_t i = 0; i < (size_t)J * N0; ++i) psi[6 * i] = 1.;          // :125
+    const uint64_t q0 = 0;
+    return mdlc_set_state(c, V.data(), psi.data(), tp.data(), &q0);
+}
+
+extern "C" int mdlc_qsteps(mdlc_ctx* c, long long n) {
+    if (!c) return set_error("NULL context");
+    if (n < 0) return set_error("mdlc_qsteps: n < 0");
+    HIPCHK(hipSetDevice(c->dev));
+    if (qsteps_async(c, n)) return -1;
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+extern "C" int mdlc_time_qsteps(mdlc_ctx* c, int nsteps, int warmup, int launches, double* ms) {
+    if (!c || !ms) return set_error("mdlc_time_qsteps: NULL argument");
+    if (nsteps < 1 || nsteps > kMaxLaunchSteps || warmup < 0 || launches < 1)
+        return set_error("mdlc_time_qsteps: nsteps must be in [1, %d], warmup >= 0, launches >= 1", kMaxLaunchSteps);
+    HIPCHK(hipSetDevice(c->dev));
+    if (qsteps_async(c, (long long)warmup * nsteps)) return -1;
+    std::vector<hipEvent_t> ev((size_t)2 * launches, nullptr);
+    int rc = 0;
+    for (auto& e : ev)
+        if (hipEventCreate(&e) != hipSuccess) rc = set_error("mdlc_time_qsteps: cannot create an event");
+    for (int l = 0; l < launches && !rc; ++l) {
+        if (launch_lc_steps(make_args(c, nsteps), c->J, c->st, ev[2 * l], ev[2 * l + 1]) != hipSuccess)
+            rc = set_error("mdlc_time_qsteps: launch failed");
+        else
+            c->qidx += (uint64_t)nsteps;
+    }
+    if (hipStreamSynchronize(c->st) != hipSuccess && !rc) rc = set_error("mdlc_time_qsteps: synchronisation failed");
+    for (int l = 0; l < launches && !rc; ++l) {
+        float t = 0;
+        if (hipEventElapsedTime(&t, ev[2 * l], ev[2 * l + 1]) != hipSuccess) rc = set_error("mdlc_time_qsteps: no event time");
+        ms[l] = t;
+    }
+    for (auto& e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+extern "C" int mdlc_ekin_x(mdlc_ctx* c, double* out) {
+    if (!c || !out) return set_error("mdlc_ekin_x: NULL argument");
+    HIPCHK(hipSetDevice(c->dev));
+    if (ekin_async(c, c->dEk, false)) return -1;
+    HIPCHK(hipMemcpyAsync(c->hEk, c->dEk, (size_t)c->J * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    memcpy(out, c->hEk, (size_t)c->J * sizeof(double));
+    return 0;
+}
+
+extern "C" int mdlc_setup_directories(mdlc_ctx* c) {            // main() :364-380
+    if (!c) return set_error("NULL context");
+    for (int k = 0; k < c->J; ++k) {
+        std::string lv[4];
+        directory_levels(&c->p, c->p.job + (uint32_t)k, lv);
+        for (int l = 0; l < 4; ++l) (void)mkdir(lv[l].c_str(), 0777);   // the reference ignores mkdir's result
+        struct stat sb;
+        if (stat(lv[3].c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
+            return set_error("cannot create output directory %s", lv[3].c_str());
+    }
+    return 0;
+}
+
+extern "C" const char* mdlc_save_directory(const mdlc_ctx* c, int k) {
+    if (!c || k < 0 || k >= c->J) return nullptr;
+    return c->dirs[k].c_str();
+}
+
+// main() :356-408.  One launch per output interval (sampleFreq - 1 steps before the first
+// output(), sampleFreq between two, the remainder after the last); each interval's EkinX goes to
+// a device buffer that the host drains every kChunk intervals into the jobs' energies.dat.
+extern "C" int mdlc_run(mdlc_ctx* c, int verbose) {
+    if (!c) return set_error("NULL context");
+    HIPCHK(hipSetDevice(c->dev));
+    if (mdlc_setup_directories(c)) return -1;
+    if (mdlc_init(c)) return -1;                                    // :391
+    std::vector<double> touts;
+    long long iterations = 0;
+    main_loop_counts(c->p, &touts, &iterations);
+    const int J = c->J;
+    const long long sf = c->p.sampleFreq, nout = (long long)touts.size();
+    long long done = 0, drained = 0;
+    auto drain = [&](long long upto) -> int {                      // outputs [drained, upto) sit in dEk
+        const long long m = upto - drained;
+        if (m <= 0) return 0;
+        HIPCHK(hipMemcpyAsync(c->hEk, c->dEk, (size_t)m * J * sizeof(double), hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        for (int k = 0; k < J; ++k) {
+            const std::string path = c->dirs[k] + "energies.dat";
+            FILE* fa = fopen(path.c_str(), "a");                    // :321
+            if (!fa) return set_error("cannot open %s: %s", path.c_str(), strerror(errno));
+            bool ok;
+            {
+                LgText tx(fa);
+                for (long long o = 0; o < m; ++o) {                 // :322 "%lg\t%lg\n"
+                    tx.num(touts[drained + o]); tx.ch('\t'); tx.num(c->hEk[(size_t)o * J + k]); tx.ch('\n');
+                }
+                tx.spill();
+                ok = tx.ok();
+            }
+            if (fclose(fa) != 0 || !ok) return set_error("write error on %s", path.c_str());
+        }
+        if (verbose) {
+            printf("mdlc: t = %g  (%lld of %lld outputs)  EkinX[job %u] = %g\n", touts[upto - 1], upto, nout,
+                   c->p.job, c->hEk[(size_t)(m - 1) * J]);
+            fflush(stdout);
+        }
+        drained = upto;
+        return 0;
+    };
+    for (long long o = 0; o < nout; ++o) {
+        const long long target = (o + 1) * sf - 1;                  // qsteps before output o (:399-406)
+        const bool stepped = target > done;
+        if (qsteps_async(c, target - done)) return -1;
+        done = target;
+        if (ekin_async(c, c->dEk + (size_t)(o - drained) * J, stepped)) return -1;
+        if (o + 1 - drained == kChunk && drain(o + 1)) return -1;
+    }
+    if (drain(nout)) return -1;
+    if (qsteps_async(c, iterations - done)) return -1;              // the steps after the last output()
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}

@@ -33,14 +33,18 @@ __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {
     return (double)b * 0x1.0p-53;
 }
 
-// draws 2p and 2p+1 of (ion, q)
-__device__ __forceinline__ void philox_pair(const QTConst& qc, uint64_t ion, uint64_t q, int p,
+// draws 2p and 2p+1 of (ion, q) under the key (seed, job)
+__device__ __forceinline__ void philox_pair(uint32_t seed, uint32_t job, uint64_t ion, uint64_t q, int p,
                                             double& ua, double& ub) {
     uint32_t o[4];
     philox4x32_10((uint32_t)ion, (uint32_t)q, (uint32_t)(q >> 32),
-                  ((uint32_t)(ion >> 32) << 8) | (uint32_t)p, qc.seed, qc.job, o);
+                  ((uint32_t)(ion >> 32) << 8) | (uint32_t)p, seed, job, o);
     ua = u53(o[0], o[1]);
     ub = u53(o[2], o[3]);
+}
+__device__ __forceinline__ void philox_pair(const QTConst& qc, uint64_t ion, uint64_t q, int p,
+                                            double& ua, double& ub) {
+    philox_pair(qc.seed, qc.job, ion, q, p, ua, ub);
 }
 
 // uniforms 2p, 2p+1 of local ion i at substep (gid, q): the precomputed drand48 reference-order

@@ -2595,9 +2595,6 @@ static FILE* open_in(const mdqt_ctx* s, const char* name, const char* mode) {
 
 extern "C" const char* mdqt_save_directory(const mdqt_ctx* s) { return s->saveDirectory; }
 
-// the reference's "(unsigned)(x)" printed with %d (x86-64 runtime behaviour)
-static int ref_udcast(double x) { return (int)(uint32_t)(int64_t)x; }
-
 extern "C" int mdqt_setup_directories(mdqt_ctx* s) {       // SpeedUp:1145-1160
     const mdqt_params* p = &s->p;
     char base[512];

@@ -550,8 +550,35 @@ hipError_t launch_temperatures(const double* V, int N, int S, double* out, hipSt
 hipError_t launch_tag_moments(const double* V, const int* tags, int N, double* out, hipStream_t s);
 hipError_t launch_anisotropize(double* V, int N, int S, double tpd, hipStream_t s);
 hipError_t launch_store_velocities(const double* V, int N, int S, int T, int t, double* vs, hipStream_t s);
-// error message of the C ABI (mdqt_last_error), shared by the mdmc_* entry points
+// error message of the C ABI (mdqt_last_error), shared by the mdmc_* and mdlc_* entry points
 int set_error(const char* fmt, ...);
+// the reference's "(unsigned)(x)" printed with %d (x86-64 runtime behaviour):
+// the directory names of every program's main()
+inline int ref_udcast(double x) { return (int)(uint32_t)(int64_t)x; }
+
+// ---- three-level laser cooling without plasma (mdlc_kernels.hip; laserCoolNoPlasmaThreeState.cpp, "LC3") ----
+// An ensemble of J independent jobs of N0 ions: job k's ions sit at [k S, k S + N0) of every array,
+// S = N0 padded to whole workgroups (kLCBlock threads), so that no workgroup straddles two jobs.
+constexpr int kLCBlock = 256;
+struct LCArgs {
+    double* vx;         // [J][S] V[0][i] (LC3:170: the only velocity row qstep() reads)
+    double* psi;        // [6][J S] component-major (re0, im0, re1, im1, re2, im2)
+    double* tPart;      // [J S]
+    double* part;       // [J][B] out: each workgroup's sum of 0.5 vx^2 after the launch's last step
+    int N0, S, B;       // ions per job, padded stride, workgroups per job (S / kLCBlock)
+    int nsteps;         // qstep() x nsteps (0: the partial sums only)
+    uint64_t q0;        // qstep index of the first step (Philox counter)
+    uint32_t seed, job0;   // Philox key of job k: (seed, job0 + k)
+    int applyForce;     // LC3:63, :287
+    // M = I - i dt H (LC3:192-208, :223): M00 = 1, M11 = mre + i (mi0 - dt v), M22 = mre + i (mi0 + dt v),
+    // M01 = M02 = M10 = M20 = i cim
+    double dt, mre, mi0, cim;
+    double ks;          // vKick Om dt: the optical kick's scale (LC3:189)
+    double vKick;       // LC3:88, :279-284
+};
+hipError_t launch_lc_steps(const LCArgs& a, int J, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// out[k] = (fixed-order sum of job k's B workgroup partials) / N0: output()'s EkinX (LC3:309-316)
+hipError_t launch_lc_ekin(const double* part, int J, int B, int N0, double* out, hipStream_t s);
 // pumping-model QT tables for another engine (mdqt_engine.cpp; used by the MC + MD tagging programs)
 void build_pump_program(int model, double detuning, double Om, double dtQ, double gamToE, double pv2q,
                         double decayRatio, uint32_t seed, uint32_t job, QTConst& q, FastTab& f);
