@@ -364,6 +364,52 @@ int         mdqt_kernel_times(mdqt_ctx* c, double* out, int n);
  * stream; resets.  Replaces no reference function (measurement) */
 int         mdqt_force_breakdown(mdqt_ctx* c, double* out, int n);
 
+/* ---- ensembles: J independent jobs stepped in batched launches ----
+ * The reference is run as a Slurm array of independent jobs of this program (exampleSlurmFile.slurm:3:
+ * 99 jobs, `exe <job>`, each seeded srand48(time + job), SpeedUp:1219) whose results are averaged; one
+ * job of N0 = 3000-3500 does not fill an MI355X.  An ensemble owns J ordinary contexts on one stream and
+ * one device and steps them with ONE force launch and ONE QT launch per MD step over a (work item, job)
+ * grid.  Job k (k = 0 .. J-1) has job = p.job + k and seed = p.seed + k, everything else equal; N
+ * differs per job (init()'s rejection sampling).  Every job's state is bit for bit what the same job
+ * gives on its own context (same kernels' bodies on the same arguments, per-job tile-pair tables and
+ * slots).  Limits: world_size 1, rng_mode 1 (Philox), qt_model 0, qt_math 2, the lane QT kernel, no
+ * overlap / fused_step, every N <= 65,536; 1 <= njobs <= 1024.  Members below 128 ions (owner-computes
+ * rows by default) get their own small force launch inside mdqt_ensemble_forces.
+ * Lockstep: every batched call first checks that all members agree on t, the qstep index and c0, and
+ * fails naming the first job index that differs — a member stepped on its own ends the ensemble's
+ * stepping; reading or writing a member's state between ensemble calls is fine (the pending-force
+ * state is per job: mdqt_get_state on a member settles that member's slots only). */
+typedef struct mdqt_ensemble mdqt_ensemble;
+/* job k's parameters (job + k: SpeedUp:1145 argv[1]; seed + k: SpeedUp:1219).  Host only, 0 <= k < 1024 */
+int         mdqt_ensemble_job_params(const mdqt_params* base, int k, mdqt_params* out);
+int         mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out);   /* njobs x mdqt_create */
+void        mdqt_ensemble_destroy(mdqt_ensemble* e);
+int         mdqt_ensemble_size(const mdqt_ensemble* e);
+/* job k's context, owned by the ensemble: for mdqt_get_state / set_state / observables / output /
+ * get_N / get_counters / save_directory / set_option ... (NULL and an error for k outside) */
+mdqt_ctx*   mdqt_ensemble_job(mdqt_ensemble* e, int k);
+/* "qt_waves": register budget of the batched production QT instance in waves per SIMD: 0 (default) = the
+ * single-job kernel's, no scratch; 3 = 168 VGPRs, 20 bytes of scratch per lane, the launch 7 % shorter at
+ * 8 jobs of N0 = 3500 (bit-identical; A/B in docs/PROGRAMS.md).  Any other name: mdqt_set_option on every
+ * member */
+int         mdqt_ensemble_set_option(mdqt_ensemble* e, const char* name, int value);
+int         mdqt_ensemble_init(mdqt_ensemble* e);              /* init() of every job, SpeedUp:289-348    */
+int         mdqt_ensemble_forces(mdqt_ensemble* e);            /* forces() of every job, :192-236: one launch */
+int         mdqt_ensemble_substeps(mdqt_ensemble* e, int n);   /* n x (step(); qstep()) of every job,
+                                                                  :1376-1377: one launch per <= 32 substeps */
+int         mdqt_ensemble_md_steps(mdqt_ensemble* e, int n);   /* n x (forces(); c0++; ratio x (step();
+                                                                  qstep())) of every job; every 64 steps the
+                                                                  range flags of all jobs, one synchronisation */
+int         mdqt_ensemble_run(mdqt_ensemble* e);               /* main()'s time loop, :1139-1383, for every
+                                                                  job: directories, init() or readConditions,
+                                                                  output() per job, writeConditions per job */
+int         mdqt_ensemble_synchronize(mdqt_ensemble* e);       /* + the range flags of all jobs */
+/* the two batched kernels' own durations from their dispatch timestamps (on > 0: every launch):
+ * out[6] = force ms (sum), force launches, QT ms (sum), QT launches, median force launch ms, median
+ * QT launch ms — since the last call; synchronises and resets.  Replaces no reference function */
+int         mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on);
+int         mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

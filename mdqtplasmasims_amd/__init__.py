@@ -3,13 +3,15 @@
 
 Native code: mdqtplasmasims_amd/csrc (HIP kernels for gfx950 + C++ host engine) built into
 mdqtplasmasims_amd/lib/libmdqt.so with the C ABI of include/mdqt.h.  This package is the Python
-mirror of the reference's function seam (engine.Simulation) and the multi-GPU driver (sharded);
+mirror of the reference's function seam (engine.Simulation), the ensemble of independent jobs stepped in
+batched launches (ensemble.Ensemble) and the multi-GPU driver (sharded);
 mdmc.MonteCarloMD and mdlc.LaserCooling mirror the Monte-Carlo + MD programs and the three-level
 laser-cooling program (include/mdmc.h, include/mdlc.h).
 """
 from ._lib import MdqtError, LIB_PATH, CLI_PATH  # noqa: F401
 from .engine import Simulation, default_params, device_count, slab  # noqa: F401
+from .ensemble import Ensemble, job_params  # noqa: F401
 from .mdlc import LaserCooling, default_params as mdlc_default_params  # noqa: F401
 
-__all__ = ["Simulation", "MdqtError", "default_params", "device_count", "slab", "LIB_PATH", "CLI_PATH",
+__all__ = ["Simulation", "Ensemble", "job_params", "MdqtError", "default_params", "device_count", "slab", "LIB_PATH", "CLI_PATH",
            "LaserCooling", "mdlc_default_params"]

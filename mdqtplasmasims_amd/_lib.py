@@ -186,6 +186,21 @@ SIGNATURES = [
     ("mdqt_enable_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("mdqt_enable_timing_kinds", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("mdqt_enable_timing_at", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    # ensembles of jobs stepped in batched launches
+    ("mdqt_ensemble_job_params", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.POINTER(MdqtParams)]),
+    ("mdqt_ensemble_create", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.POINTER(C.c_void_p)]),
+    ("mdqt_ensemble_destroy", None, [C.c_void_p]),
+    ("mdqt_ensemble_size", C.c_int, [C.c_void_p]),
+    ("mdqt_ensemble_job", C.c_void_p, [C.c_void_p, C.c_int]),
+    ("mdqt_ensemble_set_option", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    ("mdqt_ensemble_init", C.c_int, [C.c_void_p]),
+    ("mdqt_ensemble_forces", C.c_int, [C.c_void_p]),
+    ("mdqt_ensemble_substeps", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdqt_ensemble_md_steps", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdqt_ensemble_run", C.c_int, [C.c_void_p]),
+    ("mdqt_ensemble_synchronize", C.c_int, [C.c_void_p]),
+    ("mdqt_ensemble_enable_timing", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdqt_ensemble_kernel_times", C.c_int, [C.c_void_p, _dp, C.c_int]),
 ]
 
 _lib = None

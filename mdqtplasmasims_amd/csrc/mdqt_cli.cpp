@@ -10,6 +10,10 @@
 //   --pump_program=1|2|3 runs instead the main() of randomFrozenStartTag408Linear.cpp /
 //   408Quad.cpp / 422Linear.cpp (their defaults, :52-80; mdqt_run_pump): the PumpTime...
 //   directory, spinUpIons_*, taggedMoments.dat, tagged vel_distX_*, VAF.dat, the conditions.
+//
+//   --njobs=J runs the jobs <job> .. <job>+J-1 of the reference's Slurm array (exampleSlurmFile.slurm:3)
+//   as one ensemble (mdqt_ensemble_run: one force and one QT launch per MD step for all of them), job k
+//   seeded seed + k; each job's files are those of `mdqt <job>+k --seed=<seed>+k`; prints every N.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,7 +29,9 @@ static void usage(void) {
             "                  [--reNormalizewvFns=0] [--saveDirectory=dataLaserCool/]\n"
             "                  [--seed=<srand48 seed; default time(NULL)+job as SpeedUp:1219>]\n"
             "                  [--qt=1] [--device=-1]\n"
-            "       mdqt <job> --pump_program=1|2|3 [--tpumpreal=2e-7] [--tstartV0=15] [... as above]\n");
+            "       mdqt <job> --pump_program=1|2|3 [--tpumpreal=2e-7] [--tstartV0=15] [... as above]\n"
+            "       mdqt <job> --njobs=J [... as above]   jobs <job> .. <job>+J-1 as one ensemble (J >= 1;\n"
+            "                  seeds seed .. seed+J-1; not with --pump_program)\n");
 }
 
 int main(int argc, char** argv) {
@@ -40,6 +46,7 @@ int main(int argc, char** argv) {
     const double job = atof(argv[1]);                       // SpeedUp:1145
     p.job = (uint32_t)job;
     int seed_given = 0;
+    long njobs = -1;                                        // --njobs: the jobs of an ensemble (-1: not given)
     for (int i = 2; i < argc; ++i) {
         const char* a = argv[i];
         if (strncmp(a, "--", 2) != 0 || !strchr(a, '=')) { usage(); return 2; }
@@ -59,6 +66,12 @@ int main(int argc, char** argv) {
 #undef IPAR
         if (!strcmp(key, "qt")) { p.qt_enabled = atoi(v); continue; }
         if (!strcmp(key, "pump_program")) continue;         // applied above
+        if (!strcmp(key, "njobs")) {
+            char* end = NULL;
+            njobs = strtol(v, &end, 10);
+            if (end == v || *end || njobs < 1 || njobs > 1024) { usage(); return 2; }
+            continue;
+        }
         if (!strcmp(key, "seed")) { p.seed = (uint32_t)strtoul(v, NULL, 10); seed_given = 1; continue; }
         if (!strcmp(key, "saveDirectory")) {
             strncpy(p.saveDirectory, v, sizeof(p.saveDirectory) - 1);
@@ -67,7 +80,21 @@ int main(int argc, char** argv) {
         fprintf(stderr, "mdqt: unknown parameter %s\n", key);
         return 2;
     }
+    if (njobs > 0 && pump) { usage(); return 2; }
     if (!seed_given) p.seed = (uint32_t)(time(NULL) + job);   // SpeedUp:1219
+    if (njobs > 0) {
+        mdqt_ensemble* e = NULL;
+        if (mdqt_ensemble_create(&p, (int)njobs, &e)) {
+            fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
+            return 1;
+        }
+        const int rc = mdqt_ensemble_run(e);
+        if (rc) fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
+        else
+            for (int k = 0; k < (int)njobs; ++k) printf("%i\n", mdqt_get_N(mdqt_ensemble_job(e, k)));
+        mdqt_ensemble_destroy(e);
+        return rc ? 1 : 0;
+    }
     mdqt_ctx* c = NULL;
     if (mdqt_create(&p, &c)) {
         fprintf(stderr, "mdqt: %s\n", mdqt_last_error());

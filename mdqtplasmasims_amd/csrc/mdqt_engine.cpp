@@ -237,6 +237,8 @@ struct mdqt_ctx {
     std::vector<double> Vholder;   // [13][3][N] VZERO_* files (SpeedUp:752-763, :898-913)
     char saveDirectory[1024];
     std::unique_ptr<FileWriter> writer;   // background formatting/writing of the output files
+    FileWriter* shared_writer = nullptr;  // a member of an ensemble writes through the ensemble's pool (16
+                                          // threads in all, not 4 per job); owned by the ensemble
     int init_threads = 0;          // init() sampling threads (option "init_threads"; 0 auto, 1 sequential)
     // timing
     // per-launch HIP events of the hot kernels (kind 0 = force, 1 = substeps), recorded on
@@ -1943,6 +1945,33 @@ static int n3b_balance(mdqt_ctx* s) {
     return 0;
 }
 
+// forces() on the Newton-3 tiles: the launch's argument block (mdqt_forces, md_step_fused with the plain
+// table, and the ensemble's batched launch: one construction, so they cannot drift apart)
+static int n3_force_args(mdqt_ctx* s, N3Args& a, bool plain_table = false) {
+    a = N3Args{};                // variant 2 (MCMD's exact pair set, rc2) is not used here
+    if (s->force_variant > 1) return fail("mdqt_forces: force_kernel must be 0 or 1");
+    // one tile (N <= 64): its one slot has F's [3][S] layout, so the kernel writes F itself and
+    // nothing is pending (the substep kernels read F when nseg == 1)
+    const bool one_slot = s->nslots == 1 && !plain_table;
+    // the split table (ensure_aux) unless the MD steps count tile arrivals (options overlap, fused_step:
+    // then every force call of the context takes the plain table)
+    const bool split = s->nsplit > 0 && !s->force_arrive && !one_slot && !s->overlap_opt && !s->fused_opt && !plain_table;
+    a.R = s->dR; a.P = one_slot ? s->dF : s->dFpart; a.pairs = split ? s->dPairs + s->npairs : s->dPairs;
+    a.N = s->N; a.S = s->S; a.ntiles = (s->N + 63) / 64; a.npairs = split ? s->nsplit_wg : s->npairs;
+    ForceArgs c = force_args(s, nullptr);
+    a.L = c.L; a.lDeb = c.lDeb; a.Rcut = c.Rcut; a.invlDeb = c.invlDeb; a.micT = c.micT;
+    a.micGuard = c.micGuard;
+    a.guard = c.guard;
+    a.arrive = s->force_arrive;                // overlapped MD step: count finished workgroups
+    return 0;
+}
+// ... and the pending-force state after a launch with that block
+static void n3_forces_pending(mdqt_ctx* s, const N3Args& a) {
+    const bool one_slot = a.P == s->dF, split = a.pairs != s->dPairs;
+    s->f_pending = !one_slot;  // slots summed by the next substep launch (or settle_forces)
+    s->pend_nseg = s->nslots + (split ? split_slots(s) : 0);
+}
+
 extern "C" int mdqt_forces(mdqt_ctx* s) {                 // forces(), SpeedUp:192-236
     if (!s) return fail("NULL context");
     if (s->nloc == 0) return 0;
@@ -1953,26 +1982,12 @@ extern "C" int mdqt_forces(mdqt_ctx* s) {                 // forces(), SpeedUp:1
     const bool tm_marks = tm && !s->use_n3;
     if (tm_marks && mark(s, 0)) return -1;
     if (s->use_n3) {
-        N3Args a{};                  // variant 2 (MCMD's exact pair set, rc2) is not used here
-        if (s->force_variant > 1) return fail("mdqt_forces: force_kernel must be 0 or 1");
-        // one tile (N <= 64): its one slot has F's [3][S] layout, so the kernel writes F itself and
-        // nothing is pending (the substep kernels read F when nseg == 1)
-        const bool one_slot = s->nslots == 1;
-        // the split table (ensure_aux) unless the MD steps count tile arrivals (options overlap, fused_step:
-        // then every force call of the context takes the plain table)
-        const bool split = s->nsplit > 0 && !s->force_arrive && !one_slot && !s->overlap_opt && !s->fused_opt;
-        a.R = s->dR; a.P = one_slot ? s->dF : s->dFpart; a.pairs = split ? s->dPairs + s->npairs : s->dPairs;
-        a.N = s->N; a.S = s->S; a.ntiles = (s->N + 63) / 64; a.npairs = split ? s->nsplit_wg : s->npairs;
-        ForceArgs c = force_args(s, nullptr);
-        a.L = c.L; a.lDeb = c.lDeb; a.Rcut = c.Rcut; a.invlDeb = c.invlDeb; a.micT = c.micT;
-        a.micGuard = c.micGuard;
-        a.guard = c.guard;
+        N3Args a;
+        if (n3_force_args(s, a)) return -1;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (tm && take_events(s, 0, &e0, &e1)) return -1;
-        a.arrive = s->force_arrive;                // overlapped MD step: count finished workgroups
         HIPCHK(launch_forces_n3(a, s->force_variant, s->stream, e0, e1));
-        s->f_pending = !one_slot;  // slots summed by the next substep launch (or settle_forces)
-        s->pend_nseg = s->nslots + (split ? split_slots(s) : 0);
+        n3_forces_pending(s, a);
     } else if (s->use_n3b) {
         const bool bd = tm && (s->tkinds & 8u);    // the breakdown of this call
         mdqt_ctx::BdCall bc;
@@ -2037,6 +2052,33 @@ extern "C" int mdqt_forces(mdqt_ctx* s) {                 // forces(), SpeedUp:1
     return 0;
 }
 
+// The argument block of a launch of m substeps from the context's state (run_substeps, md_step_fused
+// and the ensemble's batched launch); returns t after them (t itself where !advance_t).  nseg comes from
+// the pending-force state, which the caller clears.
+static double substep_args(const mdqt_ctx* s, SubstepArgs& a, int m, int do_step, int do_qt, int advance_t) {
+    memset(&a, 0, sizeof a);
+    a.R = s->dR + (size_t)s->p.rank * 3 * s->S;
+    a.V = s->dV; a.F = s->dF; a.psi = s->dPsi; a.tPart = s->dTp;
+    a.Fpart = s->dFpart; a.nseg = s->f_pending ? s->pend_nseg : 1;
+    a.oor = s->dFlags;
+    a.n = s->nloc; a.S = s->S; a.gid0 = (uint64_t)s->lo;
+    a.q0 = s->qidx;
+    a.nsub = m; a.do_step = do_step; a.do_qt = do_qt;
+    a.L = s->L;
+    a.qc = s->qc;
+    double t = s->t;
+    a.movmask = 0;
+    a.expdet_zero = 1;
+    for (int k = 0; k < m; ++k) {
+        a.t[k] = t;
+        a.expDet[k] = expDetuning_of(&s->p, t);
+        if (t > 0) a.movmask |= 1u << k;
+        if (a.expDet[k] != 0.) a.expdet_zero = 0;
+        if (advance_t) t += s->dtQ;                    // qstep: t += dtQuant (:716)
+    }
+    return t;
+}
+
 // n substeps of (step if do_step; qstep if do_qt_flag) — t advances only when advance_t
 static int run_substeps(mdqt_ctx* s, int n, int do_step, int do_qt_flag, int advance_t) {
     if (local_reduce(s)) return -1;
@@ -2047,11 +2089,7 @@ static int run_substeps(mdqt_ctx* s, int n, int do_step, int do_qt_flag, int adv
     while (n > 0) {
         const int m = d48 ? 1 : (n < MAXSUB ? n : MAXSUB);   // drand48: the stream orders ions per substep
         SubstepArgs a;
-        memset(&a, 0, sizeof a);
-        a.R = s->dR + (size_t)s->p.rank * 3 * s->S;
-        a.V = s->dV; a.F = s->dF; a.psi = s->dPsi; a.tPart = s->dTp;
-        a.Fpart = s->dFpart; a.nseg = s->f_pending ? s->pend_nseg : 1;
-        a.oor = s->dFlags;
+        const double t = substep_args(s, a, m, do_step, do_qt, advance_t);
         if (s->sub_stream) {                            // overlapped MD step (mdqt_md_steps)
             a.arrive = s->dArrive;
             a.arrive_target = s->sub_target;
@@ -2059,21 +2097,6 @@ static int run_substeps(mdqt_ctx* s, int n, int do_step, int do_qt_flag, int adv
             a.arrive_sleep = 2;
         }
         s->f_pending = false;
-        a.n = s->nloc; a.S = s->S; a.gid0 = (uint64_t)s->lo;
-        a.q0 = s->qidx;
-        a.nsub = m; a.do_step = do_step; a.do_qt = do_qt;
-        a.L = s->L;
-        a.qc = s->qc;
-        double t = s->t;
-        a.movmask = 0;
-        a.expdet_zero = 1;
-        for (int k = 0; k < m; ++k) {
-            a.t[k] = t;
-            a.expDet[k] = expDetuning_of(&s->p, t);
-            if (t > 0) a.movmask |= 1u << k;
-            if (a.expDet[k] != 0.) a.expdet_zero = 0;
-            if (advance_t) t += s->dtQ;                    // qstep: t += dtQuant (:716)
-        }
         if (d48 && s->nloc > 0) {
             D48Args r;
             r.psi = s->dPsi; r.n = s->nloc; r.S = s->S;
@@ -2228,38 +2251,18 @@ static int md_step_fused(mdqt_ctx* s) {
     if (arrive_setup(s)) return -1;
     HIPCHK(hipSetDevice(s->dev));
     const unsigned long long T = (unsigned long long)((s->N + 63) / 64);
-    N3Args f{};
-    const ForceArgs c = force_args(s, nullptr);
-    f.R = s->dR; f.P = s->dFpart; f.pairs = s->dPairs;
-    f.N = s->N; f.S = s->S; f.ntiles = (int)T; f.npairs = s->npairs;
-    f.L = c.L; f.lDeb = c.lDeb; f.Rcut = c.Rcut; f.invlDeb = c.invlDeb; f.micT = c.micT;
-    f.micGuard = c.micGuard; f.guard = 0;
+    N3Args f;
+    if (n3_force_args(s, f, true)) return -1;          // the plain table into the slots (nslots > 1)
+    f.guard = 0;
     f.arrive = s->dArrive;
     SubstepArgs a;                                     // as run_substeps(s, ratio, 1, 1, 1)
-    memset(&a, 0, sizeof a);
     const int m = s->ratio;
-    a.R = s->dR; a.V = s->dV; a.F = s->dF; a.psi = s->dPsi; a.tPart = s->dTp;
-    a.Fpart = s->dFpart; a.nseg = s->nslots;
-    a.oor = s->dFlags;
+    const double t = substep_args(s, a, m, 1, 1, 1);
+    a.nseg = s->nslots;
     a.arrive = s->dArrive;
     a.arrive_target = s->arriveEpoch + T;
     a.spin_err = s->dSpinErr;
     a.arrive_sleep = 2;
-    a.n = s->nloc; a.S = s->S; a.gid0 = (uint64_t)s->lo;
-    a.q0 = s->qidx;
-    a.nsub = m; a.do_step = 1; a.do_qt = 1;
-    a.L = s->L;
-    a.qc = s->qc;
-    double t = s->t;
-    a.movmask = 0;
-    a.expdet_zero = 1;
-    for (int k = 0; k < m; ++k) {
-        a.t[k] = t;
-        a.expDet[k] = expDetuning_of(&s->p, t);
-        if (t > 0) a.movmask |= 1u << k;
-        if (a.expDet[k] != 0.) a.expdet_zero = 0;
-        t += s->dtQ;                                   // qstep: t += dtQuant (:716)
-    }
     if (a.movmask != (m >= 32 ? 0xFFFFFFFFu : (1u << m) - 1u)) return fail("md_step_fused: t <= 0 in the interval");
     const bool tm = s->timing && (s->tkinds & 2u) && (s->tcount[1]++ % s->tperiod == s->toffset);
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -2619,6 +2622,7 @@ extern "C" int mdqt_setup_directories(mdqt_ctx* s) {       // SpeedUp:1145-1160
 }
 
 static FileWriter& writer_of(mdqt_ctx* s) {
+    if (s->shared_writer) return *s->shared_writer;    // a member of an ensemble: the ensemble's pool
     if (!s->writer) s->writer.reset(new FileWriter(4));
     return *s->writer;
 }
@@ -2627,9 +2631,10 @@ static std::string path_in(const mdqt_ctx* s, const char* name) { return std::st
 
 // wait for the background writers; reports the first file error
 static int flush_files(mdqt_ctx* s) {
-    if (!s->writer) return 0;
+    FileWriter* w = s->shared_writer ? s->shared_writer : s->writer.get();
+    if (!w) return 0;
     std::string e;
-    if (s->writer->flush(&e)) return fail("%s", e.c_str());
+    if (w->flush(&e)) return fail("%s", e.c_str());
     return 0;
 }
 
@@ -3540,3 +3545,8 @@ extern "C" int mdqt_get_drand48_state(mdqt_ctx* s, uint64_t* x) {
     *x = h;
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// ensembles of jobs stepped in batched launches (works on mdqt_ctx's internals: this translation unit)
+// ---------------------------------------------------------------------------------------------
+#include "mdqt_ensemble.hpp"

@@ -671,6 +671,16 @@ hipError_t launch_substeps_r(const SubstepArgs& a, const FastTab* tab, int mode,
 // after this launch's tile pairs
 hipError_t launch_md_step(const N3Args& f, const SubstepArgs& a, const FastTab* tab, int variant, hipStream_t s,
                           hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// An ensemble of independent jobs in one launch (mdqt_ensemble_*): `jobs` = device array of the jobs'
+// argument blocks; grid (largest job's workgroups, njobs).  Forces: max_npairs = the largest a.npairs,
+// guard = any job's.  Substeps: `a` = host copy of one job's block (selects the instance, as
+// launch_substeps_r mode 2 does: model 0 only), max_n the largest a.n, tab[1] the by-lane table the jobs
+// share, wpe the production instance's register budget in waves per SIMD (0 = the single-job kernel's, or 3).
+hipError_t launch_forces_n3_ens(const N3Args* jobs, int njobs, int max_npairs, int variant, bool guard, hipStream_t s,
+                                hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t launch_substeps_r_ens(const SubstepArgs* jobs, const SubstepArgs& a, int njobs, int max_n, const FastTab* tab,
+                                 int wpe, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
+                                 int* instance = nullptr);
 // measureSpinUps (randomFrozenStartTag408Linear.cpp:600, :422Linear) / tagParticles
 // (MonteCarloFollowedByQTTagging408Linear.cpp:1022): tag[i] = 1 with probability of spin up
 hipError_t launch_tag_spin_up(const double* psi, int n, int S, uint64_t gid0, uint64_t q, const QTConst& qc,

@@ -1,0 +1,123 @@
+"""An ensemble of independent MDQT jobs on one MI355X, stepped in batched launches.
+
+The reference is run as a Slurm array of independent jobs of laserCoolingPlusExpansionMDQTSpeedUp.cpp
+(exampleSlurmFile.slurm:3, ``exe <job>``, srand48(time + job) at SpeedUp:1219) whose results are
+averaged.  :class:`Ensemble` owns ``njobs`` such jobs — job k has ``job + k`` and ``seed + k`` — and steps
+them with one force launch and one QT launch per MD step (include/mdqt.h, "ensembles").  Every job's
+state is bit for bit what :class:`~mdqtplasmasims_amd.engine.Simulation` gives for that job alone.
+
+    =================================  ===========================  ==========================
+    reference (SpeedUp), per job       here, all jobs               C ABI (include/mdqt.h)
+    =================================  ===========================  ==========================
+    init()            :289-348         Ensemble.init()              mdqt_ensemble_init
+    forces()          :192-236         Ensemble.forces()            mdqt_ensemble_forces
+    step();qstep() x n  :1376-1377     Ensemble.substeps(n)         mdqt_ensemble_substeps
+    forces + ratio substeps, x n       Ensemble.md_steps(n)         mdqt_ensemble_md_steps
+    main()            :1139-1383       Ensemble.run()               mdqt_ensemble_run
+    =================================  ===========================  ==========================
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from ._lib import MdqtParams, check, lib
+from .engine import Simulation, default_params
+
+
+def job_params(base: MdqtParams, k: int) -> MdqtParams:
+    """job k's parameters of an ensemble created from `base` (job + k, seed + k; host only)"""
+    out = MdqtParams()
+    check(lib().mdqt_ensemble_job_params(C.byref(base), int(k), C.byref(out)), "ensemble_job_params")
+    return out
+
+
+class _Member(Simulation):
+    """a job of an ensemble: the whole Simulation interface on a context the ensemble owns"""
+
+    def __init__(self, ensemble, handle, params):  # no mdqt_create
+        self._ensemble = ensemble                  # keeps the owner alive
+        self.params = params
+        self.h = C.c_void_p(handle)
+
+    def close(self):                               # not this view's to destroy
+        self.h = None
+
+
+class Ensemble:
+    """``njobs`` independent jobs (job + k, seed + k) resident on one MI355X, stepped together."""
+
+    def __init__(self, njobs: int, **params):
+        self.params = default_params(**params)
+        h = C.c_void_p()
+        check(lib().mdqt_ensemble_create(C.byref(self.params), int(njobs), C.byref(h)), "mdqt_ensemble_create")
+        self.h = h
+        self.jobs = [_Member(self, lib().mdqt_ensemble_job(h, k), job_params(self.params, k))
+                     for k in range(lib().mdqt_ensemble_size(h))]
+
+    # ---- lifecycle ----
+    def close(self):
+        if getattr(self, "h", None):
+            for j in self.jobs:
+                j.close()
+            lib().mdqt_ensemble_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return len(self.jobs)
+
+    @property
+    def N(self):
+        """every job's ion number"""
+        return [j.N for j in self.jobs]
+
+    def set_option(self, name: str, value: int):
+        """"qt_waves" (the batched QT kernel's register budget) or any Simulation option, on every job"""
+        check(lib().mdqt_ensemble_set_option(self.h, name.encode(), int(value)), "ensemble_set_option")
+
+    # ---- the reference's function seam, for every job at once ----
+    def init(self):
+        check(lib().mdqt_ensemble_init(self.h), "ensemble_init")
+        return self
+
+    def forces(self):
+        check(lib().mdqt_ensemble_forces(self.h), "ensemble_forces")
+
+    def substeps(self, n: int):
+        check(lib().mdqt_ensemble_substeps(self.h, int(n)), "ensemble_substeps")
+
+    def md_steps(self, n: int):
+        check(lib().mdqt_ensemble_md_steps(self.h, int(n)), "ensemble_md_steps")
+
+    def run(self):
+        check(lib().mdqt_ensemble_run(self.h), "ensemble_run")
+
+    def synchronize(self):
+        check(lib().mdqt_ensemble_synchronize(self.h), "ensemble_synchronize")
+
+    # ---- timing ----
+    def enable_timing(self, on: bool = True):
+        """record the two batched kernels' dispatch timestamps at every launch"""
+        check(lib().mdqt_ensemble_enable_timing(self.h, 1 if on else 0))
+
+    def kernel_times(self):
+        """{force_ms, n_force, substep_ms, n_substep, force_median_ms, substep_median_ms} of the batched
+        launches since the last call (synchronises and resets)"""
+        out = (C.c_double * 6)()
+        check(lib().mdqt_ensemble_kernel_times(self.h, out, 6), "ensemble_kernel_times")
+        keys = ("force_ms", "n_force", "substep_ms", "n_substep", "force_median_ms", "substep_median_ms")
+        return {k: (int(out[i]) if k.startswith("n_") else out[i]) for i, k in enumerate(keys)}
+
+
+__all__ = ["Ensemble", "job_params"]

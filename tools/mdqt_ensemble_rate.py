@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Rate of an ensemble of MDQT jobs stepped in batched launches (mdqtplasmasims_amd.Ensemble) on one GPU,
+against one Simulation alone and against k Simulations on k streams (the pattern of bench.py's
+replicas_line, re-implemented here with the same synchronise placement: warm-up, synchronise, timed MD
+steps issued from one host thread, synchronise).
+
+Configs: c2 = N0 3500 full MDQT (bench.py's C2), n500 = N0 500 full MDQT.  Jobs k = 1 .. are seeded
+12345 + k, job = k, as replicas_line seeds them, so the three patterns step the same systems.
+
+Prints ONE JSON line:
+  single:    the rate of job 1 alone, its two kernels' mean launch durations (event timestamps)
+  streams:   per k in --streams: the aggregate rate of k Simulations round-robin on their own streams
+  ensemble:  per J in --jobs: the aggregate wall-clock rate of one md_steps(--steps) call (timing off;
+             value), of --steps calls of md_steps(1) (value_call_per_step: the argument blocks copied
+             before every QT launch instead of ahead), then from a timed pass with the kernels' dispatch
+             timestamps: median force / QT launch (us), and their FP64 roof
+             fractions as the project counts them (QT 1,750 flop per particle-qstep, force 30 flop per
+             pair, N (N - 1) / 2 pairs per job; against 78.6 TF)
+Rates are particle-qsteps/s summed over the jobs.  Any error exits non-zero; there is no CPU fallback.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FP64_PEAK = 78.6e12
+QT_FLOP = 1750.0          # per particle-qstep
+PAIR_FLOP = 30.0          # per evaluated pair
+CONFIGS = {"c2": dict(N0=3500), "n500": dict(N0=500)}
+
+
+def timed(step, sync, steps, warmup):
+    for _ in range(warmup):
+        step()
+    sync()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    sync()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser(formatter_class=argparse.RawTextHelpFormatter)
+    ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
+    ap.add_argument("--jobs", default="1,2,4,8,16,32,64", help="ensemble sizes J")
+    ap.add_argument("--streams", default="2,4,8", help="k of the k-streams pattern ('' = skip)")
+    ap.add_argument("--steps", type=int, default=1000, help="timed MD steps (the window has to be long: a 100-step\n"
+                    "window of one C2 job is 4 ms and measures the clock ramp as much as the kernels)")
+    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--qt-waves", type=int, default=0, help="Ensemble option qt_waves (0, 3)")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--json", default=None, help="also write the JSON line to this file")
+    a = ap.parse_args()
+
+    import mdqtplasmasims_amd as M
+    params = dict(CONFIGS[a.config], device=a.device)
+    jobs = [int(x) for x in a.jobs.split(",") if x]
+    streams = [int(x) for x in a.streams.split(",") if x]
+    out = dict(tool="mdqt_ensemble_rate", config=a.config, steps=a.steps, warmup=a.warmup, qt_waves=a.qt_waves,
+               unit="particle-qsteps/s", fp64_peak=FP64_PEAK)
+
+    # one Simulation alone
+    with M.Simulation(seed=12346, job=1, **params) as s:
+        s.init()
+        ratio = int(s.const("plasmaToQuantumTimestepRatio"))
+        el = timed(lambda: s.md_steps(1), s.synchronize, a.steps, a.warmup)
+        s.enable_timing(1)
+        timed(lambda: s.md_steps(1), s.synchronize, min(a.steps, 200), 0)
+        kt = s.kernel_times()
+        out["single"] = dict(N=s.N, ms_per_md_step=el / a.steps * 1e3, value=s.N * ratio * a.steps / el,
+                             force_us=kt["force_ms"] / max(kt["n_force"], 1) * 1e3,
+                             qt_us=kt["substep_ms"] / max(kt["n_substep"], 1) * 1e3)
+    out["ratio"] = ratio
+
+    # k Simulations on k streams, round-robin from this thread
+    out["streams"] = []
+    for k in streams:
+        sims = [M.Simulation(seed=12345 + j, job=j, **params).init() for j in range(1, k + 1)]
+        try:
+            def step():
+                for x in sims:
+                    x.md_steps(1)
+
+            def sync():
+                for x in sims:
+                    x.synchronize()
+            el = timed(step, sync, a.steps, a.warmup)
+            ntot = sum(x.N for x in sims)
+        finally:
+            for x in sims:
+                x.close()
+        out["streams"].append(dict(jobs=k, N_total=ntot, ms_per_md_step=el / a.steps * 1e3,
+                                   value=ntot * ratio * a.steps / el))
+
+    # the ensemble
+    out["ensemble"] = []
+    for J in jobs:
+        with M.Ensemble(njobs=J, seed=12346, job=1, **params) as e:
+            if a.qt_waves:
+                e.set_option("qt_waves", a.qt_waves)
+            e.init()
+            # one md_steps call: the argument blocks of the steps are built ahead, one copy per <= 64 steps
+            e.md_steps(a.warmup)
+            el = timed(lambda: e.md_steps(a.steps), e.synchronize, 1, 0)
+            # one call per MD step (the k-streams pattern's call shape): a copy before every QT launch
+            el1 = timed(lambda: e.md_steps(1), e.synchronize, a.steps, 0)
+            e.enable_timing(True)
+            e.md_steps(min(a.steps, 200))
+            kt = e.kernel_times()
+            Ns = e.N
+        ntot = sum(Ns)
+        pairs = sum(n * (n - 1) / 2 for n in Ns)
+        f_us, q_us = kt["force_median_ms"] * 1e3, kt["substep_median_ms"] * 1e3
+        out["ensemble"].append(dict(
+            jobs=J, N_total=ntot, ms_per_md_step=el / a.steps * 1e3, value=ntot * ratio * a.steps / el,
+            value_call_per_step=ntot * ratio * a.steps / el1,
+            force_us=f_us, qt_us=q_us, n_force=kt["n_force"], n_qt=kt["n_substep"],
+            force_roof=(pairs * PAIR_FLOP / (f_us * 1e-6) / FP64_PEAK) if f_us > 0 else None,
+            qt_roof=(ntot * ratio * QT_FLOP / (q_us * 1e-6) / FP64_PEAK) if q_us > 0 else None))
+
+    line = json.dumps(out)
+    print(line)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
