@@ -126,6 +126,13 @@ int         mdqt_substeps(mdqt_ctx* c, int n);               /* n x (step(); qst
                                                                  fused in one launch            */
 int         mdqt_md_steps(mdqt_ctx* c, int n);               /* n x (forces(); c0++;
                                                                  ratio x (step(); qstep()))     */
+/* Position-range check: the substep kernels raise a word in host-pinned memory when a position leaves
+ * [-L/8, 9L/8] (an ion moving more than L/8 in half a substep: a broken run).  mdqt_md_steps reads that
+ * word before every MD step with a plain host load — it issues no stream synchronisation on a healthy
+ * run — so inside a call it sees what completed launches raised: the report lags the step that caused it
+ * by the launch-queue depth.  mdqt_synchronize and the state read-backs (mdqt_get_state) drain the stream
+ * and then check, so an excursion is reported no later than the next host synchronisation.  The call that
+ * sees it fails with the "positions left [-L/8, 9L/8]" error, and later pair kernels range-check. */
 
 /* Stateless kernel-level entry points on caller host arrays (explicit box and screening
  * length), for callers whose force law is the same Yukawa pair sum but whose box is not

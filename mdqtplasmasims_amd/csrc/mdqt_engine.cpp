@@ -198,7 +198,7 @@ struct mdqt_ctx {
     int last_fused = 0;                    // the last MD step ran as one k_md_step launch
     int last_qt_kernel = 0;                // QT kernel instance of the last substep launch (QTKernel codes)
     int last_qt_nseg = 0;                  // force partials that launch summed in its prologue
-    int* dSpinErr = nullptr;
+    int* dSpinErr = nullptr;               // = dFlags + 1 (host-mapped, see hFlags)
     unsigned long long* force_arrive = nullptr;   // set around a force launch of an overlapped step
     hipStream_t sub_stream = nullptr;             // set around the QT launch of an overlapped step
     unsigned long long sub_target = 0;
@@ -220,7 +220,11 @@ struct mdqt_ctx {
     int split_cus = 0;             // option force_split_cus: the CU count the split table is cut for (0: the device's)
     // rng_mode 0: the reference's drand48 stream, consumed in ion order on the device
     unsigned long long* dX48 = nullptr;   // [1] stream state + [48] jA + [48] jC
-    int* dFlags = nullptr;         // [0] set by the substep kernels when a position leaves [-L/8, 9L/8]
+    // the words the substep kernels raise, in host-pinned, device-mapped memory of this context: the
+    // kernels store to them in the failure case only, the host reads them without a stream operation
+    // ([0]: a position left [-L/8, 9L/8]; [1]: an overlapped / fused QT launch gave up its arrival wait)
+    volatile int* hFlags = nullptr;
+    int* dFlags = nullptr;         // the device address of hFlags
     bool guard = false;            // host view: range-check every pair (see ForceArgs::guard)
     double* dU = nullptr;                 // [5][S] uniforms of the current substep
     ncclComm_t comm = nullptr;     // RCCL communicator over the world_size ranks (sharded runs)
@@ -277,28 +281,35 @@ static int tail_reset(mdqt_ctx* s, bool keep_scale = false) {
     return 0;
 }
 
-// The substep kernels raise dFlags[0] if a position leaves [-L/8, 9L/8] (an ion moving more than
-// L/8 in half a substep: not a physical run).  Checked at every host synchronisation point;
-// from then on every pair is range-checked, and the call reports the event as an error.
-static int check_range_flag(mdqt_ctx* s) {
-    if (s->dSpinErr) {                  // an overlapped QT launch gave up waiting for its forces
-        int e = 0;
-        if (hipMemcpyAsync(&e, s->dSpinErr, sizeof e, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-            hipStreamSynchronize(s->stream) != hipSuccess)
-            return fail("reading the overlap flag failed");
-        if (e) return fail("overlapped MD step: a QT launch timed out waiting for its force launch");
-    }
-    int f = 0;
-    if (hipMemcpyAsync(&f, s->dFlags, sizeof f, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipStreamSynchronize(s->stream) != hipSuccess)
-        return fail("reading the position-range flag failed");
-    if (f && !s->guard) {
+// The substep kernels raise hFlags[0] if a position leaves [-L/8, 9L/8] (an ion moving more than
+// L/8 in half a substep: not a physical run).  The word lives in host-pinned memory the kernels
+// store to directly, so reading it is a host load: poll_flags is called before every MD step of
+// mdqt_md_steps' loops and drains nothing.  A store is certain to be visible once its kernel has
+// completed, so inside a loop the poll sees what completed launches raised and lags the host's
+// issue point by the launch-queue depth; check_range_flag, called where the host has synchronised
+// with the stream anyway (mdqt_synchronize, the state read-backs), drains the stream first and so
+// reports every excursion no later than the next host synchronisation.  From then on every pair
+// is range-checked, and the call reports the event as an error.
+static int poll_flags(mdqt_ctx* s) {
+    if (s->hFlags[1]) return fail("overlapped MD step: a QT launch timed out waiting for its force launch");
+    if (s->hFlags[0] && !s->guard) {
         s->guard = true;
         return fail("positions left [-L/8, 9L/8] during the run (ion displacement > L/8 per half "
                     "substep); pair range checks are now on, but forces since the last sync used "
                     "the in-box minimum image");
     }
+    return 0;
+}
+static int check_range_flag(mdqt_ctx* s) {
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return fail("reading the position-range flag failed");
+    if (poll_flags(s)) return -1;
     return tail_check(s);
+}
+// mdqt_md_steps' loops, before MD step k: the flags every step (host loads); the Newton-3 block
+// scheme's measured tail sums (a read-back: those MD steps take milliseconds) every 64 steps
+static int loop_check(mdqt_ctx* s, int k) {
+    if (poll_flags(s)) return -1;
+    return (k > 0 && k % 64 == 0) ? tail_check(s) : 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -936,12 +947,19 @@ extern "C" int mdqt_create(const mdqt_params* p, mdqt_ctx** out) {
         return fail("hipMalloc lane tables");
     }
     {
-        const int f[2] = {0, 1};
-        if (hipMalloc(&s->dFlags, sizeof f) != hipSuccess ||
-            hipMemcpy(s->dFlags, f, sizeof f, hipMemcpyHostToDevice) != hipSuccess) {
+        void *h = nullptr, *d = nullptr;
+        if (hipHostMalloc(&h, 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess) {
             mdqt_destroy(s);
-            return fail("hipMalloc flags");
+            return fail("hipHostMalloc flags");
         }
+        s->hFlags = (volatile int*)h;
+        s->hFlags[0] = s->hFlags[1] = 0;
+        if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+            mdqt_destroy(s);
+            return fail("hipHostGetDevicePointer flags");
+        }
+        s->dFlags = (int*)d;
+        s->dSpinErr = s->dFlags + 1;
     }
     build_constants(s);
     if (s->p.rng_mode == 0) {
@@ -985,13 +1003,12 @@ extern "C" void mdqt_destroy(mdqt_ctx* s) {
     if (s->dComm) (void)hipFree(s->dComm);
     if (s->dSpinUp) (void)hipFree(s->dSpinUp);
     if (s->dArrive) (void)hipFree(s->dArrive);
-    if (s->dSpinErr) (void)hipFree(s->dSpinErr);
     if (s->evQ) (void)hipEventDestroy(s->evQ);
     if (s->evS) (void)hipEventDestroy(s->evS);
     if (s->qs) (void)hipStreamDestroy(s->qs);
     if (s->dTkde) (void)hipFree(s->dTkde);
     if (s->dX48) (void)hipFree(s->dX48);
-    if (s->dFlags) (void)hipFree(s->dFlags);
+    if (s->hFlags) (void)hipHostFree((void*)s->hFlags);
     if (s->comm) (void)ncclCommDestroy(s->comm);
     for (auto& pool : s->evpool)
         for (hipEvent_t ev : pool) (void)hipEventDestroy(ev);
@@ -1025,6 +1042,7 @@ extern "C" double mdqt_get_const(const mdqt_ctx* s, const char* n) {
     if (!strcmp(n, "vKickDP")) return s->vKickDP;
     if (!strcmp(n, "lDeb")) return s->lDeb;
     if (!strcmp(n, "L")) return s->L;
+    if (!strcmp(n, "range_guard")) return s->guard ? 1 : 0;   // the pair kernels range-check (see poll_flags)
     if (!strcmp(n, "decayRatioD5Halves")) return s->r;
     if (!strcmp(n, "kRat")) return s->kRat;
     if (!strcmp(n, "force_segments")) return s->nseg;
@@ -1162,9 +1180,8 @@ static int upload(mdqt_ctx* s, const double* R, const double* V, size_t ld, cons
             if (!(x >= plo && x <= phi)) oor = 1;
         }
         s->guard = oor != 0;
-        const int zero = 0;
-        HIPCHK(hipMemcpyAsync(s->dFlags, &zero, sizeof zero, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));         // no earlier launch can raise the flag any more
+        s->hFlags[0] = 0;
     }
     const int lo = s->lo, n = s->nloc;
     if (V) {
@@ -2175,10 +2192,6 @@ static int arrive_setup(mdqt_ctx* s) {
     s->dArrive = nullptr;
     HIPCHK(hipMalloc(&s->dArrive, (size_t)T * sizeof(unsigned long long)));
     HIPCHK(hipMemset(s->dArrive, 0, (size_t)T * sizeof(unsigned long long)));
-    if (!s->dSpinErr) {
-        HIPCHK(hipMalloc(&s->dSpinErr, sizeof(int)));
-        HIPCHK(hipMemset(s->dSpinErr, 0, sizeof(int)));
-    }
     HIPCHK(hipDeviceSynchronize());
     s->arriveCap = T;
     s->arriveEpoch = 0;
@@ -2209,7 +2222,7 @@ static int md_steps_overlapped(mdqt_ctx* s, int n) {
     HIPCHK(hipStreamWaitEvent(s->qs, s->evS, 0));
     for (int k = 0; k < n; ++k) {
         if (k > 0) HIPCHK(hipStreamWaitEvent(s->stream, s->evQ, 0));
-        if (k > 0 && k % 64 == 0 && check_range_flag(s)) return -1;
+        if (loop_check(s, k)) return -1;
         s->force_arrive = s->dArrive;
         const int rc = mdqt_forces(s);
         s->force_arrive = nullptr;
@@ -2281,7 +2294,7 @@ extern "C" int mdqt_md_steps(mdqt_ctx* s, int n) {
     if (!s) return fail("NULL context");
     if (n > 0 && overlap_applies(s)) return md_steps_overlapped(s, n);
     for (int k = 0; k < n; ++k) {
-        if (k > 0 && k % 64 == 0 && check_range_flag(s)) return -1;
+        if (loop_check(s, k)) return -1;
         if (fused_applies(s)) {
             if (local_reduce(s) || md_step_fused(s)) return -1;
             s->last_fused = 1;

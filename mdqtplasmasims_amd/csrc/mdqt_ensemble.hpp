@@ -32,7 +32,6 @@ struct mdqt_ensemble {
     hipEvent_t ring_ev[kRing] = {};
     bool ring_used[kRing] = {};
     unsigned ring_pos = 0;
-    int* hFlags = nullptr;                         // pinned [J]: the members' range flags (one sync for all)
     int qt_waves = 0;                              // option "qt_waves": register budget of the production QT instance
     bool timing = false;
     std::vector<hipEvent_t> evpool[2];             // 0 = force launches, 1 = QT launches (start, stop, ...)
@@ -196,15 +195,14 @@ int ens_substeps(mdqt_ensemble* e, int n) {
     return 0;
 }
 
-// check_range_flag of every member with one synchronisation
-int ens_range_flags(mdqt_ensemble* e) {
+// check_range_flag of every member with one synchronisation (drain), or, inside the MD-step loops, the
+// members' words as they stand (host loads: what completed launches raised)
+int ens_range_flags(mdqt_ensemble* e, bool drain = true) {
     const int J = (int)e->jobs.size();
-    for (int k = 0; k < J; ++k)
-        HIPCHK(hipMemcpyAsync(e->hFlags + k, e->jobs[k]->dFlags, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    if (drain) HIPCHK(hipStreamSynchronize(e->stream));
     int first = -1;
-    for (int k = 0; k < J; ++k)
-        if (e->hFlags[k] && !e->jobs[k]->guard) {
+    for (int k = 0; k < J; ++k)                    // each member's own host-mapped word (mdqt_ctx::hFlags)
+        if (e->jobs[k]->hFlags[0] && !e->jobs[k]->guard) {
             e->jobs[k]->guard = true;
             if (first < 0) first = k;
         }
@@ -232,7 +230,7 @@ int ens_md_steps(mdqt_ensemble* e, int n) {
     const int ahead = tiles ? std::min(64, e->sub_blocks / (J * per_step)) : 0;
     if (ahead < 2) {
         for (int k = 0; k < n; ++k) {
-            if (k > 0 && k % 64 == 0 && ens_range_flags(e)) return -1;
+            if (ens_range_flags(e, false)) return -1;
             if (ens_forces(e)) return -1;
             for (mdqt_ctx* s : e->jobs) s->c0++;
             if (ens_substeps(e, ratio)) return -1;
@@ -240,7 +238,7 @@ int ens_md_steps(mdqt_ensemble* e, int n) {
         return 0;
     }
     for (int k = 0; k < n;) {
-        if (k > 0 && k % 64 == 0 && ens_range_flags(e)) return -1;
+        if (ens_range_flags(e, false)) return -1;
         const int b = std::min(std::min(n - k, ahead), 64 - k % 64);
         EnsForce f;
         if (ens_force_blocks(e, f)) return -1;
@@ -305,7 +303,6 @@ extern "C" void mdqt_ensemble_destroy(mdqt_ensemble* e) {
     if (e->dForce) (void)hipFree(e->dForce);
     if (e->dSub) (void)hipFree(e->dSub);
     if (e->ring) (void)hipHostFree(e->ring);
-    if (e->hFlags) (void)hipHostFree(e->hFlags);
     for (hipEvent_t ev : e->ring_ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& pool : e->evpool)
         for (hipEvent_t ev : pool) (void)hipEventDestroy(ev);
@@ -345,8 +342,7 @@ extern "C" int mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemb
     e->slot_bytes = std::max((size_t)e->sub_blocks * sizeof(SubstepArgs), (size_t)njobs * sizeof(N3Args));
     if (hipMalloc(&e->dForce, (size_t)njobs * sizeof(N3Args)) != hipSuccess ||
         hipMalloc(&e->dSub, (size_t)e->sub_blocks * sizeof(SubstepArgs)) != hipSuccess ||
-        hipHostMalloc((void**)&e->ring, e->slot_bytes * mdqt_ensemble::kRing, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&e->hFlags, (size_t)njobs * sizeof(int), hipHostMallocDefault) != hipSuccess)
+        hipHostMalloc((void**)&e->ring, e->slot_bytes * mdqt_ensemble::kRing, hipHostMallocDefault) != hipSuccess)
         return fail("mdqt_ensemble_create: allocating the argument blocks of %d jobs failed", njobs);
     for (hipEvent_t& ev : e->ring_ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence));
     *out = e.release();
@@ -433,7 +429,7 @@ extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
             for (mdqt_ctx* s : e->jobs)
                 if (output_async(s)) return -1;         // each member's own device pass and synchronisation
         if (tsc == ratio) {                                                             // :1369
-            if (steps > 0 && steps % 64 == 0 && ens_range_flags(e)) return -1;
+            if (ens_range_flags(e, false)) return -1;
             if (ens_forces(e)) return -1;
             for (mdqt_ctx* s : e->jobs) s->c0++;
             tsc = 0;

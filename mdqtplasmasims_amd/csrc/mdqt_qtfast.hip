@@ -417,7 +417,12 @@ __device__ unsigned long long g_md_stamps[4 * 4096];
 // production model-0 launch is k_substeps_lanes_im<true, true> (FAST + IM01 + EDZ).
 // NORN: reNormalizewvFns is off (the reference's default, SpeedUp:74) — the renormalisation and
 // its uniform branch compiled out, so one substep's tail and the next one's head share a basic block
-template <bool DPPX, bool FAST, bool FUSED, bool IM01 = false, bool EDZ = false, bool NORN = false>
+// JUNI: a substep in which an ion of the wave jumps runs as one straight-line block chosen wave-uniformly
+// (MDQT_JUMP_UNIFORM, see the substep body).  Off where the extra registers of that block cost more than
+// the jump tail: the QT workgroups of k_md_step (one VGPR count for both parts: 214 instead of 168 would
+// take the tile pairs from three waves per SIMD to two) and the ensemble's three-waves-per-SIMD set (168
+// VGPRs: 196 bytes of scratch instead of 20) keep the per-lane branch.
+template <bool DPPX, bool FAST, bool FUSED, bool IM01 = false, bool EDZ = false, bool NORN = false, bool JUNI = !FUSED>
 __device__ __forceinline__ void lane_substeps(const SubstepArgs& a, const FastTab* __restrict__ tab, int blk) {
 #if defined(MDQT_EXPT_QTSTAMPS)
     unsigned long long st_[16] = {};
@@ -636,6 +641,12 @@ __device__ __forceinline__ void lane_substeps(const SubstepArgs& a, const FastTa
 #ifndef MDQT_PHASE_BOUND
 #define MDQT_PHASE_BOUND 1
 #endif
+        // 1: a substep in which an ion of the wave jumps runs as one straight-line block chosen
+        // wave-uniformly (see the substep body); 0: the per-lane branch, whose two sides such a wave
+        // executes one after the other (A/B builds)
+#ifndef MDQT_JUMP_UNIFORM
+#define MDQT_JUMP_UNIFORM 1
+#endif
         // Wave-uniform bound on every coupling phase of the launch (production instance): |v| grows
         // by at most |dt f| + kickmax per substep and tPart by dtQ, so when the bound on |phi| is
         // below 2^19 the per-substep |phi| >= 2^20 library fallback cannot trigger and is left out
@@ -702,12 +713,13 @@ __device__ __forceinline__ void lane_substeps(const SubstepArgs& a, const FastTa
                 else sincos_fast(phin, snn, csn);
 #endif
             };
-            if (nojump) {
-                {                                 // kick terms on the P lanes (host table)
-                    const double kt = kick_term(w, w0, w1, w2, kw0, kw1, kw2);
-                    kick = DPPX ? lane_sum_p8(kt, one) : lane_sum_p(kt);
-                }
-                next_phase();
+            // the no-jump substep's kick (the kick terms on the P lanes, host table) and its four
+            // Runge-Kutta stages: w after the substep
+            auto rk_kick = [&]() {
+                const double kt = kick_term(w, w0, w1, w2, kw0, kw1, kw2);
+                return DPPX ? lane_sum_p8(kt, one) : lane_sum_p(kt);
+            };
+            auto rk_stages = [&]() {
                 const cxd md = {mre, fma(mi1, u, mi0)};
                 const cxd c2 = {fma(dms, sn, c2re), fma(dmc, cs, c2im)};
                 cxd y = w, acc = {0., 0.};
@@ -729,9 +741,11 @@ __device__ __forceinline__ void lane_substeps(const SubstepArgs& a, const FastTa
                     if (stg < 2) y = {fma(0.5, d.re, w.re), fma(0.5, d.im, w.im)};
                     else if (stg == 2) y = {w.re + d.re, w.im + d.im};
                 }
-                w = {fma(0.125, acc.re, w.re), fma(0.125, acc.im, w.im)};
-            } else {                                  // quantum jump (:573-703)
-                tPart = 0;
+                return cxd{fma(0.125, acc.re, w.re), fma(0.125, acc.im, w.im)};
+            };
+            // the quantum jump (:573-703) of w: the state it lands on and its kick.  TAPE: the
+            // uniforms of the drand48 tape (a.U), else Philox
+            auto jump = [&](auto tape, double& jkick) {
                 const double nk = sq(w);
                 double n3, n4, n5, n6;                    // |w|^2 of the P states 2..5
                 if constexpr (DPPX) {
@@ -740,7 +754,7 @@ __device__ __forceinline__ void lane_substeps(const SubstepArgs& a, const FastTa
                     n3 = dpp<BCAST(2)>(nk); n4 = dpp<BCAST(3)>(nk); n5 = dpp<BCAST(4)>(nk); n6 = dpp<BCAST(5)>(nk);
                 }
                 double randDOrS, randDir, rand3, dummy;
-                if (a.U) {
+                if constexpr (decltype(tape)::value) {
                     draw_pair(qc, a.U, S, i, gid, a.q0 + (uint64_t)s, 1, randDOrS, randDir);
                     draw_pair(qc, a.U, S, i, gid, a.q0 + (uint64_t)s, 2, rand3, dummy);
                     (void)dummy;
@@ -751,9 +765,47 @@ __device__ __forceinline__ void lane_substeps(const SubstepArgs& a, const FastTa
                     randDir = dpp<BCAST(0)>(x1);
                     rand3 = dpp<BCAST(8)>(x0);
                 }
-                const int target = (DPPX || qc.model == 0)   // DPPX: model 0
-                                       ? jump_target(qc, n3, n4, n5, n6, u2, randDOrS, randDir, rand3, kick)
-                                       : jump_target_pump(qc, n3, n4, n5, n6, u2, randDOrS, randDir, rand3, kick);
+                return (DPPX || qc.model == 0)            // DPPX: model 0
+                           ? jump_target(qc, n3, n4, n5, n6, u2, randDOrS, randDir, rand3, jkick)
+                           : jump_target_pump(qc, n3, n4, n5, n6, u2, randDOrS, randDir, rand3, jkick);
+            };
+            if constexpr (JUNI && MDQT_JUMP_UNIFORM) {
+            // A wave-uniform choice.  No ion of the wave jumps (the common case): the no-jump substep,
+            // one basic block with the pipelined next_phase().  Some ion jumps: every lane runs ONE
+            // straight-line block — the Runge-Kutta stages (kept by the ions that do not jump), the
+            // jump's draws and target (kept by those that do), per-lane selects, and one next_phase()
+            // on the selected kick — instead of both sides of a per-lane branch, each with its own
+            // next_phase().  A lane's values come from the same operations on the same operands
+            // either way (an ion's 16 lanes jump together, and every cross-lane move stays inside
+            // them): bit-identical to the per-lane branch.
+            auto jump_substep = [&](auto tape) {
+                const double kick_rk = rk_kick();
+                const cxd w_rk = rk_stages();
+                double kick_j;
+                const int target = jump(tape, kick_j);
+                w = {nojump ? w_rk.re : (st == target ? 1. : 0.), nojump ? w_rk.im : 0.};
+                kick = nojump ? kick_rk : kick_j;
+                tPart = nojump ? tPart : 0.;
+                next_phase();
+            };
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(!nojump) == 0, 1)) {
+                kick = rk_kick();
+                next_phase();
+                w = rk_stages();
+            } else if (a.U) {
+                jump_substep(std::true_type{});
+            } else {
+                jump_substep(std::false_type{});
+            }
+            } else if (nojump) {
+                kick = rk_kick();
+                next_phase();
+                w = rk_stages();
+            } else {                                  // quantum jump (:573-703)
+                tPart = 0;
+                int target;
+                if (a.U) target = jump(std::true_type{}, kick);
+                else target = jump(std::false_type{}, kick);
                 w = {st == target ? 1. : 0., 0.};
                 next_phase();
             }
@@ -1008,23 +1060,23 @@ hipError_t launch_tag_spin_up(const double* psi, int n, int S, uint64_t gid0, ui
 // bytes of scratch per lane and its launch is 7 % shorter at 8 jobs of N0 = 3500: Ensemble option
 // "qt_waves" 3, A/B in docs/PROGRAMS.md; four waves per SIMD, 128 VGPRs and 176 bytes, was 57 % longer
 // and is not built).  The default set keeps the single-job kernels' budget and has no scratch.
-#define LANE_ENS_KERNELS(SUFFIX, ATTR)                                                                              \
+#define LANE_ENS_KERNELS(SUFFIX, ATTR, JUNI)                                                                        \
     template <bool DPPX, bool FAST>                                                                                 \
     __global__ __launch_bounds__(256) ATTR void k_substeps_lanes_r_ens##SUFFIX(const SubstepArgs* __restrict__ jobs, \
                                                                                const FastTab* __restrict__ tab) {   \
         const SubstepArgs& a = jobs[blockIdx.y];                                                                    \
         if ((int)blockIdx.x * kLaneIons >= a.n) return;                                                             \
-        lane_substeps<DPPX, FAST, false>(a, tab, blockIdx.x);                                                       \
+        lane_substeps<DPPX, FAST, false, false, false, false, JUNI>(a, tab, blockIdx.x);                            \
     }                                                                                                               \
     template <bool DPPX, bool EDZ, bool NORN = false>                                                               \
     __global__ __launch_bounds__(256) ATTR void k_substeps_lanes_im_ens##SUFFIX(const SubstepArgs* __restrict__ jobs, \
                                                                                 const FastTab* __restrict__ tab) {  \
         const SubstepArgs& a = jobs[blockIdx.y];                                                                    \
         if ((int)blockIdx.x * kLaneIons >= a.n) return;                                                             \
-        lane_substeps<DPPX, true, false, true, EDZ, NORN>(a, tab, blockIdx.x);                                      \
+        lane_substeps<DPPX, true, false, true, EDZ, NORN, JUNI>(a, tab, blockIdx.x);                                \
     }
-LANE_ENS_KERNELS(, LANE_WPE_ATTR)
-LANE_ENS_KERNELS(_w3, __attribute__((amdgpu_waves_per_eu(3, 3))))
+LANE_ENS_KERNELS(, LANE_WPE_ATTR, true)
+LANE_ENS_KERNELS(_w3, __attribute__((amdgpu_waves_per_eu(3, 3))), false)   // (lane_substeps: JUNI)
 #undef LANE_ENS_KERNELS
 
 // The lane kernels of launch_substeps_r's mode 2, model 0, over an ensemble: `jobs` is the device array of
