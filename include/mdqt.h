@@ -259,7 +259,7 @@ int         mdqt_get_spin_up_list(mdqt_ctx* c, int* tags, int* n_up);
  *                     (N - 1) g(L/2 (1 - 2^-20)) stays inside the budget) the pair terms in f32;
  *                     each shell's bound <= 10^-k; k = 13 default, 0 = off.  "force_ufar_radius",
  *                     "force_ufar32_radius", "force_ufar_bound" (both shells)
- *   "force_form_mode": how the four tiers' radii are bounded (round 6).  1 (default, with
+ *   "force_form_mode": how the four tiers' radii are bounded (round 6).  2 is the default.  1 (with
  *                     force_tail_mode 1, spatial order and the fast variant) = measured and
  *                     enforced: every force call's per-sub-tile sums also hold, for each sub-block
  *                     evaluated in an error-bounded form, n g(gap) err_form(gap); they are held to
@@ -272,8 +272,9 @@ int         mdqt_get_spin_up_list(mdqt_ctx* c, int* tags, int* n_up);
  *                     constants the model's; "force_form_measured" 1 where mode 1 applies.  2 = as
  *                     1, and where the tail skips nothing (r_t = L/2) the active tiers share its
  *                     unused 10^-force_tail_exp equally (each tier's eps 10^-k + that share), so
- *                     every configuration's per-ion total is the one an active tail has.  0 = the
- *                     a-priori radii above
+ *                     every configuration's per-ion total is the one an active tail has: with the
+ *                     default exponents, where the tail is exact (C3 / C5) the per-ion bound under
+ *                     this default is 1.5e-12, not mode 1's 5e-13.  0 = the a-priori radii above
  *   "qt_enabled":     1 = qstep() runs in the substeps, 0 = skipped (t still advances): the
  *                     pumping programs' pump window (randomFrozenStartTag408Linear.cpp main)
  *   "qt_math":        0 = the reference's exact operations, 1 = FMA-contracted with a refined

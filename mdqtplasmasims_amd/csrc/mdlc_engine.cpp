@@ -14,18 +14,10 @@
 #include <vector>
 
 #include "../../include/mdlc.h"
-#include "mdqt_internal.hpp"
+#include "mdqt_ctx.hpp"   // HIPCHK, mdqt::set_error
 #include "mdqt_mt32.hpp"
-#include "mdqt_writer.hpp"
 
 using namespace mdqt;
-
-#define HIPCHK(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess)                                                                               \
-            return set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
-    } while (0)
 
 struct mdlc_ctx {
     mdlc_params p;

@@ -17,17 +17,10 @@
 #include <vector>
 
 #include "../../include/mdmc.h"
-#include "mdqt_internal.hpp"
+#include "mdqt_ctx.hpp"   // HIPCHK, mdqt::set_error
 #include "mdqt_mt32.hpp"   // Mt32: the reference's std::mt19937 with the state in plain view
 
 using namespace mdqt;
-
-#define HIPCHK(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess)                                                                               \
-            return set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
-    } while (0)
 
 struct mdmc_ctx {
     mdmc_params p;

@@ -1,7 +1,6 @@
 // mdqt_ensemble — J independent jobs of the SpeedUp program stepped by ONE force launch and ONE QT launch
-// per MD step (include/mdqt.h, "ensembles").  Included at the end of mdqt_engine.cpp: it works on
-// mdqt_ctx's internals and on the argument helpers the single-job path uses (n3_force_args,
-// substep_args), so a member's launch arguments are the ones its own mdqt_forces / mdqt_substeps
+// per MD step (include/mdqt.h, "ensembles").  It works on mdqt_ctx's internals (mdqt_ctx.hpp) and on
+// the argument helpers the single-job path uses (mdqt_step.cpp: n3_force_args, substep_args), so a member's launch arguments are the ones its own mdqt_forces / mdqt_substeps
 // would pass — which is the whole bit-identity argument: the batched kernels run the single-job
 // kernels' bodies on those arguments (mdqt_forces.hip k_pairs_n3_ens, mdqt_qtfast.hip LANE_ENS_KERNELS).
 //
@@ -15,42 +14,16 @@
 // its copy has completed.  mdqt_ensemble_substeps and mdqt_ensemble_run copy one launch's blocks just
 // before it; mdqt_ensemble_md_steps builds the blocks of up to 64 MD steps ahead and copies them at once
 // (ens_md_steps has the reason and the numbers).
-#pragma once
 
-struct mdqt_ensemble {
-    std::vector<mdqt_ctx*> jobs;
-    int dev = 0;
-    hipStream_t stream = nullptr;                  // jobs[0]'s own stream, shared by every member
-    std::unique_ptr<FileWriter> writer;            // the members' output files (<= 16 threads in all)
-    N3Args* dForce = nullptr;                      // [J] the batched force launch's blocks (Newton-3 members, packed)
-    SubstepArgs* dSub = nullptr;                   // [sub_blocks] the batched QT launches' blocks: [launch][J]
-    int sub_blocks = 0;                            // max(J, 1024): mdqt_ensemble_md_steps builds launches ahead
-    std::vector<N3Args> force_held;                // what dForce holds
-    static constexpr int kRing = 8;
-    char* ring = nullptr;                          // pinned, kRing slots of slot_bytes
-    size_t slot_bytes = 0;
-    hipEvent_t ring_ev[kRing] = {};
-    bool ring_used[kRing] = {};
-    unsigned ring_pos = 0;
-    int qt_waves = 0;                              // option "qt_waves": register budget of the production QT instance
-    bool timing = false;
-    std::vector<hipEvent_t> evpool[2];             // 0 = force launches, 1 = QT launches (start, stop, ...)
-    int evused[2] = {0, 0};
-};
+#include <algorithm>
+
+#include "mdqt_ctx.hpp"
+
+using namespace mdqt;
 
 namespace {
 
 constexpr int kEnsembleMaxJobs = 1024;
-
-int ens_job_params(const mdqt_params* base, int k, mdqt_params* out) {
-    if (!base || !out) return fail("mdqt_ensemble_job_params: NULL argument");
-    if (k < 0 || k >= kEnsembleMaxJobs) return fail("mdqt_ensemble_job_params: job index %d outside [0, %d)", k, kEnsembleMaxJobs);
-    mdqt_params p = *base;
-    p.job = base->job + (uint32_t)k;               // the array index, SpeedUp:1145
-    p.seed = base->seed + (uint32_t)k;             // srand48(time + job), SpeedUp:1219
-    *out = p;
-    return 0;
-}
 
 // a pinned slot nobody reads any more
 int ens_ring_slot(mdqt_ensemble* e, char** slot, int* idx) {
@@ -68,39 +41,27 @@ int ens_upload(mdqt_ensemble* e, void* dst, const void* src_slot, size_t bytes, 
     return 0;
 }
 
-int ens_take_events(mdqt_ensemble* e, int k, hipEvent_t* e0, hipEvent_t* e1) {
-    auto& pool = e->evpool[k];
-    while ((int)pool.size() < e->evused[k] + 2) {
-        hipEvent_t ev;
-        HIPCHK(hipEventCreateWithFlags(&ev, kTimingEventFlags));
-        pool.push_back(ev);
-    }
-    *e0 = pool[e->evused[k]++];
-    *e1 = pool[e->evused[k]++];
-    return 0;
-}
-
 // Every batched call: the members still are what the batched kernels cover, and still in lockstep.
 // The pending-force state is NOT compared: it is per job by design (a one-tile job never has pending
 // slots; mdqt_get_state on a member settles that member's) and each QT block takes its own nseg.
 int ens_check(const mdqt_ensemble* e, const char* what) {
-    if (!e) return fail("%s: NULL ensemble", what);
+    if (!e) return set_error("%s: NULL ensemble", what);
     const mdqt_ctx* a = e->jobs[0];
     for (size_t k = 0; k < e->jobs.size(); ++k) {
         const mdqt_ctx* s = e->jobs[k];
-        if (s->stream != e->stream) return fail("%s: job index %zu was moved to another stream", what, k);
+        if (s->stream != e->stream) return set_error("%s: job index %zu was moved to another stream", what, k);
         if (s->overlap_opt || s->fused_opt)
-            return fail("%s: job index %zu has the option overlap / fused_step set (one system per launch)", what, k);
-        if (s->qt_math != 2) return fail("%s: job index %zu has qt_math %d (the batched QT kernels are qt_math 2)", what, k, s->qt_math);
-        if (s->substep_mode == 1) return fail("%s: job index %zu has substep_kernel 1 (the batched QT kernels are the lane kernels)", what, k);
-        if (s->N < 1) return fail("%s: job index %zu has no ions (mdqt_ensemble_init or mdqt_set_state first)", what, k);
+            return set_error("%s: job index %zu has the option overlap / fused_step set (one system per launch)", what, k);
+        if (s->qt_math != 2) return set_error("%s: job index %zu has qt_math %d (the batched QT kernels are qt_math 2)", what, k, s->qt_math);
+        if (s->substep_mode == 1) return set_error("%s: job index %zu has substep_kernel 1 (the batched QT kernels are the lane kernels)", what, k);
+        if (s->N < 1) return set_error("%s: job index %zu has no ions (mdqt_ensemble_init or mdqt_set_state first)", what, k);
         if (s->use_n3b || s->N > 65536)
-            return fail("%s: job index %zu has N = %d: beyond the Newton-3 tile scheme (N <= 65,536)", what, k, s->N);
-        if (s->force_arrive || s->sub_stream || !s->local.empty()) return fail("%s: job index %zu is part of another scheme", what, k);
+            return set_error("%s: job index %zu has N = %d: beyond the Newton-3 tile scheme (N <= 65,536)", what, k, s->N);
+        if (s->force_arrive || s->sub_stream || !s->local.empty()) return set_error("%s: job index %zu is part of another scheme", what, k);
         if (memcmp(&s->t, &a->t, sizeof(double)) || s->qidx != a->qidx || s->c0 != a->c0)
-            return fail("%s: job index %zu is out of step with job index 0 (t %.17g / %.17g, qstep %llu / %llu, c0 %d / %d): "
-                        "a member stepped on its own ends the ensemble's stepping",
-                        what, k, s->t, a->t, (unsigned long long)s->qidx, (unsigned long long)a->qidx, s->c0, a->c0);
+            return set_error("%s: job index %zu is out of step with job index 0 (t %.17g / %.17g, qstep %llu / %llu, c0 %d / %d): "
+                             "a member stepped on its own ends the ensemble's stepping",
+                             what, k, s->t, a->t, (unsigned long long)s->qidx, (unsigned long long)a->qidx, s->c0, a->c0);
     }
     return 0;
 }
@@ -121,7 +82,7 @@ int ens_force_blocks(mdqt_ensemble* e, EnsForce& f) {
         if (!s->use_n3) continue;
         N3Args a;
         if (n3_force_args(s, a)) return -1;
-        if (f.variant >= 0 && f.variant != s->force_variant) return fail("mdqt_ensemble_forces: job index %d has another force_kernel", k);
+        if (f.variant >= 0 && f.variant != s->force_variant) return set_error("mdqt_ensemble_forces: job index %d has another force_kernel", k);
         f.variant = s->force_variant;
         f.guard = f.guard || a.guard;
         f.maxp = std::max(f.maxp, a.npairs);
@@ -142,7 +103,7 @@ int ens_force_blocks(mdqt_ensemble* e, EnsForce& f) {
 int ens_force_launch(mdqt_ensemble* e, const EnsForce& f) {
     if (f.h.empty()) return 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e->timing && ens_take_events(e, 0, &e0, &e1)) return -1;
+    if (e->timing && take_events(e->evpool[0], e->evused[0], &e0, &e1)) return -1;
     HIPCHK(launch_forces_n3_ens(e->dForce, (int)f.h.size(), f.maxp, f.variant, f.guard, e->stream, e0, e1));
     return 0;
 }
@@ -180,7 +141,7 @@ int ens_substeps(mdqt_ensemble* e, int n) {
         }
         if (ens_upload(e, e->dSub, slot, (size_t)J * sizeof(SubstepArgs), idx)) return -1;
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (e->timing && ens_take_events(e, 1, &e0, &e1)) return -1;
+        if (e->timing && take_events(e->evpool[1], e->evused[1], &e0, &e1)) return -1;
         int inst = 0;
         HIPCHK(launch_substeps_r_ens(e->dSub, h[0], J, maxn, e->jobs[0]->dFTab, e->qt_waves, e->stream, e0, e1, &inst));
         for (int k = 0; k < J; ++k) {
@@ -206,11 +167,7 @@ int ens_range_flags(mdqt_ensemble* e, bool drain = true) {
             e->jobs[k]->guard = true;
             if (first < 0) first = k;
         }
-    if (first >= 0)
-        return fail("job index %d: positions left [-L/8, 9L/8] during the run (ion displacement > L/8 per half "
-                    "substep); pair range checks are now on, but forces since the last sync used the in-box "
-                    "minimum image", first);
-    return 0;
+    return first >= 0 ? range_flag_error(first) : 0;
 }
 
 // n MD steps without the argument hand-off inside them.  A copy between two launches costs more than
@@ -271,7 +228,7 @@ int ens_md_steps(mdqt_ensemble* e, int n) {
             if (ens_force_launch(e, f)) return -1;
             for (int c = 0; c < per_step; ++c, ++l) {
                 hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (e->timing && ens_take_events(e, 1, &e0, &e1)) return -1;
+                if (e->timing && take_events(e->evpool[1], e->evused[1], &e0, &e1)) return -1;
                 HIPCHK(launch_substeps_r_ens(e->dSub + (size_t)l * J, h[(size_t)l * J], J, maxn, e->jobs[0]->dFTab,
                                              e->qt_waves, e->stream, e0, e1, &inst));
             }
@@ -288,7 +245,13 @@ int ens_md_steps(mdqt_ensemble* e, int n) {
 }  // namespace
 
 extern "C" int mdqt_ensemble_job_params(const mdqt_params* base, int k, mdqt_params* out) {
-    return ens_job_params(base, k, out);
+    if (!base || !out) return set_error("mdqt_ensemble_job_params: NULL argument");
+    if (k < 0 || k >= kEnsembleMaxJobs) return set_error("mdqt_ensemble_job_params: job index %d outside [0, %d)", k, kEnsembleMaxJobs);
+    mdqt_params p = *base;
+    p.job = base->job + (uint32_t)k;               // the array index, SpeedUp:1145
+    p.seed = base->seed + (uint32_t)k;             // srand48(time + job), SpeedUp:1219
+    *out = p;
+    return 0;
 }
 
 extern "C" void mdqt_ensemble_destroy(mdqt_ensemble* e) {
@@ -310,31 +273,31 @@ extern "C" void mdqt_ensemble_destroy(mdqt_ensemble* e) {
 }
 
 extern "C" int mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out) {
-    if (!p || !out) return fail("mdqt_ensemble_create: NULL argument");
+    if (!p || !out) return set_error("mdqt_ensemble_create: NULL argument");
     *out = nullptr;
-    if (njobs < 1 || njobs > kEnsembleMaxJobs) return fail("mdqt_ensemble_create: njobs must be 1 .. %d", kEnsembleMaxJobs);
-    if (p->world_size != 1) return fail("mdqt_ensemble_create: world_size must be 1 (an ensemble's jobs are whole systems on one device)");
+    if (njobs < 1 || njobs > kEnsembleMaxJobs) return set_error("mdqt_ensemble_create: njobs must be 1 .. %d", kEnsembleMaxJobs);
+    if (p->world_size != 1) return set_error("mdqt_ensemble_create: world_size must be 1 (an ensemble's jobs are whole systems on one device)");
     if (p->rng_mode != 1)
-        return fail("mdqt_ensemble_create: rng_mode must be 1 (Philox): the drand48 order needs one substep per launch "
-                    "and a resolve kernel per job");
-    if (p->qt_model != 0) return fail("mdqt_ensemble_create: qt_model must be 0 (the SpeedUp program; the pump programs are not batched)");
+        return set_error("mdqt_ensemble_create: rng_mode must be 1 (Philox): the drand48 order needs one substep per launch "
+                         "and a resolve kernel per job");
+    if (p->qt_model != 0) return set_error("mdqt_ensemble_create: qt_model must be 0 (the SpeedUp program; the pump programs are not batched)");
     std::unique_ptr<mdqt_ensemble, void (*)(mdqt_ensemble*)> e(new (std::nothrow) mdqt_ensemble(), mdqt_ensemble_destroy);
-    if (!e) return fail("mdqt_ensemble_create: out of memory");
+    if (!e) return set_error("mdqt_ensemble_create: out of memory");
     try {
         e->jobs.reserve((size_t)njobs);
         e->writer.reset(new FileWriter(std::min(16, 4 * njobs)));
     } catch (const std::exception& x) {
-        return fail("mdqt_ensemble_create: %s", x.what());
+        return set_error("mdqt_ensemble_create: %s", x.what());
     }
     for (int k = 0; k < njobs; ++k) {
         mdqt_params pk;
         mdqt_ctx* s = nullptr;
-        if (ens_job_params(p, k, &pk) || mdqt_create(&pk, &s)) return -1;
+        if (mdqt_ensemble_job_params(p, k, &pk) || mdqt_create(&pk, &s)) return -1;
         e->jobs.push_back(s);
         s->shared_writer = e->writer.get();
         if (k == 0) { e->dev = s->dev; e->stream = s->own; }
-        if (s->qt_math != 2) return fail("mdqt_ensemble_create: qt_math must be 2");
-        if (s->overlap_opt || s->fused_opt) return fail("mdqt_ensemble_create: the options overlap / fused_step are one system per launch");
+        if (s->qt_math != 2) return set_error("mdqt_ensemble_create: qt_math must be 2");
+        if (s->overlap_opt || s->fused_opt) return set_error("mdqt_ensemble_create: the options overlap / fused_step are one system per launch");
         mdqt_set_stream(s, (void*)e->stream);
     }
     HIPCHK(hipSetDevice(e->dev));
@@ -343,7 +306,7 @@ extern "C" int mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemb
     if (hipMalloc(&e->dForce, (size_t)njobs * sizeof(N3Args)) != hipSuccess ||
         hipMalloc(&e->dSub, (size_t)e->sub_blocks * sizeof(SubstepArgs)) != hipSuccess ||
         hipHostMalloc((void**)&e->ring, e->slot_bytes * mdqt_ensemble::kRing, hipHostMallocDefault) != hipSuccess)
-        return fail("mdqt_ensemble_create: allocating the argument blocks of %d jobs failed", njobs);
+        return set_error("mdqt_ensemble_create: allocating the argument blocks of %d jobs failed", njobs);
     for (hipEvent_t& ev : e->ring_ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence));
     *out = e.release();
     return 0;
@@ -353,16 +316,16 @@ extern "C" int mdqt_ensemble_size(const mdqt_ensemble* e) { return e ? (int)e->j
 
 extern "C" mdqt_ctx* mdqt_ensemble_job(mdqt_ensemble* e, int k) {
     if (!e || k < 0 || k >= (int)e->jobs.size()) {
-        fail("mdqt_ensemble_job: job index %d outside the ensemble", k);
+        set_error("mdqt_ensemble_job: job index %d outside the ensemble", k);
         return nullptr;
     }
     return e->jobs[(size_t)k];
 }
 
 extern "C" int mdqt_ensemble_set_option(mdqt_ensemble* e, const char* name, int value) {
-    if (!e || !name) return fail("mdqt_ensemble_set_option: NULL argument");
+    if (!e || !name) return set_error("mdqt_ensemble_set_option: NULL argument");
     if (!strcmp(name, "qt_waves")) {
-        if (value != 0 && value != 3) return fail("qt_waves must be 0 (the single-job kernel's register budget) or 3");
+        if (value != 0 && value != 3) return set_error("qt_waves must be 0 (the single-job kernel's register budget) or 3");
         e->qt_waves = value;
         return 0;
     }
@@ -372,7 +335,7 @@ extern "C" int mdqt_ensemble_set_option(mdqt_ensemble* e, const char* name, int 
 }
 
 extern "C" int mdqt_ensemble_init(mdqt_ensemble* e) {             // init() of every job, SpeedUp:289-348
-    if (!e) return fail("NULL ensemble");
+    if (!e) return set_error("NULL ensemble");
     for (mdqt_ctx* s : e->jobs)                     // one after the other: a job's sampling already takes up to 16 threads
         if (mdqt_init(s)) return -1;
     return 0;
@@ -386,7 +349,7 @@ extern "C" int mdqt_ensemble_forces(mdqt_ensemble* e) {           // forces() of
 
 extern "C" int mdqt_ensemble_substeps(mdqt_ensemble* e, int n) {  // n x (step(); qstep()), SpeedUp:1376-1377
     if (ens_check(e, "mdqt_ensemble_substeps")) return -1;
-    if (n < 0) return fail("negative substep count");
+    if (n < 0) return set_error("negative substep count");
     HIPCHK(hipSetDevice(e->dev));
     return ens_substeps(e, n);
 }
@@ -398,15 +361,15 @@ extern "C" int mdqt_ensemble_md_steps(mdqt_ensemble* e, int n) {  // mdqt_md_ste
 }
 
 extern "C" int mdqt_ensemble_synchronize(mdqt_ensemble* e) {
-    if (!e) return fail("NULL ensemble");
+    if (!e) return set_error("NULL ensemble");
     HIPCHK(hipSetDevice(e->dev));
     return ens_range_flags(e);
 }
 
-// main()'s time loop (SpeedUp:1248-1383) as mdqt_run has it (mdqt_engine.cpp), for every job at once:
+// main()'s time loop (SpeedUp:1248-1383) as mdqt_run has it (mdqt_io.cpp), for every job at once:
 // the members are in lockstep, so job 0's t and c0 drive the loop
 extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
-    if (!e) return fail("NULL ensemble");
+    if (!e) return set_error("NULL ensemble");
     for (mdqt_ctx* s : e->jobs)
         if (mdqt_setup_directories(s)) return -1;
     if (e->jobs[0]->p.newRun == 1) {
@@ -423,7 +386,6 @@ extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
     const double tend = a->p.tmax + 0.0009;
     const int sf = a->p.sampleFreq, ratio = a->ratio;
     int tsc = ratio;                                                                    // :1235
-    long steps = 0;
     while (a->t <= tend) {                                                              // :1248
         if ((a->c0 + 1) % sf == 0 && tsc == 1)                                          // :1365
             for (mdqt_ctx* s : e->jobs)
@@ -433,15 +395,10 @@ extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
             if (ens_forces(e)) return -1;
             for (mdqt_ctx* s : e->jobs) s->c0++;
             tsc = 0;
-            steps++;
         }
         // fuse the following iterations while they are pure step();qstep() (App. C-9)
-        int n = 0, ts = tsc;
-        double tt = a->t;
-        do {
-            n++; ts++; tt += a->dtQ;
-        } while (n < MAXSUB && tt <= tend && !((a->c0 + 1) % sf == 0 && ts == 1) && ts != ratio);
-        if (ens_substeps(e, n)) return -1;                                             // :1376-1377
+        const int n = fusable_substeps(a, tend, a->c0, tsc);
+        if (ens_substeps(e, n)) return -1;                                            // :1376-1377
         tsc += n;
     }
     for (mdqt_ctx* s : e->jobs)
@@ -450,7 +407,7 @@ extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
 }
 
 extern "C" int mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on) {
-    if (!e) return fail("NULL ensemble");
+    if (!e) return set_error("NULL ensemble");
     e->timing = on > 0;
     e->evused[0] = e->evused[1] = 0;
     return 0;
@@ -459,8 +416,8 @@ extern "C" int mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on) {
 // the two batched kernels' own durations (their dispatch timestamps) since the last call: out[6] = force
 // ms (sum), force launches, QT ms (sum), QT launches, median force launch (ms), median QT launch (ms); resets
 extern "C" int mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n) {
-    if (!e || !out) return fail("mdqt_ensemble_kernel_times: NULL argument");
-    if (n < 6) return fail("mdqt_ensemble_kernel_times: need 6 doubles");
+    if (!e || !out) return set_error("mdqt_ensemble_kernel_times: NULL argument");
+    if (n < 6) return set_error("mdqt_ensemble_kernel_times: need 6 doubles");
     HIPCHK(hipSetDevice(e->dev));
     HIPCHK(hipStreamSynchronize(e->stream));
     for (int k = 0; k < 2; ++k) {

@@ -1,5 +1,5 @@
 // init() sampling of laserCoolingPlusExpansionMDQTSpeedUp.cpp (:289-335) from one drand48 stream,
-// sequential or in parallel with identical results (see mdqt_engine.cpp, mdqt_init).  Host only;
+// sequential or in parallel with identical results (see mdqt_engine.cpp:mdqt_init).  Host only;
 // header so that tests/native/init_check.cpp can compare the two paths at large N on the CPU.
 #pragma once
 

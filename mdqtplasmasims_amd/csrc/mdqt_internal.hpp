@@ -1,4 +1,4 @@
-// Internal interface between the host engine (mdqt_engine.cpp) and the gfx950 kernels
+// Internal interface between the host engine (mdqt_ctx.hpp and its sources) and the gfx950 kernels
 // (mdqt_kernels.hip).  Plain structs passed BY VALUE as kernel arguments (no __constant__
 // globals: several contexts with different parameters may live in one process).
 #pragma once
@@ -247,7 +247,7 @@ __device__ __forceinline__ double exp2_neg(double t) {
 }
 constexpr double kNegLog2e = -1.4426950408889634;   // -log2(e)
 
-// Far tile pairs of the Newton-3 blocks (box gap >= the far radius, mdqt_engine.cpp far_radius):
+// Far tile pairs of the Newton-3 blocks (box gap >= the far radius, mdqt_force_plan.cpp far_radius_l):
 // every pair term there is below g(r_far), so a term error of relative size kFarRelErr is below
 // g(r_far) kFarRelErr and an ion's force moves by at most (N - 1) g(r_far) kFarRelErr (<= 1e-13 by
 // the choice of r_far).  Their pair form: rsq1 (v_rsq_f64 + ONE Newton step: 1e-14 relative) and
@@ -258,7 +258,7 @@ constexpr double kFarRelErr = 3e-9;
 // raw rsq's e <= kRsqRawErr: <= kRsq1RelErr — and 2^t by the 64-entry table with a degree-4 series
 // (2.53e-15 measured, + the table entry's and the product's rounding: kTab4RelErr).  t carries ri's
 // error times r/lDeb, the force factor 3 ri's: a term is within (r/lDeb + 3)(kRsq1RelErr + 2^-52) +
-// kTab4RelErr of itself (mdqt_engine.cpp far_err, level 5).
+// kTab4RelErr of itself (mdqt_force_plan.cpp far_err, level 5).
 constexpr double kRsq1RelErr = 2.2e-14;
 // 2^t of the exact (and mid) pair forms by the 64-entry LDS table (mdqt_pairs.hpp exp2_neg_cut_tab)
 #ifndef MDQT_EXP_TAB
@@ -313,7 +313,7 @@ constexpr double kRsqF32RelErr = 0x1p-23;
 constexpr double kUfar32A = 22. * 0x1p-24;
 constexpr double kUfar32B = 52. * 0x1p-24;
 // a term's relative error in the pair form of plan level e (0 exact, 1 mid, 2 far, 3 very far, 4 ultra
-// far, 5 ultra far in f32) as kFormErrA[e] r/lDeb + kFormErrB[e] (mdqt_engine.cpp far_err; the measured
+// far, 5 ultra far in f32) as kFormErrA[e] r/lDeb + kFormErrB[e] (mdqt_force_plan.cpp far_err; the measured
 // form bound of k_n3b_plan, force_form_mode 1)
 constexpr double kFormErrA[6] = {0., kRsq1RelErr + 0x1p-52, 0., kRsqRawErr, kRsqRawErr + 0x1p-24, kUfar32A};
 constexpr double kFormErrB[6] = {0., 3. * (kRsq1RelErr + 0x1p-52) + kTab4RelErr, kFarRelErr,
@@ -449,7 +449,7 @@ struct N3BArgs {
                         // as exact as the exact form's r < Rcut), not on their low-precision r
     double Rskip;       // force tile pairs whose boxes are >= Rskip apart are skipped (use_sort 1):
                         // Rcut exactly (every skipped pair is beyond L/2), or the error-bounded tail
-                        // radius r_t < L/2 of mdqt_engine.cpp tail_radius (potentials: always Rcut)
+                        // radius r_t < L/2 of mdqt_force_plan.cpp tail_radius (potentials: always Rcut)
     double* tailb;      // force_tail_mode 1: per 16-ion sub-tile [4T], the sum over the pairs the call
                         // drops inside L/2 (tail-skipped tile pairs, skipped sub-tile groups) of
                         // n_b g(sub-block gap) — the measured bound on what each of its ions loses

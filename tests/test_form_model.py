@@ -1,4 +1,4 @@
-"""force_form_mode 1's tier radii (round 6; mdqt_engine.cpp model_tier_radius, exported as
+"""force_form_mode 1's tier radii (round 6; mdqt_force_plan.cpp:model_tier_radius, exported as
 mdqt_tier_radius_model — host arithmetic, no device): against a numpy restatement of the density model,
 against the radii the GPU runs reported (profiles/r06f_form_census.txt), and the invariants the
 enforcement relies on (the model radius never beyond the a-priori cap, the tiers in order, wider with a

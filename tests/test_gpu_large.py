@@ -93,7 +93,7 @@ def test_large_config_forces_and_interval(cfg, orc):
     dabs = np.abs(F[:, idx] - G).max()
     err = dabs / np.abs(G).max()
     # the error-bounded tail (force_tail_exp, default 12): tile pairs >= r_t apart are skipped, every
-    # ion's force moves by at most `bound` (mdqt_engine.cpp tail_radius; 0 where r_t = L/2)
+    # ion's force moves by at most `bound` (mdqt_force_plan.cpp:tail_radius; 0 where r_t = L/2)
     # and the far pair form (force_far_exp, default 13): <= far bound more
     rt, bound = s.const("force_skip_radius"), s.const("force_tail_bound")
     rf, fbound = s.const("force_far_radius"), s.const("force_far_bound")
@@ -209,7 +209,7 @@ def test_one_axis_image_instance_matches_per_pair_image():
 def test_error_bounded_tail_and_far_form(cfg):
     """The error-bounded parts of the Newton-3 block forces against the exact sum to L/2 on EVERY
     ion: the skip radius r_t < L/2 (force_tail_exp 12: |dF_i| <= (N - 1) g(r_t) <= 1e-12,
-    mdqt_engine.cpp tail_radius; active at N ~ 1e6), the far pair form beyond r_far (force_far_exp
+    mdqt_force_plan.cpp:tail_radius; active at N ~ 1e6), the far pair form beyond r_far (force_far_exp
     13: (N - 1) g(r_far) kFarRelErr <= 1e-13) and the very-far form beyond r_vfar (force_vfar_exp
     13: (N - 1) g(r) ((r/lDeb + 3) kRsqRawErr + kExp5RelErr) <= 1e-13), the ultra-far forms and the
     mid form beyond r_mid (force_mid_exp 13, round 4: (N - 1) g(r) ((r/lDeb + 3)(kRsq1RelErr + 2^-52)
@@ -285,7 +285,7 @@ def test_error_bounded_tail_and_far_form(cfg):
 @pytest.mark.parametrize("cfg", ["C4", "C5"])
 def test_form_bound_measured_and_enforced(cfg):
     """force_form_mode 1 and 2 (round 6; 2 the default): the tiers' radii from the density model of the sums the
-    plan measures (mdqt_engine.cpp tier_radius) — below the a-priori radii of mode 0 — and every
+    plan measures (mdqt_force_plan.cpp:tier_radius) — below the a-priori radii of mode 0 — and every
     sub-block evaluated in an error-bounded form adding n_b g(gap) err_form(gap) to its sub-tiles' sums
     (k_n3b_plan), which k_tail_max holds to force_error_eps (the tail's eps where r_t < L/2 + 10^-13 per
     active tier; mode 2, where the tail skips nothing, each tier + a fifth of the tail's 1e-12), recomputing
@@ -340,7 +340,7 @@ def test_form_bound_measured_and_enforced(cfg):
 def clustered_state(N0, L, frac, rc, seed=5):
     """A deliberately clustered configuration: a fraction `frac` of the N0 ions uniform in a ball of
     radius rc at the box centre, the rest uniform in the box, in random index order — far from the
-    uniform density the skip radius's model (mdqt_engine.cpp tail_radius_sum) assumes.  V = 0,
+    uniform density the skip radius's model (mdqt_force_plan.cpp:tail_radius_sum) assumes.  V = 0,
     every psi = |0>, tPart = 0, t = 0."""
     rng = np.random.default_rng(seed)
     nc = int(frac * N0)

@@ -68,7 +68,7 @@ def n3b_tile_pairs(N, world, rank, BW=8, cuts=None):
 
 
 def balance_cuts(w, world):
-    """mdqt_engine.cpp:n3b_balance: cut points with each rank's prefix work nearest r / W of the total,
+    """mdqt_force_plan.cpp:n3b_balance: cut points with each rank's prefix work nearest r / W of the total,
     at least one block per rank"""
     pre = np.concatenate([[0.0], np.cumsum(np.asarray(w, dtype=float))])
     NB, tot = len(w), pre[-1]

@@ -1,11 +1,11 @@
 """Load balance of the sharded Newton-3 block kernel, measured on one GPU.
 
-Rank r of W owns blocks [r NB / W, (r + 1) NB / W) (mdqt_engine.cpp plan sizing); its block kernel
+Rank r of W owns blocks [r NB / W, (r + 1) NB / W) (mdqt_engine.cpp:choose_segments); its block kernel
 does the evaluated lane-steps of those blocks' workgroups.  mdqt_force_block_work at world 1 gives
 every block's evaluated lane-steps for the reference's init() positions (k_n3b_census, the block
 kernel's own classification), so each partition's per-rank work follows; reported: max / mean over
 the ranks for W = 2, 4, 8, with equal block counts and with the work-weighted ranges the engine takes
-(mdqt_engine.cpp n3b_balance, option force_balance), at init() and after 3 MD steps.
+(mdqt_force_plan.cpp:n3b_balance, option force_balance), at init() and after 3 MD steps.
 
     python tools/load_balance.py [c4 c5 c1m] > profiles/r05_load_balance.json
 """
@@ -31,7 +31,7 @@ def partition(work, W, cuts=None):
 
 
 def balance_cuts(w, W):
-    """mdqt_engine.cpp:n3b_balance's cut points (tests/test_n3b_protocol.py restates the same)"""
+    """mdqt_force_plan.cpp:n3b_balance's cut points (tests/test_n3b_protocol.py restates the same)"""
     pre = np.concatenate([[0.0], np.cumsum(np.asarray(w, dtype=float))])
     NB, tot = len(w), pre[-1]
     cut = [0] * (W + 1)
