@@ -125,6 +125,31 @@ int mdmc_tagged_moments_qt(mdmc_ctx* c, double out4[4], double* dist);
 int mdmc_get_psi(mdmc_ctx* c, double* psi);         /* [N][12][2] (re, im; states past the model's zero) */
 int mdmc_set_psi(mdmc_ctx* c, const double* psi);
 
+/* ---- ensembles ----
+ * The reference runs these programs as a Slurm array of independent jobs (exampleSlurmFile.slurm:3,16,
+ * `srun tagQuad $SLURM_ARRAY_TASK_ID`).  An ensemble holds njobs such jobs in one process: member k has
+ * job + k and seed + k, and its state and files are bit for bit those of its own run.  A single job's
+ * Metropolis anneal is one workgroup on one CU (the chain is sequential); the ensemble anneals all members
+ * with ONE launch of njobs workgroups, so N <= 6144 (the LDS-resident kernel).  The MD stages queue every
+ * member's own launches on its own stream, so they overlap on the chip.  Members need no lockstep: any
+ * mdmc_* call on a member between ensemble calls is legal and the member simply carries its state. */
+typedef struct mdmc_ensemble mdmc_ensemble;
+int       mdmc_ensemble_job_params(const mdmc_params* base, int k, mdmc_params* out); /* job+k, seed+k only; k in [0,1024) */
+int       mdmc_ensemble_create(const mdmc_params* p, int njobs, mdmc_ensemble** out); /* njobs x mdmc_create; 1..1024 */
+void      mdmc_ensemble_destroy(mdmc_ensemble* e);
+int       mdmc_ensemble_size(const mdmc_ensemble* e);
+mdmc_ctx* mdmc_ensemble_job(mdmc_ensemble* e, int k);      /* owned by the ensemble */
+int       mdmc_ensemble_init(mdmc_ensemble* e);            /* mdmc_init of every member */
+/* mdmc_monte_carlo of every member in batched launches; accepted [njobs] or NULL */
+int       mdmc_ensemble_monte_carlo(mdmc_ensemble* e, int nsteps, long long* accepted);
+int       mdmc_ensemble_md_steps(mdmc_ensemble* e, int nsteps);  /* mdmc_md_steps of every member, step by step */
+int       mdmc_ensemble_run(mdmc_ensemble* e, int verbose);      /* mdmc_run of every member, stage by stage */
+int       mdmc_ensemble_enable_timing(mdmc_ensemble* e, int on); /* timestamps on the anneal launches, stage timers */
+/* out[0..5): the anneal launches since the last call: sum (ms), count, median, min, max (ms);
+ * out[5..11): wall ms of the last run's stages (timing on): anneal, pre-record MD, QT pump, recorded MD,
+ * autocorrelations, the rest.  Fills min(n, 11) entries, n >= 3 */
+int       mdmc_ensemble_kernel_times(mdmc_ensemble* e, double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,18 @@ MDMC_SIGNATURES = [
     ("mdmc_tagged_moments_qt", C.c_int, [C.c_void_p, _dp, _dp]),
     ("mdmc_get_psi", C.c_int, [C.c_void_p, _dp]),
     ("mdmc_set_psi", C.c_int, [C.c_void_p, _dp]),
+    # ensembles of MC + MD jobs (the anneal of every chain in one launch)
+    ("mdmc_ensemble_job_params", C.c_int, [C.POINTER(MdmcParams), C.c_int, C.POINTER(MdmcParams)]),
+    ("mdmc_ensemble_create", C.c_int, [C.POINTER(MdmcParams), C.c_int, C.POINTER(C.c_void_p)]),
+    ("mdmc_ensemble_destroy", None, [C.c_void_p]),
+    ("mdmc_ensemble_size", C.c_int, [C.c_void_p]),
+    ("mdmc_ensemble_job", C.c_void_p, [C.c_void_p, C.c_int]),
+    ("mdmc_ensemble_init", C.c_int, [C.c_void_p]),
+    ("mdmc_ensemble_monte_carlo", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),
+    ("mdmc_ensemble_md_steps", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdmc_ensemble_run", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdmc_ensemble_enable_timing", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdmc_ensemble_kernel_times", C.c_int, [C.c_void_p, _dp, C.c_int]),
 ]
 
 # (name, restype, argtypes) of every symbol include/mdqt.h declares

@@ -7,6 +7,10 @@
 //
 // Runs main()'s stages (MCMD:1030-1167) on the GPU through include/mdmc.h and writes the same
 // directory tree and files (pairPairCorrStepNum%d.dat, temperature.dat, VAF.dat, ...).
+//
+//   --njobs=J runs the jobs <job> .. <job>+J-1 of the reference's Slurm array (exampleSlurmFile.slurm:3,16)
+//   as one ensemble (mdmc_ensemble_run: the J Metropolis chains annealed by one launch), job k seeded
+//   seed + k; each job's files are those of `mdmc <job>+k --seed=<seed>+k`.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,7 +29,9 @@ static void usage(void) {
             "                  [--anisotropyEstablishmentTime=10] [--anisotropyFromForcesRelaxSteps=2000]\n"
             "                  [--saveDirectory=data/] [--seed=<mt19937 seed; default time(NULL)+job>]\n"
             "                  [--device=-1] [--force_kernel=1] [--quiet=0]\n"
-            "                  [--qt_model=0|1|2|3] [--tpumpreal=2e-7] [--detuning=-2.5] [--Om=0.7]\n");
+            "                  [--qt_model=0|1|2|3] [--tpumpreal=2e-7] [--detuning=-2.5] [--Om=0.7]\n"
+            "       mdmc <job> --njobs=J [... as above]   jobs <job> .. <job>+J-1 as one ensemble (J in 1 .. 1024;\n"
+            "                  seeds seed .. seed+J-1; N <= 6144)\n");
 }
 
 int main(int argc, char** argv) {
@@ -42,6 +48,7 @@ int main(int argc, char** argv) {
     const double job = atof(argv[1]);                       // MCMD:1035
     p.job = (uint32_t)job;
     int seed_given = 0, quiet = 0;
+    long njobs = -1;                                        // --njobs: the jobs of an ensemble (-1: not given)
     for (int i = 2; i < argc; ++i) {
         const char* a = argv[i];
         if (strncmp(a, "--", 2) != 0 || !strchr(a, '=')) { usage(); return 2; }
@@ -63,6 +70,12 @@ int main(int argc, char** argv) {
 #undef DPAR
 #undef IPAR
         if (!strcmp(key, "quiet")) { quiet = atoi(v); continue; }
+        if (!strcmp(key, "njobs")) {
+            char* end = NULL;
+            njobs = strtol(v, &end, 10);
+            if (end == v || *end || njobs < 1 || njobs > 1024) { usage(); return 2; }
+            continue;
+        }
         if (!strcmp(key, "seed")) { p.seed = (uint32_t)strtoul(v, NULL, 10); seed_given = 1; continue; }
         if (!strcmp(key, "saveDirectory")) {
             strncpy(p.saveDirectory, v, sizeof(p.saveDirectory) - 1);
@@ -72,6 +85,17 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (!seed_given) p.seed = (uint32_t)(time(NULL) + job);   // the reference: std::random_device (:52)
+    if (njobs > 0) {
+        mdmc_ensemble* e = NULL;
+        if (mdmc_ensemble_create(&p, (int)njobs, &e) != 0) {
+            fprintf(stderr, "mdmc: %s\n", mdqt_last_error());
+            return 1;
+        }
+        const int rc = mdmc_ensemble_run(e, !quiet);
+        if (rc != 0) fprintf(stderr, "mdmc: %s\n", mdqt_last_error());
+        mdmc_ensemble_destroy(e);
+        return rc ? 1 : 0;
+    }
     mdmc_ctx* c = NULL;
     if (mdmc_create(&p, &c) != 0) {
         fprintf(stderr, "mdmc: %s\n", mdqt_last_error());

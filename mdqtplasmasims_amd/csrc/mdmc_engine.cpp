@@ -12,56 +12,14 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <chrono>
 #include <random>
 #include <string>
 #include <vector>
 
-#include "../../include/mdmc.h"
-#include "mdqt_ctx.hpp"   // HIPCHK, mdqt::set_error
-#include "mdqt_mt32.hpp"   // Mt32: the reference's std::mt19937 with the state in plain view
+#include "mdmc_ctx.hpp"   // struct mdmc_ctx; HIPCHK, mdqt::set_error, Mt32
 
 using namespace mdqt;
-
-struct mdmc_ctx {
-    mdmc_params p;
-    int N = 0, S = 0, nbins = 0, T = 0, nt = 0, npairs = 0;
-    double L = 0., rCut = 0.;
-    double collisionFreq = 0.;
-    int addLaserForce = 0;
-    // the reference's RNG (MCMD:52-55, :87)
-    Mt32 rng;
-    std::uniform_real_distribution<double> uni{0., 1.};
-    std::normal_distribution<double> vd;
-    int dev = 0;
-    hipStream_t st = nullptr;
-    double *dR = nullptr, *dV = nullptr, *dA = nullptr, *dU = nullptr, *dD = nullptr;
-    double* dRn = nullptr;          // positions of the next MDStep, pre-advanced by k_vv_step
-    bool rnValid = false;           // dRn == stepPositions(dR, dV, dA): cleared by every other writer
-    double *dSlots = nullptr, *dVS = nullptr, *dPart = nullptr, *dOut = nullptr;
-    double *dTemp = nullptr, *dMom = nullptr;   // per-step observables of the run (4 / 20 per step)
-    int capTemp = 0;
-    int2* dPairs = nullptr;
-    unsigned* dHist = nullptr;
-    int* dTags = nullptr;
-    uint32_t* dMT = nullptr;
-    unsigned long long* dAcc = nullptr;
-    double* hHits = nullptr;       // pinned ring of collision entries (i, vx, vy, vz), read by k_collide
-    int hitCap = 0, hitOff = 0;
-    std::string saveDir;
-    // QT tagging variants (qt_model 1..3)
-    int qt = 0;
-    double dtQ = 0., gamToE = 0., pv2q = 0., decayRatio = 0.;
-    int qtRatio = 0, pumpSteps = 0;
-    QTConst qc;
-    FastTab ftab;
-    FastTab* dFTab = nullptr;      // [2]: by state, by lane (the same for the pumping models)
-    double* dPsi = nullptr;        // [24][S] component-major (re0, im0, re1, ...), as include/mdqt.h's engine
-    double* dTp = nullptr;         // [S] tPart
-    int* dFlags = nullptr;
-    double *dKdePart = nullptr, *dKde = nullptr;
-    uint64_t qidx = 0;
-    unsigned short x48[3] = {0x330E, 0xABCD, 0x1234};   // drand48's default state (no srand48 in QTT)
-};
 
 namespace {
 
@@ -162,6 +120,8 @@ extern "C" void mdmc_destroy(mdmc_ctx* c) {
     for (void* q : ps)
         if (q) (void)hipFree(q);
     if (c->hHits) (void)hipHostFree(c->hHits);
+    if (c->hStage) (void)hipHostFree(c->hStage);
+    if (c->evDrain) (void)hipEventDestroy(c->evDrain);
     if (c->st) (void)hipStreamDestroy(c->st);
     delete c;
 }
@@ -234,6 +194,12 @@ extern "C" int mdmc_create(const mdmc_params* p, mdmc_ctx** out) {
     c->hitCap = 4 * 65536;
     if (hipHostMalloc((void**)&c->hHits, (size_t)c->hitCap * 4 * sizeof(double), hipHostMallocDefault) != hipSuccess)
         return fail_free(c, "mdmc_create: pinned allocation failed");
+    const size_t stageD = 24 + (p->qt_model != 0 ? (size_t)3 * TKDE_BINS : 0);
+    if (hipHostMalloc((void**)&c->hStage, stageD * sizeof(double) + (size_t)(c->nbins > 0 ? c->nbins : 1) * sizeof(unsigned),
+                      hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&c->evDrain, hipEventDisableTiming) != hipSuccess)
+        return fail_free(c, "mdmc_create: pinned allocation failed");
+    c->hStageHist = reinterpret_cast<unsigned*>(c->hStage + stageD);
     c->saveDir = c->p.saveDirectory;
     if (p->qt_model != 0) {
         // the QT tagging program's constants: 408 (QTT408Linear:115-121) / 422 (QTT422Linear:115-121)
@@ -336,6 +302,16 @@ extern "C" int mdmc_init(mdmc_ctx* c) {
     return 0;
 }
 
+void mdmc::mc_args(const mdmc_ctx* c, MCArgs& a) {
+    memset(&a, 0, sizeof a);
+    a.R = c->dR; a.U = c->dU; a.D = c->dD; a.mt = c->dMT; a.accepted = c->dAcc;
+    a.N = c->N; a.S = c->S;
+    a.L = c->L; a.kappa = c->p.kappa; a.rCut = c->rCut; a.maxRStep = c->p.maxRStep; a.Gamma = c->p.Gamma;
+    a.micT = mic_threshold(c->L);
+    a.fast = c->p.force_kernel == 1;
+    a.rc2 = sqrt_threshold(c->rCut);
+}
+
 // MonteCarloStep() x nsteps (:315-382) on the device with the reference's mt19937 stream
 extern "C" int mdmc_monte_carlo(mdmc_ctx* c, int nsteps, long long* accepted) {
     if (!c) return set_error("NULL context");
@@ -345,14 +321,9 @@ extern "C" int mdmc_monte_carlo(mdmc_ctx* c, int nsteps, long long* accepted) {
     if (rng_to_device(c)) return -1;
     HIPCHK(hipMemsetAsync(c->dAcc, 0, sizeof(unsigned long long), c->st));
     MCArgs a;
-    a.R = c->dR; a.U = c->dU; a.D = c->dD; a.mt = c->dMT; a.accepted = c->dAcc;
-    a.N = c->N; a.S = c->S;
-    a.L = c->L; a.kappa = c->p.kappa; a.rCut = c->rCut; a.maxRStep = c->p.maxRStep; a.Gamma = c->p.Gamma;
-    a.micT = mic_threshold(c->L);
-    a.fast = c->p.force_kernel == 1;
-    a.rc2 = sqrt_threshold(c->rCut);
+    mdmc::mc_args(c, a);
     for (int done = 0; done < nsteps;) {                      // bounded launches
-        a.nsteps = std::min(10000, nsteps - done);
+        a.nsteps = std::min(mdmc::kAnnealChunk, nsteps - done);
         HIPCHK(launch_monte_carlo(a, c->st));
         done += a.nsteps;
     }
@@ -366,7 +337,7 @@ extern "C" int mdmc_monte_carlo(mdmc_ctx* c, int nsteps, long long* accepted) {
 // One MDStep() (:504-511) queued on the stream: stepPositions, calculateAccelerations,
 // stepVelocities.  The collision rolls and Maxwellian draws of the step are state-independent,
 // so the host makes them (the reference's rng, its order :474-482) while the device runs.
-static int md_step_async(mdmc_ctx* c) {
+int mdmc::md_step_async(mdmc_ctx* c) {
     const int N = c->N;
     const double dt = c->p.timeStep;
     if (!c->rnValid)                                                                          // :452-467
@@ -410,7 +381,7 @@ extern "C" int mdmc_md_steps(mdmc_ctx* c, int nsteps) {
     if (!c) return set_error("NULL context");
     HIPCHK(hipSetDevice(c->dev));
     for (int k = 0; k < nsteps; ++k)
-        if (md_step_async(c)) return -1;
+        if (mdmc::md_step_async(c)) return -1;
     HIPCHK(hipStreamSynchronize(c->st));
     c->hitOff = 0;
     return 0;
@@ -427,23 +398,34 @@ extern "C" int mdmc_set_laser_force(mdmc_ctx* c, int on) {
     return 0;
 }
 
-// recordPairPairCorr (:584-635): the histogram on the device, the normalisation here
-static int pair_corr_host(mdmc_ctx* c, std::vector<double>& g) {
-    HIPCHK(hipSetDevice(c->dev));
+// recordPairPairCorr (:584-635): the histogram on the device (queued, read back into the pinned landing
+// area, evDrain behind the copy), the normalisation here once the copy has landed
+static int pair_corr_queue(mdmc_ctx* c) {
+    const int nb = c->nbins;
+    if (nb > 0) {
+        HIPCHK(hipMemsetAsync(c->dHist, 0, nb * sizeof(unsigned), c->st));
+        HIPCHK(launch_pair_hist(c->dR, c->N, c->S, c->L, c->p.pairPairStep, nb, c->dHist, c->st));
+        HIPCHK(hipMemcpyAsync(c->hStageHist, c->dHist, nb * sizeof(unsigned), hipMemcpyDeviceToHost, c->st));
+    }
+    HIPCHK(hipEventRecord(c->evDrain, c->st));
+    return 0;
+}
+static void pair_corr_finish(const mdmc_ctx* c, std::vector<double>& g) {
     const int nb = c->nbins;
     g.assign(nb > 0 ? nb : 0, 0.);
-    if (nb <= 0) return 0;
-    std::vector<unsigned> h(nb);
-    HIPCHK(hipMemsetAsync(c->dHist, 0, nb * sizeof(unsigned), c->st));
-    HIPCHK(launch_pair_hist(c->dR, c->N, c->S, c->L, c->p.pairPairStep, nb, c->dHist, c->st));
-    HIPCHK(hipMemcpyAsync(h.data(), c->dHist, nb * sizeof(unsigned), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
+    const unsigned* h = c->hStageHist;
     const int N = c->N;
     const double ps = c->p.pairPairStep;
     for (int i = 0; i < nb; i++) {                               // :627-635
         if (i == 0) g[i] = (double)h[i] / (N * 4 / 3 * M_PI * ps * ps * ps);
         else g[i] = (double)h[i] / (N * 3 * ps * ps * ps * i * i);
     }
+}
+static int pair_corr_host(mdmc_ctx* c, std::vector<double>& g) {
+    HIPCHK(hipSetDevice(c->dev));
+    if (pair_corr_queue(c)) return -1;
+    HIPCHK(hipEventSynchronize(c->evDrain));
+    pair_corr_finish(c, g);
     return 0;
 }
 
@@ -476,13 +458,17 @@ extern "C" int mdmc_set_velocity_store(mdmc_ctx* c, const double* vs) {
 }
 
 // recordVAF, recordLongViscAutoCorr, recordVCubeAutoCorr, recordVFourthAutoCorr (:655-807)
-extern "C" int mdmc_autocorrelations(mdmc_ctx* c, double* out) {
-    if (!c || !out) return set_error("mdmc_autocorrelations: NULL argument");
-    HIPCHK(hipSetDevice(c->dev));
+static int autocorr_queue(mdmc_ctx* c, double* out) {
     const double G = c->p.Gamma;
     const double c2 = 3 / (G * G), c4 = 3 * 9 / (G * G * G * G);   // :710, :785
     HIPCHK(launch_autocorr(c->dVS, c->N, c->T, c2, c4, c->dPart, c->dOut, c->st));
     HIPCHK(hipMemcpyAsync(out, c->dOut, (size_t)4 * c->T * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    return 0;
+}
+extern "C" int mdmc_autocorrelations(mdmc_ctx* c, double* out) {
+    if (!c || !out) return set_error("mdmc_autocorrelations: NULL argument");
+    HIPCHK(hipSetDevice(c->dev));
+    if (autocorr_queue(c, out)) return -1;
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
 }
@@ -622,7 +608,7 @@ static int need_qt(const mdmc_ctx* c, const char* what) {
 
 // qstep() x n (QTT:555-756): the pumping model's fused QT substeps on this system's velocities
 // (no drift: the MD steps move the ions), in launches of up to MAXSUB substeps
-static int qsteps_async(mdmc_ctx* c, int n) {
+int mdmc::qsteps_async(mdmc_ctx* c, int n) {
     while (n > 0) {
         const int m = n < MAXSUB ? n : MAXSUB;
         SubstepArgs a;
@@ -643,7 +629,7 @@ static int qsteps_async(mdmc_ctx* c, int n) {
 extern "C" int mdmc_qsteps(mdmc_ctx* c, int n) {
     if (need_qt(c, "mdmc_qsteps")) return -1;
     HIPCHK(hipSetDevice(c->dev));
-    if (qsteps_async(c, n)) return -1;
+    if (mdmc::qsteps_async(c, n)) return -1;
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
 }
@@ -739,9 +725,49 @@ extern "C" int mdmc_setup_directories(mdmc_ctx* c) {            // main() :1037-
 
 extern "C" const char* mdmc_save_directory(const mdmc_ctx* c) { return c ? c->saveDir.c_str() : ""; }
 
-static int write_pair_corr(mdmc_ctx* c, int stepNum) {          // :639-651
+// ------------------------------------------------------------------------------------------
+// main() (:1030-1167; QTT:1140-1254) by stage, for J contexts in lockstep: mdmc_run is J = 1, an
+// ensemble's run J members.  Every stage queues all members' launches and copies of a step on
+// their own streams first and then drains member by member (wait for the copies, format,
+// write), so a step with a host round trip costs one wait, not J in a row, and the host
+// formats one member's rows while the device runs the others' MD step.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+typedef std::chrono::steady_clock Clock;
+enum Stage { ST_ANNEAL = 0, ST_PRE, ST_PUMP, ST_REC, ST_AUTO, ST_REST };
+
+struct Run {
+    mdmc_ctx* const* c;
+    int J;
+    mdmc_ensemble* ens;           // NULL: one context, annealed by its own launch
+    int verbose;
+    Clock::time_point t0;
+};
+
+struct Files {                    // one open file per member, closed on every way out
+    std::vector<FILE*> f;
+    ~Files() { close(); }
+    void close() {
+        for (FILE* x : f)
+            if (x) fclose(x);
+        f.clear();
+    }
+};
+
+// with an ensemble's timing on: the wall time since the last stage ended, the queued work included
+int stage_end(Run& r, int stage) {
+    if (!r.ens || !r.ens->timing) return 0;
+    for (int j = 0; j < r.J; ++j) HIPCHK(hipStreamSynchronize(r.c[j]->st));
+    const Clock::time_point t = Clock::now();
+    r.ens->stage_ms[stage] += std::chrono::duration<double, std::milli>(t - r.t0).count();
+    r.t0 = t;
+    return 0;
+}
+
+int write_pair_corr_file(mdmc_ctx* c, int stepNum) {             // :639-651, the histogram landed
     std::vector<double> g;
-    if (pair_corr_host(c, g)) return -1;
+    pair_corr_finish(c, g);
     char name[256];
     snprintf(name, sizeof name, "pairPairCorrStepNum%d.dat", stepNum);
     FILE* fa = open_in(c, name, "w");
@@ -751,8 +777,18 @@ static int write_pair_corr(mdmc_ctx* c, int stepNum) {          // :639-651
     return 0;
 }
 
+int write_pair_corr(Run& r, int stepNum) {
+    for (int j = 0; j < r.J; ++j)
+        if (pair_corr_queue(r.c[j])) return -1;
+    for (int j = 0; j < r.J; ++j) {
+        HIPCHK(hipEventSynchronize(r.c[j]->evDrain));
+        if (write_pair_corr_file(r.c[j], stepNum)) return -1;
+    }
+    return 0;
+}
+
 // per-step observables buffered on the device, written when a stage ends
-static int ensure_step_buffers(mdmc_ctx* c, int steps) {
+int ensure_step_buffers(mdmc_ctx* c, int steps) {
     if (steps <= c->capTemp) return 0;
     if (c->dTemp) HIPCHK(hipFree(c->dTemp));
     if (c->dMom) HIPCHK(hipFree(c->dMom));
@@ -763,7 +799,7 @@ static int ensure_step_buffers(mdmc_ctx* c, int steps) {
     return 0;
 }
 
-static int write_temp_axes(mdmc_ctx* c, const char* name, int nsteps) {   // recordTempForEachAxis :560-581
+int write_temp_axes(mdmc_ctx* c, const char* name, int nsteps) {   // recordTempForEachAxis :560-581
     std::vector<double> s((size_t)nsteps * 4);
     HIPCHK(hipMemcpyAsync(s.data(), c->dTemp, s.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -778,169 +814,237 @@ static int write_temp_axes(mdmc_ctx* c, const char* name, int nsteps) {   // rec
     return 0;
 }
 
-static int write_autocorrelations(mdmc_ctx* c) {                // :682-691 and the three siblings
-    std::vector<double> out((size_t)4 * c->T);
-    if (mdmc_autocorrelations(c, out.data())) return -1;
-    const char* names[4] = {"VAF.dat", "longViscAutoCorr.dat", "vCubeAutoCorr.dat", "vFourthAutoCorr.dat"};
-    for (int f = 0; f < 4; ++f) {
-        FILE* fa = open_in(c, names[f], "w");
-        if (!fa) return set_error("cannot open %s%s", c->saveDir.c_str(), names[f]);
-        for (int td = 0; td < c->T; ++td) fprintf(fa, "%lg\t%lg\n", td * c->p.timeStep, out[(size_t)f * c->T + td]);
-        fclose(fa);
+// main() :1037-1065 (QTT:1143-1196): the directories, init() and the potentials
+int stage_start(Run& r) {
+    for (int j = 0; j < r.J; ++j)
+        if (mdmc_setup_directories(r.c[j]) || mdmc_init(r.c[j])) return -1;
+    return 0;
+}
+
+// step 3 :1068-1078 (QTT:1198-1209): g(r) at every multiple of 10,000, then one chunk of the chains
+int stage_anneal(Run& r) {
+    const int mcs = r.c[0]->p.monteCarloSteps;
+    for (int k = 0; k < mcs;) {
+        if (k % 10000 == 0) {
+            if (write_pair_corr(r, k)) return -1;
+            if (r.verbose) printf("%d\n", k);
+        }
+        const int next = std::min(mcs, (k / 10000 + 1) * 10000);
+        if (r.ens ? mdmc::ensemble_anneal(r.ens, next - k, nullptr) : mdmc_monte_carlo(r.c[0], next - k, nullptr)) return -1;
+        k = next;
     }
     return 0;
 }
 
-// main() of the QT tagging programs (QTT:1140-1254)
-static int run_qtt(mdmc_ctx* c, int verbose) {
+// n MDStep()s of every member; `count` prints the step counter every 100 (:1081-1089, :1126-1135)
+int stage_md(Run& r, int n, bool count) {
+    for (int k = 0; k < n; k++) {
+        if (count && r.verbose && k % 100 == 0) printf("%d\n", k);
+        for (int j = 0; j < r.J; ++j)
+            if (mdmc::md_step_async(r.c[j])) return -1;
+    }
+    return 0;
+}
+
+// n MDStep()s with the axis temperatures of every step, written to `name` (:1115-1123, :1141-1165)
+int stage_md_temp_axes(Run& r, int n, const char* name) {
+    for (int k = 0; k < n; k++)
+        for (int j = 0; j < r.J; ++j) {
+            mdmc_ctx* c = r.c[j];
+            HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dTemp + (size_t)4 * k, c->st));
+            if (mdmc::md_step_async(c)) return -1;
+        }
+    for (int j = 0; j < r.J; ++j)
+        if (write_temp_axes(r.c[j], name, n)) return -1;
+    return 0;
+}
+
+// recordTemperature (:533-545) and recordTaggedParticleMoments (:1005-1027) of step 5, appended per step
+int write_recorded_mcmd(mdmc_ctx* c) {
     const mdmc_params& p = c->p;
-    if (mdmc_setup_directories(c)) return -1;                    // :1143-1167
-    if (mdmc_init(c)) return -1;                                 // steps 1-2 :1192-1196
-    for (int k = 0; k < p.monteCarloSteps;) {                    // step 3 :1198-1209
-        if (k % 10000 == 0) {
-            if (write_pair_corr(c, k)) return -1;
-            if (verbose) printf("%d\n", k);
-        }
-        const int next = std::min(p.monteCarloSteps, (k / 10000 + 1) * 10000);
-        if (mdmc_monte_carlo(c, next - k, nullptr)) return -1;
-        k = next;
+    const int T = c->T;
+    std::vector<double> s((size_t)T * 4), m((size_t)T * 20);
+    HIPCHK(hipMemcpyAsync(s.data(), c->dTemp, s.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(m.data(), c->dMom, m.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    static const char* names[5] = {"temperature.dat", "taggedVOneMoments.dat", "taggedVTwoMoments.dat",
+                                   "taggedVThreeMoments.dat", "taggedVFourMoments.dat"};
+    Files fs;
+    for (int t = 0; t < 5; ++t) fs.f.push_back(open_in(c, names[t], "a"));
+    for (FILE* x : fs.f)
+        if (!x) return set_error("cannot open the stage-5 files");
+    for (int k = 0; k < T; ++k) {
+        double t4[4], m16[16];
+        temps_from_sums(c, &s[(size_t)4 * k], t4);
+        moments_from_sums(c, &m[(size_t)20 * k], m16);
+        for (int t = 0; t < 4; ++t)
+            fprintf(fs.f[t + 1], "%lg\t%lg\t%lg\t%lg\t%lg\n", k * p.timeStep, m16[4 * t], m16[4 * t + 1], m16[4 * t + 2],
+                    m16[4 * t + 3]);
+        fprintf(fs.f[0], "%lg\n", t4[0]);
     }
-    for (int k = 0; k < p.numPreRecordMDSteps; k++) {            // step 4 :1211-1220
-        if (verbose && k % 100 == 0) printf("%d\n", k);
-        if (md_step_async(c)) return -1;
+    return 0;
+}
+
+// step 5 :1093-1104: the tags, then collisionless MD recording moments, temperature and velocities
+int stage_record_mcmd(Run& r) {
+    const mdmc_params& p = r.c[0]->p;
+    const int T = r.c[0]->T;
+    for (int j = 0; j < r.J; ++j) {
+        mdmc_ctx* c = r.c[j];
+        c->collisionFreq = 0;
+        if (mdmc_tag_particles(c, nullptr)) return -1;
+        if (ensure_step_buffers(c, std::max(T, std::max(p.numInstantaneousAnisotropySteps,
+                                                        std::max(p.anisotropyFromForcesRelaxSteps, 1 << 16))))) return -1;
     }
-    c->collisionFreq = 0;                                        // step 5 :1222-1233
-    if (verbose) printf("pumpMDTimeSteps=%d\nquantumStepsPerMD=%d\n", c->pumpSteps, c->qtRatio);
-    for (int k = 0; k < c->pumpSteps; k++) {
-        if (qsteps_async(c, c->qtRatio)) return -1;
-        if (md_step_async(c)) return -1;
-    }
-    if (mdmc_tag_qt(c, nullptr, nullptr)) return -1;
-    const int T = c->T;                                          // step 6 :1235-1245
-    std::vector<double> m(20), dist((size_t)3 * TKDE_BINS);
-    FILE* fm = open_in(c, "taggedMoments.dat", "a");
-    FILE* ft = open_in(c, "temperature.dat", "a");
-    if (!fm || !ft) return set_error("cannot open taggedMoments.dat / temperature.dat in %s", c->saveDir.c_str());
     for (int k = 0; k < T; k++) {
-        if (tagged_moments_qt_queue(c, c->dOut, true)) return -1;
-        HIPCHK(hipMemcpyAsync(m.data(), c->dOut, 20 * sizeof(double), hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipMemcpyAsync(dist.data(), c->dKde, dist.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-        double mom[4];
-        moments_qt_from_sums(m.data(), mom);
-        fprintf(fm, "%lg\t%lg\t%lg\t%lg\t%lg\n", k * p.timeStep, mom[0], mom[1], mom[2], mom[3]);   // :1114
-        char name[64];
-        snprintf(name, sizeof name, "vel_distX_timestep%06d.dat", k);                                     // :1128-1136
-        FILE* fd = open_in(c, name, "w");
-        if (!fd) return set_error("cannot open %s%s", c->saveDir.c_str(), name);
-        for (int j = 0; j < TKDE_BINS; j++) fprintf(fd, "%lg\t%lg\n", (double)(j - 2000) * 0.0025, dist[j]);
-        fclose(fd);
-        if (k % 100 == 0) {
-            if (verbose) printf("%d\n", k);
-            if (write_pair_corr(c, k)) return -1;
+        const bool gr = k % 100 == 0;
+        if (gr && r.verbose) printf("%d\n", k);
+        for (int j = 0; j < r.J; ++j) {
+            mdmc_ctx* c = r.c[j];
+            HIPCHK(launch_tag_moments(c->dV, c->dTags, c->N, c->dMom + (size_t)20 * k, c->st));
+            if (gr && pair_corr_queue(c)) return -1;
+            HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dTemp + (size_t)4 * k, c->st));
+            if (mdmc::md_step_async(c)) return -1;
+            if (mdmc_record_velocities(c, k)) return -1;
         }
-        double t4[4];
-        HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dOut, c->st));   // recordTemperature :771-792
-        HIPCHK(hipMemcpyAsync(t4, c->dOut, sizeof t4, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-        double tt[4];
-        temps_from_sums(c, t4, tt);
-        fprintf(ft, "%lg\n", tt[0]);
-        if (md_step_async(c)) return -1;
-        if (mdmc_record_velocities(c, k)) return -1;
+        if (gr)
+            for (int j = 0; j < r.J; ++j) {
+                HIPCHK(hipEventSynchronize(r.c[j]->evDrain));
+                if (write_pair_corr_file(r.c[j], k)) return -1;
+            }
     }
-    fclose(fm);
-    fclose(ft);
-    if (write_autocorrelations(c)) return -1;                    // step 7 :1247-1251
+    for (int j = 0; j < r.J; ++j)
+        if (write_recorded_mcmd(r.c[j])) return -1;
+    return 0;
+}
+
+// step 6 :1107-1110 (QTT step 7 :1247-1251): :682-691 and the three siblings
+int stage_autocorrelations(Run& r) {
+    const int T = r.c[0]->T;
+    std::vector<std::vector<double>> out((size_t)r.J, std::vector<double>((size_t)4 * T));
+    for (int j = 0; j < r.J; ++j)
+        if (autocorr_queue(r.c[j], out[j].data())) return -1;
+    static const char* names[4] = {"VAF.dat", "longViscAutoCorr.dat", "vCubeAutoCorr.dat", "vFourthAutoCorr.dat"};
+    for (int j = 0; j < r.J; ++j) {
+        mdmc_ctx* c = r.c[j];
+        HIPCHK(hipStreamSynchronize(c->st));
+        for (int f = 0; f < 4; ++f) {
+            FILE* fa = open_in(c, names[f], "w");
+            if (!fa) return set_error("cannot open %s%s", c->saveDir.c_str(), names[f]);
+            for (int td = 0; td < T; ++td) fprintf(fa, "%lg\t%lg\n", td * c->p.timeStep, out[j][(size_t)f * T + td]);
+            fclose(fa);
+        }
+    }
+    return 0;
+}
+
+// steps 7 and 8 :1115-1165: the anisotropy stages
+int stage_anisotropy(Run& r) {
+    const mdmc_params& p = r.c[0]->p;
+    for (int j = 0; j < r.J; ++j)
+        if (mdmc_anisotropize(r.c[j])) return -1;                // step 7 :1115-1123
+    if (stage_md_temp_axes(r, p.numInstantaneousAnisotropySteps, "TemperaturesAlongAxesInstantaneous.dat")) return -1;
+    for (int j = 0; j < r.J; ++j) r.c[j]->collisionFreq = 0.25;  // :1125-1135
+    if (stage_md(r, p.numReestablishEquilSteps, true)) return -1;
+    const int nest = (int)round(.8 * p.anisotropyEstablishmentTime * sqrt(p.n) / p.timeStep);   // :106
+    for (int j = 0; j < r.J; ++j) {                              // step 8 :1138-1151
+        mdmc_ctx* c = r.c[j];
+        c->addLaserForce = 1;
+        c->collisionFreq = 0;
+        if (ensure_step_buffers(c, std::max(nest, c->capTemp))) return -1;
+    }
+    if (stage_md_temp_axes(r, nest, "TemperaturesAlongAxesDuringForcePeriod.dat")) return -1;
+    for (int j = 0; j < r.J; ++j) r.c[j]->addLaserForce = 0;     // :1155-1165
+    return stage_md_temp_axes(r, p.anisotropyFromForcesRelaxSteps, "TemperaturesAlongAxesAfterForcePeriod.dat");
+}
+
+// QTT step 5 :1222-1233: the pump period (QT steps between collisionless MD steps), then the tags
+int stage_pump(Run& r) {
+    for (int j = 0; j < r.J; ++j) r.c[j]->collisionFreq = 0;
+    if (r.verbose) printf("pumpMDTimeSteps=%d\nquantumStepsPerMD=%d\n", r.c[0]->pumpSteps, r.c[0]->qtRatio);
+    for (int k = 0; k < r.c[0]->pumpSteps; k++)
+        for (int j = 0; j < r.J; ++j) {
+            mdmc_ctx* c = r.c[j];
+            if (mdmc::qsteps_async(c, c->qtRatio)) return -1;
+            if (mdmc::md_step_async(c)) return -1;
+        }
+    for (int j = 0; j < r.J; ++j)
+        if (mdmc_tag_qt(r.c[j], nullptr, nullptr)) return -1;
+    return 0;
+}
+
+// QTT step 6 :1235-1245: per step the tagged moments and distribution, g(r) every 100, the temperature
+// (all read back into the member's landing area, evDrain behind them), then the MD step
+int stage_record_qtt(Run& r) {
+    const int T = r.c[0]->T;
+    Files fm, ft;
+    for (int j = 0; j < r.J; ++j) {
+        fm.f.push_back(open_in(r.c[j], "taggedMoments.dat", "a"));
+        ft.f.push_back(open_in(r.c[j], "temperature.dat", "a"));
+        if (!fm.f.back() || !ft.f.back())
+            return set_error("cannot open taggedMoments.dat / temperature.dat in %s", r.c[j]->saveDir.c_str());
+    }
+    for (int k = 0; k < T; k++) {
+        const bool gr = k % 100 == 0;
+        for (int j = 0; j < r.J; ++j) {
+            mdmc_ctx* c = r.c[j];
+            if (tagged_moments_qt_queue(c, c->dOut, true)) return -1;
+            HIPCHK(hipMemcpyAsync(c->hStage, c->dOut, 20 * sizeof(double), hipMemcpyDeviceToHost, c->st));
+            HIPCHK(hipMemcpyAsync(c->hStage + 24, c->dKde, (size_t)3 * TKDE_BINS * sizeof(double), hipMemcpyDeviceToHost,
+                                  c->st));
+            if (gr && pair_corr_queue(c)) return -1;
+            HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dOut, c->st));   // recordTemperature :771-792
+            HIPCHK(hipMemcpyAsync(c->hStage + 20, c->dOut, 4 * sizeof(double), hipMemcpyDeviceToHost, c->st));
+            HIPCHK(hipEventRecord(c->evDrain, c->st));
+            if (mdmc::md_step_async(c)) return -1;
+            if (mdmc_record_velocities(c, k)) return -1;
+        }
+        if (gr && r.verbose) printf("%d\n", k);
+        for (int j = 0; j < r.J; ++j) {
+            mdmc_ctx* c = r.c[j];
+            HIPCHK(hipEventSynchronize(c->evDrain));
+            double mom[4], tt[4];
+            moments_qt_from_sums(c->hStage, mom);
+            fprintf(fm.f[j], "%lg\t%lg\t%lg\t%lg\t%lg\n", k * c->p.timeStep, mom[0], mom[1], mom[2], mom[3]);   // :1114
+            char name[64];
+            snprintf(name, sizeof name, "vel_distX_timestep%06d.dat", k);                                     // :1128-1136
+            FILE* fd = open_in(c, name, "w");
+            if (!fd) return set_error("cannot open %s%s", c->saveDir.c_str(), name);
+            const double* dist = c->hStage + 24;
+            for (int i = 0; i < TKDE_BINS; i++) fprintf(fd, "%lg\t%lg\n", (double)(i - 2000) * 0.0025, dist[i]);
+            fclose(fd);
+            if (gr && write_pair_corr_file(c, k)) return -1;
+            temps_from_sums(c, c->hStage + 20, tt);
+            fprintf(ft.f[j], "%lg\n", tt[0]);
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+int mdmc::run_members(mdmc_ctx* const* cs, int J, mdmc_ensemble* ens, int verbose) {
+    Run r{cs, J, ens, verbose, Clock::now()};
+    const mdmc_params& p = cs[0]->p;
+    if (stage_start(r) || stage_end(r, ST_REST)) return -1;
+    if (stage_anneal(r) || stage_end(r, ST_ANNEAL)) return -1;
+    if (stage_md(r, p.numPreRecordMDSteps, true) || stage_end(r, ST_PRE)) return -1;     // step 4
+    if (cs[0]->qt) {                                             // the QT tagging programs, QTT:1222-1251
+        if (stage_pump(r) || stage_end(r, ST_PUMP)) return -1;
+        if (stage_record_qtt(r) || stage_end(r, ST_REC)) return -1;
+        if (stage_autocorrelations(r) || stage_end(r, ST_AUTO)) return -1;
+    } else {
+        if (stage_record_mcmd(r) || stage_end(r, ST_REC)) return -1;
+        if (stage_autocorrelations(r) || stage_end(r, ST_AUTO)) return -1;
+        if (stage_anisotropy(r) || stage_end(r, ST_REST)) return -1;
+    }
     if (verbose) fflush(stdout);
     return 0;
 }
 
-// main() :1030-1167
+// main() :1030-1167 (QTT:1140-1254)
 extern "C" int mdmc_run(mdmc_ctx* c, int verbose) {
     if (!c) return set_error("NULL context");
-    if (c->qt) return run_qtt(c, verbose);
-    const mdmc_params& p = c->p;
-    if (mdmc_setup_directories(c)) return -1;                    // :1037-1058
-    if (mdmc_init(c)) return -1;                                 // step 1-2 :1062-1065
-    for (int k = 0; k < p.monteCarloSteps;) {                    // step 3 :1068-1078
-        if (k % 10000 == 0) {
-            if (write_pair_corr(c, k)) return -1;
-            if (verbose) printf("%d\n", k);
-        }
-        const int next = std::min(p.monteCarloSteps, (k / 10000 + 1) * 10000);
-        if (mdmc_monte_carlo(c, next - k, nullptr)) return -1;
-        k = next;
-    }
-    for (int k = 0; k < p.numPreRecordMDSteps; k++) {            // step 4 :1081-1089
-        if (verbose && k % 100 == 0) printf("%d\n", k);
-        if (md_step_async(c)) return -1;
-    }
-    c->collisionFreq = 0;                                        // step 5 :1093-1104
-    if (mdmc_tag_particles(c, nullptr)) return -1;
-    const int T = c->T;
-    if (ensure_step_buffers(c, std::max(T, std::max(p.numInstantaneousAnisotropySteps,
-                                                    std::max(p.anisotropyFromForcesRelaxSteps, 1 << 16))))) return -1;
-    for (int k = 0; k < T; k++) {
-        HIPCHK(launch_tag_moments(c->dV, c->dTags, c->N, c->dMom + (size_t)20 * k, c->st));
-        if (k % 100 == 0) {
-            if (verbose) printf("%d\n", k);
-            if (write_pair_corr(c, k)) return -1;
-        }
-        HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dTemp + (size_t)4 * k, c->st));
-        if (md_step_async(c)) return -1;
-        if (mdmc_record_velocities(c, k)) return -1;
-    }
-    {   // recordTemperature (:533-545) and recordTaggedParticleMoments (:1005-1027), appended per step
-        std::vector<double> s((size_t)T * 4), m((size_t)T * 20);
-        HIPCHK(hipMemcpyAsync(s.data(), c->dTemp, s.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipMemcpyAsync(m.data(), c->dMom, m.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-        FILE* ft = open_in(c, "temperature.dat", "a");
-        const char* names[4] = {"taggedVOneMoments.dat", "taggedVTwoMoments.dat", "taggedVThreeMoments.dat",
-                                "taggedVFourMoments.dat"};
-        FILE* fm[4];
-        for (int t = 0; t < 4; ++t) fm[t] = open_in(c, names[t], "a");
-        if (!ft || !fm[0] || !fm[1] || !fm[2] || !fm[3]) return set_error("cannot open the stage-5 files");
-        for (int k = 0; k < T; ++k) {
-            double t4[4], m16[16];
-            temps_from_sums(c, &s[(size_t)4 * k], t4);
-            moments_from_sums(c, &m[(size_t)20 * k], m16);
-            for (int t = 0; t < 4; ++t)
-                fprintf(fm[t], "%lg\t%lg\t%lg\t%lg\t%lg\n", k * p.timeStep, m16[4 * t], m16[4 * t + 1], m16[4 * t + 2],
-                        m16[4 * t + 3]);
-            fprintf(ft, "%lg\n", t4[0]);
-        }
-        fclose(ft);
-        for (int t = 0; t < 4; ++t) fclose(fm[t]);
-    }
-    if (write_autocorrelations(c)) return -1;                    // step 6 :1107-1110
-    if (mdmc_anisotropize(c)) return -1;                         // step 7 :1115-1123
-    for (int k = 0; k < p.numInstantaneousAnisotropySteps; k++) {
-        HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dTemp + (size_t)4 * k, c->st));
-        if (md_step_async(c)) return -1;
-    }
-    if (write_temp_axes(c, "TemperaturesAlongAxesInstantaneous.dat", p.numInstantaneousAnisotropySteps)) return -1;
-    c->collisionFreq = 0.25;                                     // :1125-1135
-    for (int k = 0; k < p.numReestablishEquilSteps; k++) {
-        if (verbose && k % 100 == 0) printf("%d\n", k);
-        if (md_step_async(c)) return -1;
-    }
-    c->addLaserForce = 1;                                        // step 8 :1138-1151
-    c->collisionFreq = 0;
-    const int nest = (int)round(.8 * p.anisotropyEstablishmentTime * sqrt(p.n) / p.timeStep);   // :106
-    if (ensure_step_buffers(c, std::max(nest, c->capTemp))) return -1;
-    for (int k = 0; k < nest; k++) {
-        HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dTemp + (size_t)4 * k, c->st));
-        if (md_step_async(c)) return -1;
-    }
-    if (write_temp_axes(c, "TemperaturesAlongAxesDuringForcePeriod.dat", nest)) return -1;
-    c->addLaserForce = 0;                                        // :1155-1165
-    for (int k = 0; k < p.anisotropyFromForcesRelaxSteps; k++) {
-        HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dTemp + (size_t)4 * k, c->st));
-        if (md_step_async(c)) return -1;
-    }
-    if (write_temp_axes(c, "TemperaturesAlongAxesAfterForcePeriod.dat", p.anisotropyFromForcesRelaxSteps)) return -1;
-    if (verbose) fflush(stdout);
-    return 0;
+    mdmc_ctx* one[1] = {c};
+    return mdmc::run_members(one, 1, nullptr, verbose);
 }

@@ -267,8 +267,10 @@ __device__ __forceinline__ double mc_pair(double dx, double dy, double dz, const
     return mc_uij(sqrt(r2), a.kappa, a.rCut);
 }
 
+// The chain of one workgroup: the body of k_monte_carlo_lds (one job) and of k_monte_carlo_lds_ens
+// (workgroup b runs jobs[b]), inlined into both so that both compile the same arithmetic.
 template <int NPT, bool FAST>
-__global__ __launch_bounds__(MCT) void k_monte_carlo_lds(MCArgs a) {
+__device__ __forceinline__ void mc_lds_chain(const MCArgs& a) {
     extern __shared__ double sR[];                   // [3][N]
     __shared__ MtLds mt;
     __shared__ int s_P, s_acc;
@@ -397,6 +399,21 @@ __global__ __launch_bounds__(MCT) void k_monte_carlo_lds(MCArgs a) {
     for (int k = tid; k < N; k += MCT) { a.R[k] = X[k]; a.R[S + k] = Y[k]; a.R[2 * S + k] = Z[k]; }
     for (int k = tid; k < 624; k += MCT) a.mt[k] = mt.w[mt.cur][k];
     if (tid == 0) { a.mt[624] = (uint32_t)mt.p; *a.accepted += acc; }
+}
+
+template <int NPT, bool FAST>
+__global__ __launch_bounds__(MCT) void k_monte_carlo_lds(MCArgs a) {
+    mc_lds_chain<NPT, FAST>(a);
+}
+
+// An ensemble of chains: grid (J), workgroup b anneals jobs[b] on its own CU (positions in its LDS,
+// energies in its registers; it writes only its job's R, U, mt and accepted).  The block is copied
+// once at entry — a wave-uniform load of never-written memory, so the loop constants sit in scalar
+// registers as the by-value argument's do.
+template <int NPT, bool FAST>
+__global__ __launch_bounds__(MCT) void k_monte_carlo_lds_ens(const MCArgs* __restrict__ jobs) {
+    const MCArgs a = jobs[blockIdx.x];
+    mc_lds_chain<NPT, FAST>(a);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -727,6 +744,39 @@ hipError_t launch_monte_carlo(const MCArgs& a, hipStream_t s) {
     }
     hipLaunchKernelGGL(k_monte_carlo, dim3(1), dim3(MCT), 0, s, a);
     return hipGetLastError();
+}
+template <int NPT, bool FAST>
+static hipError_t launch_mc_ens_v(const MCArgs* dev_jobs, const MCArgs& one, int njobs, hipStream_t s, hipEvent_t ev0,
+                                  hipEvent_t ev1) {
+    const size_t lds = (size_t)3 * one.N * sizeof(double);
+    hipError_t e = hipFuncSetAttribute((const void*)k_monte_carlo_lds_ens<NPT, FAST>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    if (ev0) hipExtLaunchKernelGGL((k_monte_carlo_lds_ens<NPT, FAST>), dim3(njobs), dim3(MCT), lds, s, ev0, ev1, 0, dev_jobs);
+    else hipLaunchKernelGGL((k_monte_carlo_lds_ens<NPT, FAST>), dim3(njobs), dim3(MCT), lds, s, dev_jobs);
+    return hipGetLastError();
+}
+template <int NPT>
+static hipError_t launch_mc_ens(const MCArgs* dev_jobs, const MCArgs& one, int njobs, hipStream_t s, hipEvent_t ev0,
+                                hipEvent_t ev1) {
+    return one.fast ? launch_mc_ens_v<NPT, true>(dev_jobs, one, njobs, s, ev0, ev1)
+                    : launch_mc_ens_v<NPT, false>(dev_jobs, one, njobs, s, ev0, ev1);
+}
+// The anneal of njobs chains in one launch: dev_jobs[b] is workgroup b's block (device memory), `one` any
+// member's block on the host (all share N and fast; its nsteps <= 0 launches nothing).  The L2 fallback
+// k_monte_carlo is not batched: N > 6144 is refused.
+hipError_t launch_monte_carlo_ens(const MCArgs* dev_jobs, const MCArgs& one, int njobs, hipStream_t s, hipEvent_t ev0,
+                                  hipEvent_t ev1) {
+    if (!dev_jobs || njobs < 1 || njobs > 65535 || one.N < 1 || one.N > 6 * MCT) return hipErrorInvalidValue;
+    if (one.nsteps <= 0) return hipSuccess;
+    switch ((one.N + MCT - 1) / MCT) {
+        case 1: return launch_mc_ens<1>(dev_jobs, one, njobs, s, ev0, ev1);
+        case 2: return launch_mc_ens<2>(dev_jobs, one, njobs, s, ev0, ev1);
+        case 3: return launch_mc_ens<3>(dev_jobs, one, njobs, s, ev0, ev1);
+        case 4: return launch_mc_ens<4>(dev_jobs, one, njobs, s, ev0, ev1);
+        case 5: return launch_mc_ens<5>(dev_jobs, one, njobs, s, ev0, ev1);
+        default: return launch_mc_ens<6>(dev_jobs, one, njobs, s, ev0, ev1);
+    }
 }
 hipError_t launch_vv_positions(const double* R, const double* V, const double* A, double* Rn, int N, int S, double dt,
                                double L, hipStream_t s) {

@@ -538,6 +538,10 @@ struct VVArgs {
 hipError_t launch_particle_potentials(const double* R, int N, int S, double L, double kappa, double rCut, double* U,
                                       hipStream_t s);
 hipError_t launch_monte_carlo(const MCArgs& a, hipStream_t s);
+// njobs chains in one launch (grid njobs; N <= 6144): dev_jobs on the device, `one` a member's block on the host;
+// ev0 / ev1 (or null) take the launch's own timestamps
+hipError_t launch_monte_carlo_ens(const MCArgs* dev_jobs, const MCArgs& one, int njobs, hipStream_t s,
+                                  hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t launch_vv_positions(const double* R, const double* V, const double* A, double* Rn, int N, int S, double dt,
                                double L, hipStream_t s);
 hipError_t launch_vv_velocities(const VVArgs& a, hipStream_t s);   // + the collision scatter when nhits > 0

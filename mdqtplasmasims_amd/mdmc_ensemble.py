@@ -1,0 +1,116 @@
+"""An ensemble of independent Monte-Carlo + MD jobs on one MI355X.
+
+The reference runs its MC + MD programs as a Slurm array of independent jobs (exampleSlurmFile.slurm:3,16,
+``srun tagQuad $SLURM_ARRAY_TASK_ID``).  :class:`MonteCarloEnsemble` owns ``njobs`` such jobs — job k has
+``job + k`` and ``seed + k`` — anneals all their Metropolis chains with one launch (one workgroup per chain)
+and queues their MD steps on the members' own streams (include/mdmc.h, "ensembles").  Every job's state and
+files are bit for bit what :class:`~mdqtplasmasims_amd.mdmc.MonteCarloMD` gives for that job alone.
+
+    =================================  ================================  ============================
+    reference (MCMD), per job          here, all jobs                    C ABI (include/mdmc.h)
+    =================================  ================================  ============================
+    init()             :173-245        MonteCarloEnsemble.init()         mdmc_ensemble_init
+    MonteCarloStep() x n  :315-382     MonteCarloEnsemble.monte_carlo(n) mdmc_ensemble_monte_carlo
+    MDStep() x n       :504-511        MonteCarloEnsemble.md_steps(n)    mdmc_ensemble_md_steps
+    main()             :1030-1167      MonteCarloEnsemble.run()          mdmc_ensemble_run
+    =================================  ================================  ============================
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from ._lib import MdmcParams, check, lib
+from .mdmc import MonteCarloMD, default_params
+
+
+def mdmc_job_params(base: MdmcParams, k: int) -> MdmcParams:
+    """job k's parameters of an ensemble created from `base` (job + k, seed + k; host only)"""
+    out = MdmcParams()
+    check(lib().mdmc_ensemble_job_params(C.byref(base), int(k), C.byref(out)), "mdmc_ensemble_job_params")
+    return out
+
+
+class _Member(MonteCarloMD):
+    """a job of an ensemble: the whole MonteCarloMD interface on a context the ensemble owns"""
+
+    def __init__(self, ensemble, handle, params):  # no mdmc_create
+        self._ensemble = ensemble                  # keeps the owner alive
+        self.p = params
+        self._h = C.c_void_p(handle)
+        self.N = int(params.N)
+        self.T = int(params.numVelAutoCorrsSteps)
+
+    def close(self):                               # not this view's to destroy
+        self._h = None
+
+
+class MonteCarloEnsemble:
+    """``njobs`` independent jobs (job + k, seed + k) resident on one MI355X."""
+
+    STAGES = ("anneal", "pre_record_md", "qt_pump", "recorded_md", "autocorrelations", "rest")
+
+    def __init__(self, njobs: int, **params):
+        self.p = default_params(**params)
+        h = C.c_void_p()
+        check(lib().mdmc_ensemble_create(C.byref(self.p), int(njobs), C.byref(h)), "mdmc_ensemble_create")
+        self.h = h
+        self.jobs = [_Member(self, lib().mdmc_ensemble_job(h, k), mdmc_job_params(self.p, k))
+                     for k in range(lib().mdmc_ensemble_size(h))]
+
+    # ---- lifecycle ----
+    def close(self):
+        if getattr(self, "h", None):
+            for j in self.jobs:
+                j.close()
+            lib().mdmc_ensemble_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return len(self.jobs)
+
+    # ---- the reference's function seam, for every job at once ----
+    def init(self):
+        check(lib().mdmc_ensemble_init(self.h), "mdmc_ensemble_init")
+        return self
+
+    def monte_carlo(self, nsteps: int) -> list:
+        """nsteps Metropolis steps of every chain (batched launches); the accepted counts by job"""
+        acc = (C.c_longlong * len(self.jobs))()
+        check(lib().mdmc_ensemble_monte_carlo(self.h, int(nsteps), acc), "mdmc_ensemble_monte_carlo")
+        return [int(a) for a in acc]
+
+    def md_steps(self, nsteps: int):
+        check(lib().mdmc_ensemble_md_steps(self.h, int(nsteps)), "mdmc_ensemble_md_steps")
+
+    def run(self, verbose: bool = False):
+        check(lib().mdmc_ensemble_run(self.h, int(bool(verbose))), "mdmc_ensemble_run")
+
+    # ---- timing ----
+    def enable_timing(self, on: bool = True):
+        """record the anneal launches' dispatch timestamps, and time the stages of run()"""
+        check(lib().mdmc_ensemble_enable_timing(self.h, 1 if on else 0))
+
+    def kernel_times(self):
+        """{anneal_ms, n_anneal, anneal_median_ms, anneal_min_ms, anneal_max_ms} of the batched launches since
+        the last call (synchronises and resets), and stage_ms: the wall time of the last run()'s stages"""
+        out = (C.c_double * 11)()
+        check(lib().mdmc_ensemble_kernel_times(self.h, out, 11), "mdmc_ensemble_kernel_times")
+        d = {"anneal_ms": out[0], "n_anneal": int(out[1]), "anneal_median_ms": out[2], "anneal_min_ms": out[3],
+             "anneal_max_ms": out[4]}
+        d["stage_ms"] = {k: out[5 + i] for i, k in enumerate(self.STAGES)}
+        return d
+
+
+__all__ = ["MonteCarloEnsemble", "mdmc_job_params"]
