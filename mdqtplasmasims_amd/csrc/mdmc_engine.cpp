@@ -172,7 +172,8 @@ extern "C" int mdmc_create(const mdmc_params* p, mdmc_ctx** out) {
               hipMalloc(&c->dSlots, 3 * sz * c->nt) == hipSuccess &&
               hipMalloc(&c->dVS, (size_t)3 * N * c->T * sizeof(double)) == hipSuccess &&
               hipMalloc(&c->dPart, (size_t)nblk * 4 * c->T * sizeof(double)) == hipSuccess &&
-              hipMalloc(&c->dOut, (size_t)4 * c->T * sizeof(double)) == hipSuccess &&
+              // dOut: the autocorrelations [4][T], the temperature sums and k_tag_moments' sums
+              hipMalloc(&c->dOut, (size_t)std::max(4 * c->T, kTagMomentSums) * sizeof(double)) == hipSuccess &&
               hipMalloc(&c->dPairs, (size_t)c->npairs * sizeof(int2)) == hipSuccess &&
               hipMalloc(&c->dHist, (size_t)(c->nbins > 0 ? c->nbins : 1) * sizeof(unsigned)) == hipSuccess &&
               hipMalloc(&c->dTags, (size_t)4 * N * sizeof(int)) == hipSuccess &&
@@ -553,7 +554,7 @@ static void moments_from_sums(const mdmc_ctx* c, const double* m, double* out16)
 extern "C" int mdmc_tagged_moments(mdmc_ctx* c, double out16[16]) {
     if (!c || !out16) return set_error("mdmc_tagged_moments: NULL argument");
     HIPCHK(hipSetDevice(c->dev));
-    double m[20];
+    double m[kTagMomentSums];
     HIPCHK(launch_tag_moments(c->dV, c->dTags, c->N, c->dOut, c->st));
     HIPCHK(hipMemcpyAsync(m, c->dOut, sizeof m, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -668,7 +669,7 @@ extern "C" int mdmc_tagged_moments_qt(mdmc_ctx* c, double out4[4], double* dist)
     if (!out4) return set_error("mdmc_tagged_moments_qt: NULL argument");
     HIPCHK(hipSetDevice(c->dev));
     if (tagged_moments_qt_queue(c, c->dOut, dist != nullptr)) return -1;
-    double m[20];
+    double m[kTagMomentSums];
     HIPCHK(hipMemcpyAsync(m, c->dOut, sizeof m, hipMemcpyDeviceToHost, c->st));
     if (dist) HIPCHK(hipMemcpyAsync(dist, c->dKde, (size_t)3 * TKDE_BINS * sizeof(double), hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));

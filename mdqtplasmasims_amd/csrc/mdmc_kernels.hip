@@ -614,11 +614,11 @@ __global__ __launch_bounds__(RBT) void k_temperatures(const double* __restrict__
 
 __global__ __launch_bounds__(RBT) void k_tag_moments(const double* __restrict__ V, const int* __restrict__ tags, int N,
                                                      double* __restrict__ out) {
-    __shared__ double sp[20][RBT / 64];
+    __shared__ double sp[kTagMomentSums][RBT / 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    double m[20];
+    double m[kTagMomentSums];
 #pragma unroll
-    for (int q = 0; q < 20; ++q) m[q] = 0.;
+    for (int q = 0; q < kTagMomentSums; ++q) m[q] = 0.;
     for (int i = tid; i < N; i += RBT) {
         const double v = V[i];
         const double v2 = v * v, v3 = v * v * v, v4 = v * v * v * v;
@@ -629,12 +629,12 @@ __global__ __launch_bounds__(RBT) void k_tag_moments(const double* __restrict__ 
             }
     }
 #pragma unroll
-    for (int q = 0; q < 20; ++q) {
+    for (int q = 0; q < kTagMomentSums; ++q) {
         const double s = wave_sum(m[q]);
         if (lane == 0) sp[q][w] = s;
     }
     __syncthreads();
-    if (tid < 20) {
+    if (tid < kTagMomentSums) {
         double s = 0.;
         for (int q = 0; q < RBT / 64; ++q) s = s + sp[tid][q];
         out[tid] = s;

@@ -551,6 +551,8 @@ int autocorr_blocks(int N);
 hipError_t launch_autocorr(const double* vs, int N, int T, double c2, double c4, double* part, double* out,
                            hipStream_t s);
 hipError_t launch_temperatures(const double* V, int N, int S, double* out, hipStream_t s);
+// out[kTagMomentSums]: (sum v, v^2, v^3, v^4, count) of the four tag sets
+constexpr int kTagMomentSums = 20;
 hipError_t launch_tag_moments(const double* V, const int* tags, int N, double* out, hipStream_t s);
 hipError_t launch_anisotropize(double* V, int N, int S, double tpd, hipStream_t s);
 hipError_t launch_store_velocities(const double* V, int N, int S, int T, int t, double* vs, hipStream_t s);

@@ -493,6 +493,260 @@ def mcmd_autocorrelations(vs: np.ndarray, Gamma: float) -> np.ndarray:
     return out
 
 
+def mcmd_autocorrelations_direct(vs: np.ndarray, Gamma: float):
+    """The four lag sums of MCMD:655-807 term by term (no FFT), for any N and T: the products and
+    sums in np.longdouble, rounded once.  Returns (out [4][T], mag [4][T]): mag[f][td] is the sum of
+    the magnitudes of everything a lag adds up (float64; a scale for summation bounds): per (i, j)
+    the three components' products and, for f = 1 and 3, the offset of :710 / :785."""
+    vs = np.asarray(vs, dtype=np.float64)
+    _, N, T = vs.shape
+    ld = np.longdouble
+    c2 = 3 / (Gamma * Gamma)
+    c4 = 3 * 9 / (Gamma * Gamma * Gamma * Gamma)
+    av = np.abs(vs)
+    pw = [av, av * av, av * av * av, (av * av) * (av * av)]      # |a b| = |a| |b|: the magnitudes
+    pwl = [vs.astype(ld)]
+    pwl.append(pwl[0] * pwl[0]); pwl.append(pwl[1] * pwl[0]); pwl.append(pwl[1] * pwl[1])
+    off = [0.0, c2, 0.0, c4]
+    out = np.empty((4, T)); mag = np.empty((4, T))
+    for td in range(T):
+        n = T - td
+        for f in range(4):
+            s = np.einsum("cij,cij->", pwl[f][:, :, :n], pwl[f][:, :, td:]) - ld(off[f]) * (N * n)
+            out[f, td] = float(s / (N * n))
+            mag[f, td] = np.einsum("cij,cij->", pw[f][:, :, :n], pw[f][:, :, td:]) + off[f] * (N * n)
+    return out, mag
+
+
+def _c_round(x):
+    """C round(): halves away from zero (np.round goes to even)"""
+    r = np.trunc(x)
+    f = x - r                          # exact
+    r += f >= 0.5
+    r -= f <= -0.5
+    return r
+
+
+def mcmd_constants(N: int, pairPairStep: float = 0.05):
+    """(L, rCut, nbins): MCMD:73, :74 and the row count of :616 / :627"""
+    import math
+    L = math.pow(N * 4. * math.pi / 3., 1. / 3)
+    rCut = L / 2.
+    return L, rCut, int((L / 2) / pairPairStep)
+
+
+def _mcmd_uij(r, kappa, rCut):
+    """calcUIJ :153-159 on an array of distances (float64, the reference's operations)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(r < rCut, np.exp(-1 * kappa * r) / r, 0.0)
+
+
+def _mcmd_dist(p, R, L):
+    """nearest-image distances (:224-234) from the points p [3][m] to the ions R [3][N]: [m][N]"""
+    d = p[:, :, None] - R[:, None, :]
+    d = d - L * _c_round(d / L)
+    return np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), d
+
+
+def mcmd_potentials(R, L, kappa, rCut, block=256):
+    """calculatePotentialEnergyForParticles :207-245: U[i] = sum_{j != i} u(r_ij); the pair terms
+    in float64 as the reference makes them (u_ij and u_ji are the same float64 number: the
+    displacement only changes sign, and C round is odd), summed per ion in np.longdouble and
+    rounded once"""
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    N = R.shape[1]
+    U = np.zeros(N, dtype=np.longdouble)
+    for i0 in range(0, N, block):
+        i1 = min(N, i0 + block)
+        r, _ = _mcmd_dist(R[:, i0:i1], R[:, i0:], L)         # the rows' pairs with j >= i0
+        k = np.arange(i1 - i0)
+        r[k, k] = 1.0                                        # j == i is skipped (:237)
+        u = _mcmd_uij(r, kappa, rCut)
+        u[k, k] = 0.0
+        u = u.astype(np.longdouble)
+        U[i0:i1] += u.sum(axis=1)
+        U[i1:] += u[:, i1 - i0:].sum(axis=0)                 # the same pairs seen from j >= i1
+    return U.astype(np.float64)
+
+
+def mcmd_monte_carlo(R, U, mt, nsteps, L, kappa, rCut, maxRStep, Gamma):
+    """MonteCarloStep() x nsteps (:315-382) with changePotentialEnergy (:249-313) on R [3][N] and
+    U [N] in place, drawing from mt (an MT19937).  float64 and the reference's operations; the sums
+    U[NPart] (:301) and the energy difference (:341-345) through math.fsum.  Returns (accepted,
+    min_margin): the smallest distance of any decision from its threshold, |dE| for a move accepted
+    at :347 and |dice - exp(-dE / 2 Gamma)| for one rolled at :354-357.  A chain whose min_margin is
+    far above the rounding of dE (~1e-13) has the same decisions in any summation order."""
+    import math
+    N = R.shape[1]
+    acc = 0
+    margin = math.inf
+    for _ in range(int(nsteps)):
+        while True:                                                       # :325-334
+            P = int(math.floor(mt.uniform() * N))
+            rx = maxRStep * (2 * mt.uniform() - 1)
+            ry = maxRStep * (2 * mt.uniform() - 1)
+            rz = maxRStep * (2 * mt.uniform() - 1)
+            if rx * rx + ry * ry + rz * rz < maxRStep * maxRStep:
+                break
+        old = R[:, P].copy()
+        new = old + np.array([rx, ry, rz])                                # :262-271
+        for c in range(3):
+            if new[c] < 0:
+                new[c] += L
+            if new[c] > L:
+                new[c] -= L
+        r, _ = _mcmd_dist(np.stack([new, old], axis=1), R, L)             # :273-296
+        r[:, P] = 1.0
+        u = _mcmd_uij(r, kappa, rCut)
+        u[:, P] = 0.0                                                     # j != NPart (:299, :303)
+        Un = U + (u[0] - u[1])                                            # :305
+        Un[P] = math.fsum(u[0].tolist())                                          # :301, :312
+        dE = math.fsum((Un - U).tolist())                                          # :341-345
+        good = dE < 0                                                     # :347
+        if good:
+            margin = min(margin, abs(dE))
+        else:                                                             # :353-360
+            dice = mt.uniform()
+            odds = math.exp(-(dE / 2) * Gamma)
+            good = dice < odds
+            margin = min(margin, abs(dice - odds))
+        if good:                                                          # :363-376
+            R[:, P] = new
+            U[:] = Un
+            acc += 1
+    return acc, margin
+
+
+def mcmd_accelerations(R, L, kappa, rCut, block=256):
+    """calculateAccelerations :387-448 with calcAIJ :161-169: A[c][i] = sum_j a(r_ij) d_ij,c.  The
+    nearest-image displacement and the test r < rCut are the reference's float64 operations (they
+    fix the pair set); the pair term and the row sums are np.longdouble, rounded once.  Returns
+    (A [3][N], mag [3][N]) with mag[c][i] = sum_j |a(r_ij) d_ij,c| (a scale for summation bounds)."""
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    N = R.shape[1]
+    ld = np.longdouble
+    A = np.empty((3, N)); mag = np.empty((3, N))
+    for i0 in range(0, N, block):
+        i1 = min(N, i0 + block)
+        r, d = _mcmd_dist(R[:, i0:i1], R, L)
+        k = np.arange(i0, i1)
+        r[k - i0, k] = 2 * rCut + 1                          # no self term
+        ii, jj = np.nonzero(r < rCut)
+        dl = d[:, ii, jj].astype(ld)
+        r2 = dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2]
+        rl = np.sqrt(r2)
+        pref = np.exp(-ld(kappa) * rl) * (1 / (r2 * rl) + ld(kappa) / r2)
+        rows = np.searchsorted(ii, np.arange(i1 - i0 + 1))   # ii ascends: where each row's pairs start
+        some = np.diff(rows) > 0                             # reduceat gives f[k] for an empty row
+        for c in range(3):
+            f = np.concatenate([pref * dl[c], np.zeros(1, ld)])
+            A[c, i0:i1] = np.where(some, np.add.reduceat(f, rows[:-1]), 0)
+            mag[c, i0:i1] = np.where(some, np.add.reduceat(np.abs(f), rows[:-1]), 0)
+    return A, mag
+
+
+def mcmd_md_step(R, V, A, L, kappa, rCut, timeStep=0.005, laser=False, oneAxis=False, beta=26000., n=0.4):
+    """MDStep :504-511 with collisionFreq 0: stepPositions :452-467, calculateAccelerations (above),
+    stepVelocities :484-498 with the laser term of either setting of applyForceAlongOneAxisOnly.
+    The per-ion updates are the reference's float64 expressions.  Returns (R, V, A, mag)."""
+    import math
+    R = np.array(R, dtype=np.float64); V = np.array(V, dtype=np.float64)
+    A = np.asarray(A, dtype=np.float64)
+    R = R + timeStep * V + timeStep * timeStep / 2 * A                    # :455-457
+    R = np.where(R < 0, R + L, R)                                         # :459-464
+    R = np.where(R > L, R - L, R)
+    An, mag = mcmd_accelerations(R, L, kappa, rCut)
+    V = V + timeStep / 2 * (A + An)                                       # :484-486
+    if laser:                                                             # :488-498
+        p6 = math.pow(10, -6)
+        sq = math.sqrt(n)
+        if oneAxis:
+            V[0] += V[0] * timeStep * 1.234 * p6 * beta / sq
+        else:
+            V[0] += V[0] * timeStep * 1.234 * p6 * beta / sq / 2
+            V[1] += V[1] * timeStep * 1.234 * p6 * beta / sq / 4 * (-1)
+            V[2] += V[2] * timeStep * 1.234 * p6 * beta / sq / 4 * (-1)
+    return R, V, An, mag
+
+
+def mcmd_pair_corr(R, L, pairPairStep=0.05, block=256):
+    """recordPairPairCorr :591-635: integer bin counts from the reference's float64 distance and its
+    (int)(d / step) truncation, then its normalisation, bin 0 with the integer N*4/3 of :629"""
+    import math
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    N = R.shape[1]
+    nb = int((L / 2) / pairPairStep)
+    h = np.zeros(nb, dtype=np.int64)
+    for i0 in range(0, N, block):
+        i1 = min(N, i0 + block)
+        r, _ = _mcmd_dist(R[:, i0:i1], R, L)
+        b = (r / pairPairStep).astype(np.int64)                           # :615
+        k = np.arange(i0, i1)
+        b[k - i0, k] = nb                                                 # j != i (:597)
+        b = b[b < nb]                                                     # :616
+        h += np.bincount(b, minlength=nb)[:nb]
+    g = np.zeros(nb)
+    ps = pairPairStep
+    for i in range(nb):
+        if i == 0:
+            g[i] = float(h[i]) / ((N * 4 // 3) * math.pi * ps * ps * ps)  # :629
+        else:
+            g[i] = float(h[i]) / (N * 3 * ps * ps * ps * i * i)           # :632
+    return g
+
+
+def mcmd_temperatures(V):
+    """recordTemperature :535-543 and recordTempForEachAxis :567-576: (<v^2> over all components,
+    <vx^2>, <vy^2>, <vz^2>), the float64 squares summed with math.fsum"""
+    import math
+    V = np.asarray(V, dtype=np.float64)
+    N = V.shape[1]
+    sq = V * V
+    return np.array([math.fsum(sq.ravel().tolist()) / (3 * N)] + [math.fsum(sq[c].tolist()) / N for c in range(3)])
+
+
+def mcmd_tag_particles(V, mt, Gamma):
+    """tagParticles :810-921: tags [4][N] from vx and the rolls drawn from mt (an MT19937), which
+    :819-838 and :869-888 draw only for |vx| <= 3 vT"""
+    import math
+    vx = np.asarray(V, dtype=np.float64)[0]
+    N = vx.size
+    vT = math.sqrt(1 / Gamma)
+    tags = np.zeros((4, N), dtype=np.int32)
+    for i in range(N):
+        v = float(vx[i])
+        out = v < -3 * vT or v > 3 * vT
+        tags[0, i] = (v > 3 * vT) if out else (mt.uniform() < (.5 + v / vT / 6))
+        roll = mt.uniform()
+        tags[1, i] = (not roll < .5) if out else (roll < (.5 / 9 / vT / vT * v * v))
+        tags[2, i] = (v > 3 * vT) if out else (mt.uniform() < (.5 + .5 / 27 / vT / vT / vT * v * v * v))
+        roll = mt.uniform()
+        tags[3, i] = (not roll < .5) if out else (roll < (.5 / 81 / vT / vT / vT / vT * v * v * v * v))
+    return tags
+
+
+def mcmd_tagged_moments(V, tags, Gamma):
+    """recordTaggedParticleMoments :937-998 for tags [4][N]: the float64 powers of vx (:941-944)
+    summed with math.fsum.  Returns (out [4][4] = first, second - 1/Gamma, third, fourth -
+    3/Gamma^2 per tag set, mag [4][4] = sum of |term| / count, count [4])."""
+    import math
+    vx = np.asarray(V, dtype=np.float64)[0]
+    out = np.zeros((4, 4)); mag = np.zeros((4, 4)); cnt = np.zeros(4, dtype=np.int64)
+    for t in range(4):
+        v = vx[np.asarray(tags[t]) != 0]
+        cnt[t] = v.size
+        if v.size == 0:
+            out[t] = np.nan
+            continue
+        terms = [v, v * v, v * v * v, v * v * v * v]
+        for m in range(4):
+            out[t, m] = math.fsum(terms[m].tolist()) / v.size
+            mag[t, m] = math.fsum(np.abs(terms[m]).tolist()) / v.size
+        out[t, 1] -= 1 / (Gamma)                                          # :974
+        out[t, 3] -= 3 / (Gamma * Gamma)                                  # :977
+    return out, mag, cnt
+
+
 class MT19937:
     """std::mt19937 (C++ [rand.predef]) + libstdc++'s generate_canonical<double, 53> behind
     uniform_real_distribution<double>(0, 1) (MCMD:53-54): u = (g1 + g2 2^32) / 2^64, values >= 1

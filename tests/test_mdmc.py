@@ -14,6 +14,12 @@ Tolerances (per test):
     <= 2 ulp per pair from the reference's pow(r,-3) form; summation order differs);
   * g(r): every bin equal (integer counts, same normalisation expression);
   * autocorrelations: <= 1e-9 of the largest term (10^7-term sums in different orders).
+
+The reference build exists only at N = 4096.  Every other size (the other Metropolis kernel
+instances, ragged force tiles, partial reduction passes, the autocorrelation blockings) is checked
+in tests/test_gpu_mdmc_sizes.py against the any-N restatements oracle.mcmd_*, with these
+tolerances where a quantity is the same and derived summation bounds elsewhere; the restatements
+are pinned to the reference build in tests/test_mdmc_restatement.py.
 """
 import os
 import tempfile

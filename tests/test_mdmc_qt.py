@@ -21,6 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 MODELS = [1, 2, 3]
+SIZES = [512, 1000]      # 1000: a partly filled last workgroup, k_tagged_kde's last chunk holds 232 ions
 
 
 @pytest.fixture(scope="module")
@@ -80,17 +81,18 @@ def test_qtt_init_wavefunctions(mc, orc):
     e.close()
 
 
+@pytest.mark.parametrize("N", SIZES)
 @pytest.mark.parametrize("model", MODELS)
-def test_qtt_qstep_matches_oracle(mc, orc, model):
+def test_qtt_qstep_matches_oracle(mc, orc, model, N):
     """one pump qstep of every ion vs the oracle's pumping qstep with the QTT constants and the
     same Philox draws (seed, job, ion, qstep 0, draws 0..4)"""
     seed, job = 21, 2
-    e = mc.MonteCarloMD(qt_model=model, N=512, seed=seed, job=job)
+    e = mc.MonteCarloMD(qt_model=model, N=N, seed=seed, job=job)
     e.init()
     rng = np.random.default_rng(model)
     n = 5 if model == 3 else 7
-    z = np.zeros((512, 12), complex)
-    z[:, :n] = rng.normal(size=(512, n)) + 1j * rng.normal(size=(512, n))
+    z = np.zeros((N, 12), complex)
+    z[:, :n] = rng.normal(size=(N, n)) + 1j * rng.normal(size=(N, n))
     z /= np.linalg.norm(z, axis=1, keepdims=True)
     z[:40, 2:2 + (2 if model == 3 else 4)] *= 30.0            # heavy P populations: jumps
     z /= np.linalg.norm(z, axis=1, keepdims=True)
@@ -104,7 +106,7 @@ def test_qtt_qstep_matches_oracle(mc, orc, model):
     o = orc.OracleSim(qt_model=model, Om=e.p.Om, detuning=e.p.detuning, density=2.0)
     o.set_qt_constants(c["dtQ"], c["gamToE"], c["pv2q"], c["r"])
     jumps = 0
-    for i in range(512):
+    for i in range(N):
         u = [orc.philox_uniform(seed, job, i, 0, d) for d in range(5)]
         res = o.qstep_ion(0.0, np.stack([z[i].real, z[i].imag], -1).reshape(-1), V[0, i], 0.0, u)
         ref = res["psi"].reshape(12, 2)
@@ -116,17 +118,18 @@ def test_qtt_qstep_matches_oracle(mc, orc, model):
     e.close()
 
 
+@pytest.mark.parametrize("N", SIZES)
 @pytest.mark.parametrize("model", MODELS)
-def test_qtt_tags_moments_and_distributions(mc, orc, model):
+def test_qtt_tags_moments_and_distributions(mc, orc, model, N):
     seed, job = 8, 1
-    e = mc.MonteCarloMD(qt_model=model, N=512, seed=seed, job=job)
+    e = mc.MonteCarloMD(qt_model=model, N=N, seed=seed, job=job)
     e.init()
     e.qsteps(7)
     psi = e.get_psi()
     tags, cnt = e.tag_qt()
     nr = np.abs(psi) ** 2
-    exp = np.zeros(512, np.int32)
-    for i in range(512):                                         # QTT:1022-1067 / 422 :992-1034
+    exp = np.zeros(N, np.int32)
+    for i in range(N):                                         # QTT:1022-1067 / 422 :992-1034
         rnd = orc.philox_uniform(seed, job, i, 7, 6)
         r2 = orc.philox_uniform(seed, job, i, 7, 7)
         if model == 3:
@@ -149,6 +152,30 @@ def test_qtt_tags_moments_and_distributions(mc, orc, model):
         v = V[c][tags == 1]
         P = np.exp(-V2 * (vel[:, None] - v[None, :]) ** 2).sum(1) / (6.0 * math.sqrt(2 * math.pi * 0.002 * 0.002))
         assert np.abs(dist[c] - P).max() <= 1e-12 * P.max()
+    e.close()
+
+
+def test_tagged_moments_with_one_recorded_step(mc, orc):
+    """numVelAutoCorrsSteps = 1, the smallest accepted: the moment kernel's 20 sums land in the buffer
+    the [4][T] autocorrelations share (sized for the larger of the two)"""
+    seed, job, N = 6, 1, 512
+    e = mc.MonteCarloMD(qt_model=1, N=N, seed=seed, job=job, numVelAutoCorrsSteps=1)
+    e.init()
+    _, V, _, _ = e.get_state()
+    tags4 = e.tag_particles()
+    assert tags4.sum(axis=1).min() > 0
+    m = e.tagged_moments()
+    m0, mag, _ = orc.mcmd_tagged_moments(V, tags4, e.p.Gamma)
+    assert np.all(np.abs(m - m0) <= (N + 8) * 2.0 ** -53 * mag)      # any order of an N-term sum
+    e.qsteps(7)
+    tags, cnt = e.tag_qt()
+    assert 0 < cnt == tags.sum()
+    mom = e.tagged_moments_qt(dist=False)
+    vx = V[0][tags == 1]
+    ref = [vx.sum() / cnt, (vx * vx).sum() / cnt, (vx * vx * vx).sum() / cnt, (vx * vx * vx * vx).sum() / cnt]
+    np.testing.assert_allclose(mom, ref, rtol=1e-12, atol=1e-15)
+    t = e.temperatures()
+    assert np.all(np.abs(t - orc.mcmd_temperatures(V)) <= (N + 8) * 2.0 ** -53 * t)
     e.close()
 
 
