@@ -305,7 +305,7 @@ def test_c2_headline_qt_instance_matches_oracle(eng, orc):
           f"|dpsi|={dpsi:.2e} F rel={dF:.2e}")
     assert dR <= 1e-10 and dV <= 1e-10
     assert dpsi <= 1e-9
-    assert dF <= 1e-12
+    assert dF <= 1e-13                               # BASELINE's force gate (recorded: 2.19e-14)
     s.close()
 
 
