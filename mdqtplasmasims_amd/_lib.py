@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# MDQT_LIB: an alternative build of the same library (kernel A/B experiments, tools/expt.sh)
+# MDQT_LIB: an alternative build of the same library (kernel A/B experiments, tools/expt_build.sh)
 LIB_PATH = os.environ.get("MDQT_LIB") or os.path.join(HERE, "lib", "libmdqt.so")
 CLI_PATH = os.path.join(HERE, "bin", "mdqt")
 MDMC_CLI_PATH = os.path.join(HERE, "bin", "mdmc")

@@ -36,12 +36,6 @@ typedef struct ncclComm* ncclComm_t;
         if (r_ != ncclSuccess) return mdqt::set_error("%s failed: %s", #expr, ncclGetErrorString(r_)); \
     } while (0)
 
-#ifndef MDQT_TAIL_MODE
-#define MDQT_TAIL_MODE 1
-#endif
-#ifndef MDQT_FORM_MODE
-#define MDQT_FORM_MODE 2
-#endif
 struct mdqt_ctx {
     mdqt_params p;
     // derived constants (SpeedUp:79-85, :146-149, :295-297)
@@ -60,10 +54,8 @@ struct mdqt_ctx {
            *dTp = nullptr, *dScr = nullptr, *dKde = nullptr, *dUrow = nullptr;
     double* dUpart = nullptr;      // potential-row partials of its own (small systems, world 1)
     int n3_potential = 1;          // option "potential_n3": 1 = Newton-3 tiles where the forces use them
-#ifndef MDQT_N3B_PAIRS_DEFAULT
-#define MDQT_N3B_PAIRS_DEFAULT 1                  // A/B round 6 (r06e): N = 1M force call -4.3 %, C5 -2.3 %, C3 -2.3 %
-#endif
-    int n3b_pairs = MDQT_N3B_PAIRS_DEFAULT;   // option "force_n3b_pairs": the paired-wave block kernel (k_pairs_n3b_pw)
+    int n3b_pairs = 1;             // option "force_n3b_pairs": the paired-wave block kernel (k_pairs_n3b_pw); A/B round 6
+                                   // (r06e): N = 1M force call -4.3 %, C5 -2.3 %, C3 -2.3 %
     int pot_plan = 1;              // option "potential_plan": 1 = Epotential on the blocks takes the force call's
                                    // plan (skips, sub-tile groups, error-bounded forms); 0 = every pair to L/2 exactly
     size_t capUpart = 0;
@@ -100,7 +92,7 @@ struct mdqt_ctx {
     // pairs on the device (k_pairs_n3b; all-reduced over the ranks), and every tile whose sum
     // exceeds eps gets the exact sum over those tile pairs added to its rows (k_tail_fix) — so every
     // ion meets eps whatever the configuration; the host widens r_t when that happened (tail_check)
-    int tail_mode = MDQT_TAIL_MODE;
+    int tail_mode = 1;
     double* dTail = nullptr;       // [4T]: the per-sub-tile sums of the current call
     unsigned long long* dTailSt = nullptr;   // [8]: k_tail_max's running maxima and counters
     int* dTailList = nullptr;      // [T]: this call's tiles over eps (this rank's)
@@ -133,8 +125,8 @@ struct mdqt_ctx {
     // recomputed exactly (k_tail_fix), and the radii come from the density model of those sums
     // (tier_radius) — so every ion meets that eps whatever the configuration; 2 as 1, and where the tail
     // is exact (r_t = L/2) the tiers share its unused 10^-tail_exp (tier_eps): the same total per ion.  2 is the
-    // default (MDQT_FORM_MODE): where the tail is exact (C3 / C5) the per-ion bound is then 1.5e-12, not 1's 5e-13
-    int form_mode = MDQT_FORM_MODE;
+    // default: where the tail is exact (C3 / C5) the per-ion bound is then 1.5e-12, not 1's 5e-13
+    int form_mode = 2;
     mutable double form_key[6][6] = {}, form_val[6][2] = {};   // tier_radius memo by level (N, L, lDeb, k, tail_exp, scale)
     uint32_t* dKeys = nullptr;     // [2][N] Hilbert keys, sorted keys
     int* dIon = nullptr;           // [2][N] identity, sorted index -> ion

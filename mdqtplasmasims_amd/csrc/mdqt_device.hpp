@@ -120,9 +120,6 @@ __device__ __forceinline__ cxd renorm_div(cxd w, double sumsq) {
 // sincos.  F = true: Cody-Waite reduction by pi/2 (three-part constant, FMA) and the classic
 // minimax kernels on [-pi/4, pi/4] (fdlibm's __kernel_sin/__kernel_cos coefficients, < 1 ulp),
 // about a third of the library's instruction count; |x| >= 2^20 takes the library path.
-#ifndef MDQT_FAST_SINCOS
-#define MDQT_FAST_SINCOS 1
-#endif
 // Horner step z * p + c as one three-address v_fma_f64.  (With the coefficient c held in a VGPR —
 // the lane kernel's SGPRs are all taken — the compiler otherwise emits a copy of c and the
 // two-address v_fmac_f64: one extra VALU per step.)  Same operation, same value as fma(z, p, c).
@@ -159,7 +156,7 @@ __device__ __forceinline__ void sincos_fast(double x, double& sn, double& cs) {
 }
 template <bool F>
 __device__ __forceinline__ void sincos_q(double x, double& sn, double& cs) {
-    if (!F || !MDQT_FAST_SINCOS || !(fabs(x) < 1048576.)) {
+    if (!F || !(fabs(x) < 1048576.)) {
         sincos(x, &sn, &cs);
         return;
     }
@@ -172,9 +169,6 @@ __device__ __forceinline__ void sincos_q(double x, double& sn, double& cs) {
 // r^8: truncation below 1e-20) and the table entries correctly rounded (60-digit decimal
 // arithmetic).  22 VALU and one LDS read instead of sincos_fast's ~40; <= 2 ulp.  |x| < 2^20 (the
 // callers take the library beyond).  `tab`: kSinCos64 (cos, sin pairs) in LDS or global memory.
-#ifndef MDQT_QT_SCTAB
-#define MDQT_QT_SCTAB 1
-#endif
 static __constant__ const double kSinCos64[128] = {
     0x1.0000000000000p+0, 0x0.0p+0, 0x1.fd88da3d12526p-1, 0x1.917a6bc29b42cp-4,
     0x1.f6297cff75cb0p-1, 0x1.8f8b83c69a60bp-3, 0x1.e9f4156c62ddap-1, 0x1.294062ed59f06p-2,
@@ -224,15 +218,13 @@ __device__ __forceinline__ void sincos_tab(double x, const double* tab, double& 
     sn = fma(ts, cr, tc * sr);
     cs = fma(tc, cr, -(ts * sr));
 }
-// the qt_math 2 kernels' phase: the table form (MDQT_QT_SCTAB) or sincos_fast, the library for
-// |x| >= 2^20
+// the qt_math 2 kernels' phase: the table form, the library for |x| >= 2^20
 __device__ __forceinline__ void sincos_q2(double x, const double* tab, double& sn, double& cs) {
     if (!(fabs(x) < 1048576.)) {
         sincos(x, &sn, &cs);
         return;
     }
-    if (MDQT_QT_SCTAB) sincos_tab(x, tab, sn, cs);
-    else sincos_fast(x, sn, cs);
+    sincos_tab(x, tab, sn, cs);
 }
 
 __device__ __forceinline__ double rho_im(cxd a, cxd b) {   // Im(a * conj(b)), SpeedUp:490-502
@@ -244,7 +236,6 @@ __device__ __forceinline__ double gat(double v, int src) {
     const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(v));
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ cxd gatc(cxd v, int src) { return {gat(v.re, src), gat(v.im, src)}; }
 
 // DPP moves inside a 16-lane row (one ion): row_shl:n (lane l reads lane l+n), row_shr:n
 // (lane l reads lane l-n), row_newbcast:n (every lane reads lane n of its row).  VALU-latency
@@ -252,9 +243,6 @@ __device__ __forceinline__ cxd gatc(cxd v, int src) { return {gat(v.re, src), ga
 // Row gathers of the sparse matvec through LDS (one ds_write_b128 + three ds_read_b128 per
 // exchange) instead of twelve ds_bpermute_b32; the 16-lane group lives in one wave, whose LDS
 // operations execute in order, so a wave-scope fence is the only synchronisation needed.
-#ifndef MDQT_GATHER_LDS
-#define MDQT_GATHER_LDS 1
-#endif
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

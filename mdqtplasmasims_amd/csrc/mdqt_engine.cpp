@@ -392,10 +392,7 @@ void mdqt::n3b_set_range(N3BArgs& b, int lo, int hi) {
     b.Plo = lo;
     b.Phi = hi;
     const int nblk = std::max(b.Phi - b.Plo, 1);
-    static const int wg_target = [] {               // (A/B experiments: MDQT_N3B_WG workgroups per rank)
-        const char* e = getenv("MDQT_N3B_WG");
-        return e && atoi(e) > 0 ? atoi(e) : 65536;
-    }();
+    constexpr int wg_target = 65536;                // workgroups per rank
     int R = std::min(b.nd, (wg_target + nblk - 1) / nblk);
     b.runlen = (b.nd + R - 1) / R;
     b.R = (b.nd + b.runlen - 1) / b.runlen;

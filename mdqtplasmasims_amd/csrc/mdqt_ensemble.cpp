@@ -2,7 +2,7 @@
 // per MD step (include/mdqt.h, "ensembles").  It works on mdqt_ctx's internals (mdqt_ctx.hpp) and on
 // the argument helpers the single-job path uses (mdqt_step.cpp: n3_force_args, substep_args), so a member's launch arguments are the ones its own mdqt_forces / mdqt_substeps
 // would pass — which is the whole bit-identity argument: the batched kernels run the single-job
-// kernels' bodies on those arguments (mdqt_forces.hip k_pairs_n3_ens, mdqt_qtfast.hip LANE_ENS_KERNELS).
+// kernels' bodies on those arguments (mdqt_forces.hip k_pairs_n3_ens, mdqt_ensemble_qt.hip LANE_ENS_KERNELS).
 //
 // The reference runs this program as a Slurm array of 99 independent jobs (exampleSlurmFile.slurm:3,
 // srand48(time + job), SpeedUp:1219); one job of N0 = 3500 does not fill an MI355X.

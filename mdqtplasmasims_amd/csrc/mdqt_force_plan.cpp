@@ -169,7 +169,7 @@ int mdqt::tail_enforce(mdqt_ctx* s, const N3BArgs& a, double* out) {
 // L/2 (= never) and bound 0 when k = 0 or that r is >= L/2; bound = (N - 1) g(r) err(r)
 static double far_err(double r, double lDeb, int level) {
     if (level == 5) return (r / lDeb + 3.) * (kRsq1RelErr + 0x1p-52) + kTab4RelErr;   // the mid form
-    if (level == 4) return (r / lDeb) * kUfar32A + kUfar32B;   // the f32 ultra-far form (MDQT_UFAR32)
+    if (level == 4) return (r / lDeb) * kUfar32A + kUfar32B;   // the f32 ultra-far form
     if (level == 3) return (r / lDeb) * (kRsqRawErr + 0x1p-24) + 3. * kRsqRawErr + kExp2fRelErr;
     return level == 2 ? (r / lDeb + 3.) * kRsqRawErr + kExp5RelErr : kFarRelErr;
 }
@@ -214,8 +214,7 @@ static double tier_eps(const mdqt_ctx* s, int k) {
     double e = pow(10., -k);
     double tb;
     if (s->form_mode == 2 && form_measured(s) && s->tail_exp > 0 && tail_radius_sum(s, &tb) >= s->L / 2.) {
-        const int n = (MDQT_EXP_TAB && s->mid_exp > 0) + (s->far_exp > 0) + (s->vfar_exp > 0) +
-                      (s->ufar_exp > 0) * (MDQT_UFAR32 ? 2 : 1);
+        const int n = (s->mid_exp > 0) + (s->far_exp > 0) + (s->vfar_exp > 0) + (s->ufar_exp > 0) * 2;
         e += pow(10., -s->tail_exp) / n;
     }
     return e;
@@ -292,11 +291,11 @@ static double model_total(const mdqt_ctx* s) {
     const double rt = tail_radius_sum(s, &t);
     if (rt < s->L / 2.) b += t;
     if (form_measured(s)) {
-        if (MDQT_EXP_TAB && tier_radius(s, s->mid_exp, 5, &t) < rt) b += t;
+        if (tier_radius(s, s->mid_exp, 5, &t) < rt) b += t;
         if (tier_radius(s, s->far_exp, 1, &t) < rt) b += t;
         if (tier_radius(s, s->vfar_exp, 2, &t) < rt) b += t;
         if (tier_radius(s, s->ufar_exp, 3, &t) < rt) b += t;
-        if (MDQT_UFAR32 && tier_radius(s, s->ufar_exp, 4, &t) < rt) b += t;
+        if (tier_radius(s, s->ufar_exp, 4, &t) < rt) b += t;
     }
     return b;
 }
@@ -305,11 +304,11 @@ static double model_total(const mdqt_ctx* s) {
 double mdqt::error_eps(const mdqt_ctx* s, const N3BArgs& a) {
     double e = a.Rskip < a.Rcut ? pow(10., -s->tail_exp) : 0.;
     if (a.formm) {
-        if (MDQT_EXP_TAB && a.Rmid < a.Rskip) e += tier_eps(s, s->mid_exp);
+        if (a.Rmid < a.Rskip) e += tier_eps(s, s->mid_exp);
         if (a.Rfar < a.Rskip) e += tier_eps(s, s->far_exp);
         if (a.Rvfar < a.Rskip) e += tier_eps(s, s->vfar_exp);
         if (a.Rufar < a.Rskip) e += tier_eps(s, s->ufar_exp);
-        if (MDQT_UFAR32 && a.Rufar32 < a.Rskip) e += tier_eps(s, s->ufar_exp);
+        if (a.Rufar32 < a.Rskip) e += tier_eps(s, s->ufar_exp);
     }
     return e;
 }
@@ -317,11 +316,11 @@ double mdqt::error_eps(const mdqt_ctx* s, const N3BArgs& a) {
 // the tiers' radii of a force call (a.Rcut set): a priori or from the model (force_form_mode 1)
 void mdqt::tier_radii(const mdqt_ctx* s, N3BArgs& a) {
     double bound;
-    a.Rmid = MDQT_EXP_TAB ? tier_radius(s, s->mid_exp, 5, &bound) : a.Rcut;
+    a.Rmid = tier_radius(s, s->mid_exp, 5, &bound);
     a.Rfar = tier_radius(s, s->far_exp, 1, &bound);
     a.Rvfar = tier_radius(s, s->vfar_exp, 2, &bound);
     a.Rufar = tier_radius(s, s->ufar_exp, 3, &bound);
-    a.Rufar32 = MDQT_UFAR32 ? tier_radius(s, s->ufar_exp, 4, &bound) : a.Rcut;
+    a.Rufar32 = tier_radius(s, s->ufar_exp, 4, &bound);
     a.formm = form_measured(s) ? 1 : 0;
     a.u32lim2 = (a.Rcut * (1. - 0x1p-20)) * (a.Rcut * (1. - 0x1p-20));
     // f32's normal range: 2^t for t >= -126 (r <= 126 lDeb ln2 = 87 lDeb); never beyond it

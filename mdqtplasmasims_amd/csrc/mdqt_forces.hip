@@ -170,13 +170,9 @@ extern "C" int mdqt_expt_n3_stamps(unsigned long long* out, int n) {
 // run order, skipping slots this rank does not write.
 // ------------------------------------------------------------------------------------------
 constexpr int BW = kN3BBlock;                       // tiles per block = waves per workgroup
-#ifndef MDQT_N3B_AX1
-#define MDQT_N3B_AX1 1                              // the one-axis per-pair image (n3b_pack_class); 0: all three axes
-#endif
-#ifndef MDQT_N3B_AX1_LEVELS
-#define MDQT_N3B_AX1_LEVELS 0x1E                    // bit x: far level x takes it (1 mid, 2 far, 3 very far,
-                                                    // 4 ultra far and its f32 level: the f64 ultra-far form, round 6)
-#endif
+// the far levels that take the one-axis per-pair image (n3b_pack_class): bit x = far level x (1 mid, 2 far,
+// 3 very far, 4 ultra far and its f32 level: the f64 ultra-far form, round 6)
+constexpr unsigned kAx1Levels = 0x1E;
 #if defined(MDQT_EXPT_CLS)
 // diagnostic build only: tile-pair classes of k_pairs_n3b (skip, per pair, uniform image)
 __device__ unsigned long long g_cls_count[3];
@@ -215,28 +211,11 @@ __device__ __forceinline__ const double* tile_base(const double* Rall, int tile,
 // (the sub-tile pairs (0, 2), (1, 3) once); group 3 would repeat group 1's pairs.
 __device__ __forceinline__ int n3b_lds(int l) { return 32 * (l >> 4) + (l & 15); }   // J ion l's first copy
 
-// The lane index recomputed where it is used (MDQT_N3B_REMAT): two VALU (v_mbcnt) in volatile asm, which
+// The lane index recomputed where it is used: two VALU (v_mbcnt) in volatile asm, which
 // the compiler neither hoists nor merges — so no VGPR holds the lane index, or a value derived from it,
 // across the block kernel's J-step loop (at its 80-VGPR budget such values were spilled and reloaded
 // with a vmcnt(0) wait at every pair-form dispatch)
-#ifndef MDQT_N3B_REMAT
-#define MDQT_N3B_REMAT 1
-#endif
-// One LDS-DMA load (global_load_lds_dwordx4: 16 bytes per lane from the lane's address g, into LDS at the
-// wave-uniform byte offset lds + 16 x lane), in inline asm so that the compiler's wait-count pass does
-// not see it: with the builtin it waited vmcnt(0) before every LDS atomic of the pair loops (a DMA
-// writing LDS might alias them), retiring the DMA at once.  The caller counts and waits for it.
-__device__ __forceinline__ void lds_dma16(const void* g, unsigned lds) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(lds) : "memory");
-}
-template <typename T>
-__device__ __forceinline__ unsigned lds_offset(T* p) {          // a __shared__ object's LDS byte offset
-    return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) T*)p);
-}
-__device__ __forceinline__ int lane_opaque(int l) {
-    if constexpr (!MDQT_N3B_REMAT) return l;
+__device__ __forceinline__ int lane_opaque(int) {   // (the argument: the lane index it stands for)
     int r;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(r));
     return r;
@@ -254,63 +233,42 @@ __device__ __forceinline__ int lane_opaque(int l) {
     double *axb = ax + b_, *ayb = ay + b_, *azb = az + b_
 
 // one sub-tile group: 16 rotation steps from LDS index b0 (the lane's first J ion) with weight w
-template <int VARIANT, bool GUARD, bool RAGGED, bool SHIFT = false, bool CUT = VARIANT == 1 && MDQT_N3_CUT,
+template <int VARIANT, bool GUARD, bool RAGGED, bool SHIFT = false, bool CUT = VARIANT == 1,
           bool POT = false, int FAR = 0, int NSTEP = 16, int MAX = -1>
 __device__ __forceinline__ void n3b_group(int b0, double w, double xi, double yi, double zi, double mi,
                                           const double (*pj)[128], const double* mj, double* ax, double* ay,
                                           double* az, double& fx, double& fy, double& fz, const PairC& c,
-                                          const double* nsh, double w_last = 1.) {
+                                          double w_last = 1.) {
     N3B_REBASE(b0);
-    if constexpr (MDQT_N3_DEFER_J) {
-        // the j side one step late (n3_step_defer): each step's LDS reads queue behind the previous
-        // step's atomics only one step later — the same adds in the same order, bit for bit
-        double qx = 0., qy = 0., qz = 0.;
 #pragma unroll
-        for (int t = 0; t < NSTEP; ++t)
-            n3_step_defer<VARIANT, GUARD, RAGGED, SHIFT, CUT, POT, FAR, MAX>(t, t == NSTEP - 1 ? w * w_last : w, xi, yi, zi,
-                                                                             mi, pjb, mjb, axb, ayb, azb, fx, fy, fz, c,
-                                                                             nsh, t - 1, qx, qy, qz);
-        n3_j_add<POT>(NSTEP - 1, axb, ayb, azb, qx, qy, qz);
-        return;
-    }
-    LdsPJ p = lds_pj(pjb, 0);
-#pragma unroll
-    for (int t = 0; t < NSTEP; ++t) {
-        if constexpr (MDQT_LDS_SPLIT) {             // (the LDS bases opaque per step: ds_read_b64, no read2)
-            lds_pj_opaque(p);
-            n3_step<VARIANT, GUARD, RAGGED, SHIFT, CUT, POT, FAR, MAX, LdsPJ>(t, t == NSTEP - 1 ? w * w_last : w, xi, yi,
-                                                                              zi, mi, p, mjb, axb, ayb, azb, fx, fy, fz,
-                                                                              c, nsh);
-        } else {
-            n3_step<VARIANT, GUARD, RAGGED, SHIFT, CUT, POT, FAR, MAX>(t, t == NSTEP - 1 ? w * w_last : w, xi, yi, zi,
-                                                                       mi, pjb, mjb, axb, ayb, azb, fx, fy, fz, c, nsh);
-        }
-    }
+    for (int t = 0; t < NSTEP; ++t)
+        n3_step<VARIANT, GUARD, RAGGED, SHIFT, CUT, POT, FAR, MAX>(t, t == NSTEP - 1 ? w * w_last : w, xi, yi, zi, mi, pjb,
+                                                                   mjb, axb, ayb, azb, fx, fy, fz, c);
 }
 
 // a whole tile pair in one pair form: the groups of `groups` (off the diagonal) or the diagonal
 // tile's three groups
-template <int VARIANT, bool GUARD, bool RAGGED, bool SHIFT = false, bool CUT = VARIANT == 1 && MDQT_N3_CUT,
+template <int VARIANT, bool GUARD, bool RAGGED, bool SHIFT = false, bool CUT = VARIANT == 1,
           bool POT = false, int FAR = 0, int MAX = -1>
 __device__ __forceinline__ void n3b_pair(bool diag, unsigned groups, int l, double xi, double yi, double zi,
                                          double mi, const double (*pj)[128], const double* mj, double* ax,
                                          double* ay, double* az, double& fx, double& fy, double& fz,
-                                         const PairC& c, const double* nsh = nullptr) {
+                                         const PairC& c) {
     l = lane_opaque(l);
     const int a = l >> 4, m = l & 15;
     if (!diag) {
         for (int d = 0; d < 4; ++d) {
             if (!((groups >> d) & 1u)) continue;    // wave-uniform
             n3b_group<VARIANT, GUARD, RAGGED, SHIFT, CUT, POT, FAR, 16, MAX>(32 * ((a + d) & 3) + m, 1., xi, yi, zi, mi, pj,
-                                                                             mj, ax, ay, az, fx, fy, fz, c, nsh);
+                                                                             mj, ax, ay, az, fx, fy, fz, c);
         }
     } else if constexpr (MAX < 0) {                 // (a tile with itself has one image)
         // sub-tile distance 1..8 inside each sub-tile, the 8th once (m < 8)
         n3b_group<VARIANT, GUARD, RAGGED, SHIFT, CUT, POT, FAR, 8>(32 * a + m + 1, 1., xi, yi, zi, mi, pj, mj, ax, ay, az,
-                                                                   fx, fy, fz, c, nsh, m >= 8 ? 0. : 1.);
+                                                                   fx, fy, fz, c, m >= 8 ? 0. : 1.);
         for (int d = 1; d < 3; ++d)
             n3b_group<VARIANT, GUARD, RAGGED, SHIFT, CUT, POT, FAR>(32 * ((a + d) & 3) + m, (d == 2 && a >= 2) ? 0. : 1.,
-                                                                    xi, yi, zi, mi, pj, mj, ax, ay, az, fx, fy, fz, c, nsh);
+                                                                    xi, yi, zi, mi, pj, mj, ax, ay, az, fx, fy, fz, c);
     }
 }
 
@@ -319,10 +277,10 @@ __device__ __forceinline__ float row_rol1f(float v) {   // lane 16 a + m <- lane
 }
 
 // An ultra-far tile pair (boxes >= r_ufar32 apart) with a uniform image, pair terms in f32
-// (MDQT_UFAR32; error analysis and bound in mdqt_internal.hpp kUfar32A/B).  Round 5: the staging wave
+// (error analysis and bound in mdqt_internal.hpp kUfar32A/B).  Round 5: the staging wave
 // also holds the J tile in f32 relative to its first ion c_J (pj32 = fl32(xj - c_J)), the wave takes
 // xi32 = fl32(xi - n L - c_J) once per tile pair and dx = fl32(xi32 - pj32) — no f64 subtraction and
-// f32 conversion per pair — and (MDQT_UF32_PK) runs two rotation steps t, t + 1 through each packed
+// f32 conversion per pair — and runs two rotation steps t, t + 1 through each packed
 // instruction (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32; v_rsq_f32, v_exp_f32 and the cutoff select
 // per step): 16.75 VALU instructions per pair instead of 29.  The cutoff on the f32 r^2 (t = -inf).  The
 // i side is summed in two f32 partials (even and odd steps), added, then added to the f64 partial; the j
@@ -331,18 +289,14 @@ __device__ __forceinline__ float row_rol1f(float v) {   // lane 16 a + m <- lane
 // once: row_ror:14 of the sum plus row_ror:15 of step t's term plus step t + 1's) and ends in one
 // ds_add_f64 per component at the group's last index.  Off the diagonal only (a tile's pair with
 // itself is never ultra far).
-static_assert(MDQT_SHIFT_I || !MDQT_UFAR32, "the f32 ultra-far form needs MDQT_SHIFT_I");
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float row_rol2f(float v) {   // lane 16 a + m <- lane 16 a + ((m + 2) & 15)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x12E, 0xF, 0xF, false));   // row_ror:14
 }
-// two rotation steps per v_pk_* instruction (MDQT_UF32_PK 1): gfx950 runs a packed f32 operation at half
+// two rotation steps per v_pk_* instruction: gfx950 runs a packed f32 operation at half
 // the rate of a scalar one (tools/ubench_f64: the same VALU cycles per pair) but issues half the
 // instructions — A/B round 5 (profiles/r05h_uf32_force_ab.txt): C4 force call 244.8 ms packed, 248.3 scalar,
-// 254.1 with the round-4 form (f64 separations); N = 1M 198.0 / 200.3 / 205.3.  0: one step at a time
-#ifndef MDQT_UF32_PK
-#define MDQT_UF32_PK 1
-#endif
+// 254.1 with the round-4 form (f64 separations); N = 1M 198.0 / 200.3 / 205.3
 
 // POT (Epotential on the plan, round 6): u = 2^t ri in the same f32 operations, one component (i side in
 // fx, j side in ax); its relative error is within the force form's (one factor ri instead of three)
@@ -378,7 +332,7 @@ __device__ __forceinline__ void n3b_group_uf32(int b0, float xi, float yi, float
         __hip_atomic_fetch_add(ax + b0 + 15, (double)ju, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         fx += (double)(iu.x + iu.y);
         (void)ay; (void)az; (void)fy; (void)fz; (void)invlf;
-    } else if constexpr (MDQT_UF32_PK) {
+    } else {
         f32x2 ix = {0.f, 0.f}, iy = {0.f, 0.f}, iz = {0.f, 0.f};
         float jx = 0.f, jy = 0.f, jz = 0.f;
 #pragma unroll
@@ -410,32 +364,6 @@ __device__ __forceinline__ void n3b_group_uf32(int b0, float xi, float yi, float
         __hip_atomic_fetch_add(ay + b_ + 15, (double)jy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         __hip_atomic_fetch_add(az + b_ + 15, (double)jz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         fx += (double)(ix.x + ix.y); fy += (double)(iy.x + iy.y); fz += (double)(iz.x + iz.y);
-    } else {
-        float ix = 0.f, iy = 0.f, iz = 0.f, jx = 0.f, jy = 0.f, jz = 0.f;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const float dx = xi - px0[t], dy = yi - py0[t], dz = zi - pz0[t];
-            const float r2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-            const float ri = __builtin_amdgcn_rsqf(r2);
-            const float e = __builtin_amdgcn_exp2f(r2 < rc2f ? (r2 * ri) * cf : -INFINITY);
-            const float ft = ((ri + invlf) * e) * (ri * ri);
-            const float px = dx * ft, py = dy * ft, pz = dz * ft;
-            if (t == 0) {
-                ix = px; iy = py; iz = pz;
-                jx = px; jy = py; jz = pz;
-            } else {
-                ix += px; iy += py; iz += pz;
-                jx = row_rol1f(jx) + px; jy = row_rol1f(jy) + py; jz = row_rol1f(jz) + pz;
-            }
-            // each step's i and j sums formed in their step: without it the compiler sank the DPP adds
-            // and the i-side adds after the last step and spilled the pending terms (80-VGPR budget)
-            asm volatile("" : "+v"(ix), "+v"(iy), "+v"(iz));
-        }
-        const int b_ = b0;
-        __hip_atomic_fetch_add(ax + b_ + 15, (double)jx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __hip_atomic_fetch_add(ay + b_ + 15, (double)jy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __hip_atomic_fetch_add(az + b_ + 15, (double)jz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        fx += (double)ix; fy += (double)iy; fz += (double)iz;
     }
 }
 
@@ -466,11 +394,11 @@ template <int VARIANT, bool POT>
 __device__ __forceinline__ N3BRadii n3b_radii(const N3BArgs& a) {
     N3BRadii r;
     r.rc2 = POT ? a.Rcut * a.Rcut : a.Rskip * a.Rskip;
-    r.rm2 = (POT || VARIANT != 1 || !MDQT_EXP_TAB || !(a.Rmid < a.Rcut)) ? INFINITY : a.Rmid * a.Rmid;
+    r.rm2 = (POT || VARIANT != 1 || !(a.Rmid < a.Rcut)) ? INFINITY : a.Rmid * a.Rmid;
     r.rf2 = (POT || VARIANT != 1 || !(a.Rfar < a.Rcut)) ? INFINITY : a.Rfar * a.Rfar;
     r.rv2 = (POT || VARIANT != 1 || !(a.Rvfar < a.Rcut)) ? INFINITY : a.Rvfar * a.Rvfar;
     r.ru2 = (POT || VARIANT != 1 || !(a.Rufar < a.Rcut)) ? INFINITY : a.Rufar * a.Rufar;
-    r.ru32 = (POT || VARIANT != 1 || !MDQT_UFAR32 || !(a.Rufar32 < a.Rcut)) ? INFINITY : a.Rufar32 * a.Rufar32;
+    r.ru32 = (POT || VARIANT != 1 || !(a.Rufar32 < a.Rcut)) ? INFINITY : a.Rufar32 * a.Rufar32;
     return r;
 }
 // the far level of a squared gap: 0 exact, 1 mid, 2 far, 3 very far, 4 ultra far, 5 ultra far in f32
@@ -621,7 +549,7 @@ __device__ __forceinline__ int n3b_pack_class(double4 t4, int strad = 0) {
     if (uni && !(fabs(t4.x) <= 127. && fabs(t4.y) <= 127. && fabs(t4.z) <= 127.)) cls -= 1;
     const bool u2 = cls >= 0 && (cls & 1);
     const int ax1 = strad == 1 ? 1 : strad == 2 ? 2 : strad == 4 ? 3 : 0;
-    const bool one = MDQT_N3B_AX1 && cls >= 0 && !(cls & 1) && ax1 &&
+    const bool one = cls >= 0 && !(cls & 1) && ax1 &&
                      fabs(t4.x) <= 127. && fabs(t4.y) <= 127. && fabs(t4.z) <= 127.;
     const int nx = (u2 || (one && ax1 != 1)) ? (int)t4.x : 0, ny = (u2 || (one && ax1 != 2)) ? (int)t4.y : 0,
               nz = (u2 || (one && ax1 != 3)) ? (int)t4.z : 0;
@@ -654,7 +582,7 @@ __device__ __forceinline__ void n3b_tile_pair(const N3BArgs& a, const PairC& c, 
                                               const double (*pj)[128], const double* mj, const float (*pj32)[128],
                                               double* ax, double* ay, double* az, double& tx, double& ty, double& tz,
                                               float cf32, float invl32, float rc2f) {
-    constexpr bool CUT = VARIANT == 1 && MDQT_N3_CUT;
+    constexpr bool CUT = VARIANT == 1;
     constexpr bool FARF = VARIANT == 1 && !GUARD && CUT;   // the error-bounded pair forms
     const unsigned groups = word & 15u;
     const int ci = (tw & 15) - 2;       // bit 0 uniform image (the tile pair's)
@@ -663,38 +591,36 @@ __device__ __forceinline__ void n3b_tile_pair(const N3BArgs& a, const PairC& c, 
                                                         az, tx, ty, tz, c);
     else if (VARIANT == 1 && (ci & 1)) {       // uniform image
         const double nsh[3] = {(double)((tw << 20) >> 24), (double)((tw << 12) >> 24), (double)((tw << 4) >> 24)};
-        // xi - n L once per tile pair (n3_step SHIFT; MDQT_SHIFT_I)
-        const double sx = MDQT_SHIFT_I ? fma(-nsh[0], a.L, xi) : xi;
-        const double sy = MDQT_SHIFT_I ? fma(-nsh[1], a.L, yi) : yi;
-        const double sz = MDQT_SHIFT_I ? fma(-nsh[2], a.L, zi) : zi;
+        // xi - n L once per tile pair (n3_step SHIFT)
+        const double sx = fma(-nsh[0], a.L, xi);
+        const double sy = fma(-nsh[1], a.L, yi);
+        const double sz = fma(-nsh[2], a.L, zi);
         if constexpr (FARF) {
             if (diag) {                 // (a tile with itself: the exact form)
                 n3b_pair<VARIANT, GUARD, false, true, CUT, POT>(true, groups, l, sx, sy, sz, mi, pj, mj, ax, ay,
-                                                                az, tx, ty, tz, c, nsh);
+                                                                az, tx, ty, tz, c);
             } else {                    // each form over the groups at its level
                 const unsigned g5 = level_groups(word, 5), g4 = level_groups(word, 4),
                                g3 = level_groups(word, 3), g2 = level_groups(word, 2),
                                g1 = level_groups(word, 1), g0 = level_groups(word, 0);
                 if (g4) n3b_pair<VARIANT, GUARD, false, true, CUT, POT, 4>(false, g4, l, sx, sy, sz, mi, pj, mj,
-                                                                           ax, ay, az, tx, ty, tz, c, nsh);
+                                                                           ax, ay, az, tx, ty, tz, c);
                 if (g3) n3b_pair<VARIANT, GUARD, false, true, CUT, POT, 3>(false, g3, l, sx, sy, sz, mi, pj, mj,
-                                                                           ax, ay, az, tx, ty, tz, c, nsh);
+                                                                           ax, ay, az, tx, ty, tz, c);
                 if (g2) n3b_pair<VARIANT, GUARD, false, true, CUT, POT, 2>(false, g2, l, sx, sy, sz, mi, pj, mj,
-                                                                           ax, ay, az, tx, ty, tz, c, nsh);
-                if (MDQT_EXP_TAB && g1)
-                    n3b_pair<VARIANT, GUARD, false, true, CUT, POT, MDQT_EXP_TAB ? 1 : 0>(
-                        false, g1, l, sx, sy, sz, mi, pj, mj, ax, ay, az, tx, ty, tz, c, nsh);
+                                                                           ax, ay, az, tx, ty, tz, c);
+                if (g1) n3b_pair<VARIANT, GUARD, false, true, CUT, POT, 1>(false, g1, l, sx, sy, sz, mi, pj, mj,
+                                                                           ax, ay, az, tx, ty, tz, c);
                 if (g0) n3b_pair<VARIANT, GUARD, false, true, CUT, POT>(false, g0, l, sx, sy, sz, mi, pj, mj, ax,
-                                                                        ay, az, tx, ty, tz, c, nsh);
-#if !defined(MDQT_EXPT_UFAR_SKIP)                   // last: nothing after it keeps sx, nsh live (diagnostic build: skip it, wrong results)
+                                                                        ay, az, tx, ty, tz, c);
+                // last: nothing after it keeps sx live
                 if (g5) n3b_pair_uf32<POT>(g5, l, (float)(sx - pj[0][0]), (float)(sy - pj[1][0]),
                                            (float)(sz - pj[2][0]), pj32, ax, ay, az, tx, ty, tz, cf32,
                                            invl32, rc2f);
-#endif
             }
         } else {
             n3b_pair<VARIANT, GUARD, false, VARIANT == 1, CUT, POT>(diag, groups, l, sx, sy, sz, mi, pj, mj,
-                                                                    ax, ay, az, tx, ty, tz, c, nsh);
+                                                                    ax, ay, az, tx, ty, tz, c);
         }
     } else if constexpr (FARF) {       // per-pair image
         const int ax1 = (tw >> 28) & 3;  // 1 + the one axis whose image varies (n3b_pack_class)
@@ -706,7 +632,7 @@ __device__ __forceinline__ void n3b_tile_pair(const N3BArgs& a, const PairC& c, 
             const double sx = fma(-(double)((tw << 20) >> 24), a.L, xi);   // (0 on the varying axis:
             const double sy = fma(-(double)((tw << 12) >> 24), a.L, yi);   //  fma(-0, L, x) = x)
             const double sz = fma(-(double)((tw << 4) >> 24), a.L, zi);
-            constexpr unsigned LV = MDQT_N3B_AX1_LEVELS;   // the levels that take it (bit x: level x)
+            constexpr unsigned LV = kAx1Levels;             // the levels that take it (bit x: level x)
             // (levels 4 and 5 in the f64 ultra-far form with the one-axis image — the f32 form needs a
             // uniform image; without LV bit 4 they ride in the very-far form)
             const unsigned g45 = level_groups(word, 4) | level_groups(word, 5);
@@ -723,9 +649,9 @@ __device__ __forceinline__ void n3b_tile_pair(const N3BArgs& a, const PairC& c, 
                 if ((LV & 4u) && g2)
                     n3b_pair<VARIANT, GUARD, false, false, CUT, POT, 2, AX>(false, g2, l, sx, sy, sz, mi, pj, mj,
                                                                             ax, ay, az, tx, ty, tz, c);
-                if ((LV & 2u) && MDQT_EXP_TAB && g1)
-                    n3b_pair<VARIANT, GUARD, false, false, CUT, POT, MDQT_EXP_TAB ? 1 : 0, AX>(
-                        false, g1, l, sx, sy, sz, mi, pj, mj, ax, ay, az, tx, ty, tz, c);
+                if ((LV & 2u) && g1)
+                    n3b_pair<VARIANT, GUARD, false, false, CUT, POT, 1, AX>(false, g1, l, sx, sy, sz, mi, pj, mj,
+                                                                            ax, ay, az, tx, ty, tz, c);
             };
             if (ax1 == 1) one_axis(std::integral_constant<int, 0>{});
             else if (ax1 == 2) one_axis(std::integral_constant<int, 1>{});
@@ -738,9 +664,9 @@ __device__ __forceinline__ void n3b_tile_pair(const N3BArgs& a, const PairC& c, 
             if (!(LV & 4u) && g2)
                 n3b_pair<VARIANT, GUARD, false, false, CUT, POT, 2>(false, g2, l, xi, yi, zi, mi, pj, mj, ax, ay,
                                                                     az, tx, ty, tz, c);
-            if (!(LV & 2u) && MDQT_EXP_TAB && g1)
-                n3b_pair<VARIANT, GUARD, false, false, CUT, POT, MDQT_EXP_TAB ? 1 : 0>(
-                    false, g1, l, xi, yi, zi, mi, pj, mj, ax, ay, az, tx, ty, tz, c);
+            if (!(LV & 2u) && g1)
+                n3b_pair<VARIANT, GUARD, false, false, CUT, POT, 1>(false, g1, l, xi, yi, zi, mi, pj, mj, ax, ay,
+                                                                    az, tx, ty, tz, c);
             if (g0) n3b_pair<VARIANT, GUARD, false, false, CUT, POT>(false, g0, l, xi, yi, zi, mi, pj, mj, ax,
                                                                      ay, az, tx, ty, tz, c);
           }
@@ -751,9 +677,8 @@ __device__ __forceinline__ void n3b_tile_pair(const N3BArgs& a, const PairC& c, 
                                                                         ay, az, tx, ty, tz, c);
             if (g2) n3b_pair<VARIANT, GUARD, false, false, CUT, POT, 2>(false, g2, l, xi, yi, zi, mi, pj, mj, ax,
                                                                         ay, az, tx, ty, tz, c);
-            if (MDQT_EXP_TAB && g1)
-                n3b_pair<VARIANT, GUARD, false, false, CUT, POT, MDQT_EXP_TAB ? 1 : 0>(false, g1, l, xi, yi, zi, mi,
-                                                                                   pj, mj, ax, ay, az, tx, ty, tz, c);
+            if (g1) n3b_pair<VARIANT, GUARD, false, false, CUT, POT, 1>(false, g1, l, xi, yi, zi, mi, pj, mj, ax,
+                                                                        ay, az, tx, ty, tz, c);
             if (g0) n3b_pair<VARIANT, GUARD, false, false, CUT, POT>(false, g0, l, xi, yi, zi, mi, pj, mj, ax, ay,
                                                                      az, tx, ty, tz, c);
         }
@@ -764,56 +689,37 @@ __device__ __forceinline__ void n3b_tile_pair(const N3BArgs& a, const PairC& c, 
 
 // POT: Epotential's pair potential (component 0 of the slots, both rows +u) instead of the force
 // the fast variant fits 80 VGPRs (6 waves per SIMD: three 8-wave workgroups per CU); the exact one (libm exp, divisions) gets 128
-#ifndef MDQT_N3B_IRUN_LDS
-#define MDQT_N3B_IRUN_LDS 1                         // the run's i accumulator in LDS (0: in the i-slot itself)
-#endif
-#ifndef MDQT_N3B_WPE                                // waves per SIMD of the fast variant (VGPR budget 512/WPE):
-#define MDQT_N3B_WPE (BW == 8 ? 6 : 8)              // 6 = three 8-wave workgroups per CU (41.5 KB LDS each)
-#endif
-// double-buffered J staging by LDS-DMA (plan path), one step ahead.  Measured (round 5, force-call A/B,
-// 2 alternations, tools/gpu/r05_ab.sh): slower than the synchronous staging — C3 6.585 vs 6.54 ms, C5
-// 31.93 vs 31.73, N = 1M 205.1 vs 203.0: the J-step barrier wait is the waves' unequal pair work, not
-// the staging load.  Off by default, kept as an option
-#ifndef MDQT_N3B_DBUF
-#define MDQT_N3B_DBUF 0
-#endif
-static_assert(!(MDQT_N3B_DBUF && MDQT_UFAR32), "the double-buffered staging has no f32 J copy: build it with MDQT_UFAR32 0");
+// waves per SIMD of the fast variant (VGPR budget 512 / 6): three 8-wave workgroups per CU (41.5 KB LDS each)
+constexpr int kN3BWpe = 6;
+static_assert(BW == 8, "kN3BWpe: three 8-wave workgroups per CU");
 // the block kernel's LDS, one object (k_pairs_n3b)
-constexpr int kN3BStageBufs = MDQT_N3B_DBUF ? 2 : 1;
 template <int W>
 struct N3BShared {
-    double pj[kN3BStageBufs][3][128];               // J positions by sub-tiles twice over (n3b_lds), per buffer
+    double pj[3][128];                              // J positions by sub-tiles twice over (n3b_lds)
     float pj32[3][128];                             // the same, fl32(xj - c_J), c_J = J's first ion (the f32 ultra-far form)
     double accj[W][3][128];                         // per-wave j accumulators
     double mjs[2][128];                             // J validity weights: all ones / the ragged last tile's
-    double etab[64];                                // 2^(k/64) (MDQT_EXP_TAB)
-#if MDQT_N3B_IRUN_LDS
+    double etab[64];                                // 2^(k/64)
     double irun[W][3][64];                          // the run's i accumulators
-#endif
-    uint2 pw[kN3BStageBufs][W];                     // plan words (class, sub-tile groups), per buffer
+    uint2 pw[W];                                    // plan words (class, sub-tile groups)
 };
 // AXP: the one-axis per-pair image (n3b_pack_class bits 28-29) in an instance of its own, launched
 // only where such tile pairs can lie inside the skip radius (launch_forces_n3b): compiled into the
 // one instance it cost the calls without any (N = 1M) 0.5 %.
 template <int VARIANT, bool GUARD, bool POT = false, bool AXP = false>
-__global__ __launch_bounds__(BW * 64) __attribute__((amdgpu_waves_per_eu(VARIANT == 1 ? MDQT_N3B_WPE : 4, VARIANT == 1 ? MDQT_N3B_WPE : 4)))
+__global__ __launch_bounds__(BW * 64) __attribute__((amdgpu_waves_per_eu(VARIANT == 1 ? kN3BWpe : 4, VARIANT == 1 ? kN3BWpe : 4)))
 void k_pairs_n3b(N3BArgs a) {
-    // all LDS in one object: beside an LDS-DMA (the plan path's J staging) a second __shared__ object
-    // can make the compiler wait for the DMA before unrelated LDS reads (cdna_hip_programming.md §5)
-    __shared__ N3BShared<BW> sh;
+    __shared__ N3BShared<BW> sh;                    // all LDS in one object
     double* const etab = sh.etab;
     stage_exp_tab(etab);
     const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;   // q: wave-uniform
-    const int l0 = l;                               // (lane_opaque's fallback)
-#ifndef MDQT_N3B_ORDER
-#define MDQT_N3B_ORDER 1
-#endif
-    // workgroup order: run-major (MDQT_N3B_ORDER 1) dispatches every block's first run — the near
-    // block distances, the heaviest work — first and the far, mostly skipped runs last, so the
-    // kernel's last round is short; 0: block-major (round 3)
+    const int l0 = l;
+    // workgroup order: run-major dispatches every block's first run — the near block distances, the
+    // heaviest work — first and the far, mostly skipped runs last, so the kernel's last round is short
+    // (round 3 was block-major)
     const int nP = a.Phi - a.Plo;
-    const int P = a.Plo + (MDQT_N3B_ORDER ? (int)blockIdx.x % nP : (int)blockIdx.x / a.R);
-    const int run = MDQT_N3B_ORDER ? (int)blockIdx.x / nP : (int)blockIdx.x % a.R;
+    const int P = a.Plo + (int)blockIdx.x % nP;
+    const int run = (int)blockIdx.x / nP;
     const int d0 = run * a.runlen, d1 = min(a.nd, d0 + a.runlen);
     const PairC c = {a.L, a.micT, a.micGuard, a.Rcut, a.lDeb, a.invlDeb, 1. / a.L, a.rc2, etab};
     const int T = a.T, N = a.N, S = a.S;
@@ -832,8 +738,7 @@ void k_pairs_n3b(N3BArgs a) {
         xi = p[0]; yi = p[PS]; zi = p[2 * PS]; mi = 1.;
     }
     // waited for here, once: as load results the compiler waited vmcnt(0) for them at every pair-form
-    // dispatch (it cannot count past the staging wave's LDS-DMA on the loop's back edge), which retired
-    // the DMA just issued instead of letting it land during the pair work
+    // dispatch
     asm volatile("" : "+v"(xi), "+v"(yi), "+v"(zi));
     // Tile-pair classes in spatial order (SpeedUp:222 keeps a pair only below r = L/2), decided
     // for all BW waves' tile pairs (I, J) by the staging wave's lanes 0..BW-1:
@@ -849,7 +754,7 @@ void k_pairs_n3b(N3BArgs a) {
     // The forces take them, with the sub-tile groups (tg[q]), from the call's plan (k_n3b_plan: one
     // 8-byte word per tile pair, loaded by lanes 0..15); without a plan (potentials, unsorted order)
     // the staging lanes classify the tile pairs themselves and every group runs in the exact form.
-    constexpr bool CUT = VARIANT == 1 && MDQT_N3_CUT;
+    constexpr bool CUT = VARIANT == 1;
     constexpr bool FARF = VARIANT == 1 && !GUARD && CUT;   // the error-bounded pair forms (potentials: on a plan)
     const N3BRadii rad = n3b_radii<VARIANT, POT>(a);
     // the f32 form's constants as wave-uniform SGPR values (in VGPRs they were spilled and reloaded
@@ -858,15 +763,9 @@ void k_pairs_n3b(N3BArgs a) {
     const float cf32 = sgpr_f((float)(a.invlDeb * kNegLog2e)), invl32 = sgpr_f((float)a.invlDeb),
                 rc2f = sgpr_f((float)a.rc2);
     // the run's i accumulator: in LDS (read and written once per block distance, so that the
-    // three-level blocking fits the 64-VGPR budget), or (MDQT_N3B_IRUN_LDS 0) the i-slot itself —
-    // each wave's own rows, read, added and written once per block distance, in order
-#if MDQT_N3B_IRUN_LDS
+    // three-level blocking fits the 64-VGPR budget)
     auto fiptr = [&]() { return sh.irun[q][0] + lane_opaque(l0); };
     constexpr size_t FS = 64;
-#else
-    auto fiptr = [&]() { return a.slots + (size_t)(a.nd + run) * ((size_t)3 * a.Npad) + I * 64 + lane_opaque(l0); };
-    const size_t FS = a.Npad;
-#endif
     bool fi_first = true;
     const uint2* plan = a.plan;                     // (potentials: the plan of launch_potential_n3b, or none)
     // every J step: the staging wave (the last; not one of the combining waves 0..2) loads J, one
@@ -892,45 +791,6 @@ void k_pairs_n3b(N3BArgs a) {
     // the plan's J-step masks (after its tile-pair words): bit b = some tile pair of J step b has work
     const unsigned* jsteps = plan ? (const unsigned*)(plan + (size_t)(a.Phi - a.Plo) * a.nd * (BW * BW)) : nullptr;
     auto half_db = [&](int db) { return !(a.NB & 1) && db == a.NB / 2 && P >= a.NB / 2; };   // the other half covers it
-    // Double-buffered J staging (MDQT_N3B_DBUF, the plan path): at the top of every J step with work the
-    // staging wave issues the LDS-DMA loads (global_load_lds_dwordx4: J's positions by sub-tiles twice
-    // over, and the step's 8 plan words) of the NEXT step with work into the other buffer, then all waves
-    // compute on this one; the DMA lands during the pair work and is retired by the staging wave's wait
-    // at the step's second barrier.  The first barrier is a raw s_barrier after lgkmcnt(0) (the
-    // combine's zeroing), so the DMA in flight is not drained there.  Without a plan (potentials,
-    // unsorted order) the staging wave loads and classifies J itself before the first barrier.
-    // Rs holds the pad ions' values (k_gather_sorted), so the DMA copies what the register path computes.
-    constexpr bool kDbuf = MDQT_N3B_DBUF != 0;
-    int buf = 0;
-    auto next_step = [&](int db, int b, int& odb, int& ob) {   // the first step with work at or after (db, b)
-        for (; db < d1; ++db, b = 0) {
-            if (half_db(db)) continue;
-            const unsigned msk = jsteps[2 * ((size_t)(P - a.Plo) * a.nd + db)];
-            const int Qn = (P + db) % a.NB;
-            for (; b < BW && Qn * BW + b < T; ++b)
-                if ((msk >> b) & 1u) { odb = db; ob = b; return; }
-        }
-        odb = d1; ob = 0;
-    };
-    auto dma_stage = [&](int bf, int db, int b) {   // (staging wave) J step (db, b) into buffer bf
-        const int J = ((P + db) % a.NB) * BW + b;
-        const int l = lane_opaque(l0);
-        const double* src = a.Rs + (size_t)J * 64 + 16 * (l >> 4) + ((2 * l) & 15);
-        // lanes 0 .. BW/2 - 1: the step's BW plan words, 16 bytes each (an LDS-DMA writes base + 16 x lane
-        // for every active lane, so only those lanes issue it)
-        const uint2* pws = plan + ((size_t)(P - a.Plo) * a.nd + db) * (BW * BW) + b * BW + 2 * (l & (BW / 2 - 1));
-        // every address formed before the first DMA: a spill reload between them would be waited for
-        // with vmcnt(0), retiring the DMA already issued
-        asm volatile("" : "+v"(src), "+v"(pws));
-        if (l < BW / 2) lds_dma16(pws, lds_offset(&sh.pw[bf][0]));
-#pragma unroll
-        for (int c3 = 0; c3 < 3; ++c3) lds_dma16(src + (size_t)c3 * a.Npad, lds_offset(&sh.pj[bf][c3][0]));
-    };
-    if (kDbuf && plan && q == kStage) {             // the launch's first step with work into buffer 0
-        int fdb, fb;
-        next_step(d0, 0, fdb, fb);
-        if (fdb < d1) dma_stage(0, fdb, fb);
-    }
     for (int db = d0; db < d1; ++db) {
         if (half_db(db)) continue;
         const int Q = (P + db) % a.NB;
@@ -946,64 +806,46 @@ void k_pairs_n3b(N3BArgs a) {
                     a.slots[(size_t)db * plane + (size_t)q * a.Npad + J * 64 + lane_opaque(l0)] = POT ? 0. : -0.;
                 continue;                           // the reduction's masks: nothing, the slot is not read)
             }
-            if (kDbuf && plan) {
-                if (q == kStage) {                  // the next step with work into the other buffer
-                    int ndb, nb;
-                    next_step(db, b + 1, ndb, nb);
-                    // this buffer's DMA was retired at the previous step's second barrier, or (the first
-                    // step) it is retired here: everything but the 4 DMA loads just issued
-                    if (ndb < d1) {
-                        dma_stage(buf ^ (kN3BStageBufs - 1), ndb, nb);
-                        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            if (q == kStage) {                  // stage J (by sub-tiles, twice over)
+                const int j = J * 64 + l;
+                const bool vj = j < N;
+                const double* p = tile_ptr(J) + l;
+                const double xj = vj ? p[0] : pad, yj = vj ? p[PS] : pad, zj = vj ? p[2 * PS] : pad;
+                const int li = n3b_lds(l);
+                sh.pj[0][li] = xj; sh.pj[0][li + 16] = xj;
+                sh.pj[1][li] = yj; sh.pj[1][li + 16] = yj;
+                sh.pj[2][li] = zj; sh.pj[2][li + 16] = zj;
+                if constexpr (FARF) {           // relative to c_J = J's first ion (pj[.][0])
+                    const float x32 = (float)(xj - uniform_f64(xj)), y32 = (float)(yj - uniform_f64(yj)),
+                                z32 = (float)(zj - uniform_f64(zj));
+                    sh.pj32[0][li] = x32; sh.pj32[0][li + 16] = x32;
+                    sh.pj32[1][li] = y32; sh.pj32[1][li + 16] = y32;
+                    sh.pj32[2][li] = z32; sh.pj32[2][li + 16] = z32;
+                }
+                if (l < BW) {
+                    if (plan) {                 // (P, db, b): one word per wave
+                        sh.pw[l] = plan[((size_t)(P - a.Plo) * a.nd + db) * (BW * BW) + b * BW + l];
                     } else {
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    }
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            } else {
-                if (q == kStage) {                  // stage J (by sub-tiles, twice over)
-                    const int j = J * 64 + l;
-                    const bool vj = j < N;
-                    const double* p = tile_ptr(J) + l;
-                    const double xj = vj ? p[0] : pad, yj = vj ? p[PS] : pad, zj = vj ? p[2 * PS] : pad;
-                    const int li = n3b_lds(l);
-                    sh.pj[buf][0][li] = xj; sh.pj[buf][0][li + 16] = xj;
-                    sh.pj[buf][1][li] = yj; sh.pj[buf][1][li + 16] = yj;
-                    sh.pj[buf][2][li] = zj; sh.pj[buf][2][li + 16] = zj;
-                    if constexpr (FARF && MDQT_UFAR32) {   // relative to c_J = J's first ion (pj[.][0])
-                        const float x32 = (float)(xj - uniform_f64(xj)), y32 = (float)(yj - uniform_f64(yj)),
-                                    z32 = (float)(zj - uniform_f64(zj));
-                        sh.pj32[0][li] = x32; sh.pj32[0][li + 16] = x32;
-                        sh.pj32[1][li] = y32; sh.pj32[1][li + 16] = y32;
-                        sh.pj32[2][li] = z32; sh.pj32[2][li + 16] = z32;
-                    }
-                    if (l < BW) {
-                        if (plan) {                 // (P, db, b): one word per wave
-                            sh.pw[buf][l] = plan[((size_t)(P - a.Plo) * a.nd + db) * (BW * BW) + b * BW + l];
-                        } else {
-                            int w = 2;              // class 0 (unsorted: every tile pair, per-pair image)
-                            if (srt && P * BW + l < T) {
-                                double g2;
-                                int sm = 0;
-                                w = n3b_pack_class(n3b_classify<VARIANT == 1>(a, c.invL, rad, P * BW + l, J, g2,
-                                                                              AXP ? &sm : nullptr), sm);
-                            }
-                            sh.pw[buf][l] = make_uint2((unsigned)w, 0xFFu);
+                        int w = 2;              // class 0 (unsorted: every tile pair, per-pair image)
+                        if (srt && P * BW + l < T) {
+                            double g2;
+                            int sm = 0;
+                            w = n3b_pack_class(n3b_classify<VARIANT == 1>(a, c.invL, rad, P * BW + l, J, g2,
+                                                                          AXP ? &sm : nullptr), sm);
                         }
+                        sh.pw[l] = make_uint2((unsigned)w, 0xFFu);
                     }
                 }
-#if !defined(MDQT_EXPT_NOBAR)                       // (diagnostic build: no J-step barriers, wrong results)
-                __syncthreads();
-#endif
             }
-            const double (*pj)[128] = sh.pj[buf];
+            __syncthreads();
+            const double (*pj)[128] = sh.pj;
             const double* mj = sh.mjs[J == T - 1];
-            const int tw = __builtin_amdgcn_readfirstlane((int)sh.pw[buf][q].x);
+            const int tw = __builtin_amdgcn_readfirstlane((int)sh.pw[q].x);
             const int cls = (tw & 15) - 2;
             const bool mine = vI && (db > 0 || J >= I);
             const bool diag = (db == 0 && J == I);
             // this wave's sub-tile groups, by pair form (k_n3b_plan)
-            const unsigned word = __builtin_amdgcn_readfirstlane(sh.pw[buf][q].y);
+            const unsigned word = __builtin_amdgcn_readfirstlane(sh.pw[q].y);
             const unsigned groups = word & 15u;
             if (mine && cls >= 0 && groups) {
                 // blocked i accumulation: the tile pair's steps into a fresh sum, those into the
@@ -1016,11 +858,7 @@ void k_pairs_n3b(N3BArgs a) {
                                                         rc2f);
                 bx += tx; by += ty; bz += tz;
             }
-            if (kDbuf && plan && q == kStage) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA retired
-#if !defined(MDQT_EXPT_NOBAR)
             __syncthreads();
-#endif
-            if (kDbuf && plan) buf ^= kN3BStageBufs - 1;
             if (q < (POT ? 1 : 3)) {                // j side of J's rows -> j-slot db
                 const int l = lane_opaque(l0);
                 const int li = n3b_lds(l);
@@ -1052,7 +890,7 @@ void k_pairs_n3b(N3BArgs a) {
         double* fi = fiptr();
         double* o = a.slots + (size_t)(a.nd + run) * plane + I * 64 + lane_opaque(l0);
         const double r0 = fi_first ? 0. : fi[0], r1 = fi_first ? 0. : fi[FS], r2 = fi_first ? 0. : fi[2 * FS];
-        if (MDQT_N3B_IRUN_LDS || fi_first) { o[0] = r0; o[a.Npad] = r1; o[2 * (size_t)a.Npad] = r2; }
+        o[0] = r0; o[a.Npad] = r1; o[2 * (size_t)a.Npad] = r2;
     }
 }
 
@@ -1066,17 +904,8 @@ __constant__ const unsigned kN3BMatchings[105] = {0xfac688, 0xf74688, 0xd7c688, 
 // a sub-tile group's estimated VALU instructions per lane (16 steps; the pairing's weights per wave-step of
 // each pair form — exact, mid, far, very far, ultra far, f32 ultra far — uniform image / per-pair image; the
 // ragged tile's exact form)
-#ifndef MDQT_N3B_PAIR_COST
-#define MDQT_N3B_PAIR_COST 0
-#endif
 __device__ __forceinline__ unsigned n3b_pair_cost(int level, bool uni, bool rag) {
-#if MDQT_N3B_PAIR_COST
-    // (round 6 A/B) issue slots per step from the forms' instruction costs (profiles/r06f_ubench_forms.txt:
-    // v_rsq_f64 ~3.3 slots, f32 transcendentals ~2.4, plain f32 0.5)
-    constexpr unsigned wu[6] = {43u, 41u, 38u, 33u, 28u, 18u}, wi[6] = {50u, 47u, 44u, 38u, 31u, 31u};
-#else
     constexpr unsigned wu[6] = {39u, 36u, 31u, 27u, 25u, 9u}, wi[6] = {48u, 44u, 38u, 32u, 32u, 32u};
-#endif
     return 16u * (rag ? 52u : uni ? wu[level] : wi[level]);
 }
 
@@ -1100,15 +929,13 @@ struct N3BSharedPW {
     float pj32[3][128];                             // fl32(xj - c_J) (the f32 ultra-far form)
     double accj[W][3][128];                         // per-wave j accumulators
     double mjs[2][128];                             // J validity weights: all ones / the ragged last tile's
-    double etab[64];                                // 2^(k/64) (MDQT_EXP_TAB)
+    double etab[64];                                // 2^(k/64)
     double irun[BW][3][64];                         // the run's i sums, per I tile of the block
     uint2 pw[BW];                                   // the J step's plan words, per I tile
 };
-#ifndef MDQT_N3B_PW_WPE
-#define MDQT_N3B_PW_WPE 5                           // waves per SIMD: five 4-wave workgroups per CU (LDS 31 KB)
-#endif
+constexpr int kN3BPwWpe = 5;                        // waves per SIMD: five 4-wave workgroups per CU (LDS 31 KB)
 template <int VARIANT, bool GUARD, bool POT = false, bool AXP = false>
-__global__ __launch_bounds__(NWP * 64) __attribute__((amdgpu_waves_per_eu(VARIANT == 1 ? MDQT_N3B_PW_WPE : 4, VARIANT == 1 ? MDQT_N3B_PW_WPE : 4)))
+__global__ __launch_bounds__(NWP * 64) __attribute__((amdgpu_waves_per_eu(VARIANT == 1 ? kN3BPwWpe : 4, VARIANT == 1 ? kN3BPwWpe : 4)))
 void k_pairs_n3b_pw(N3BArgs a) {
     __shared__ N3BSharedPW<NWP> sh;
     double* const etab = sh.etab;
@@ -1116,8 +943,8 @@ void k_pairs_n3b_pw(N3BArgs a) {
     const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;   // q: wave-uniform
     const int l0 = l;
     const int nP = a.Phi - a.Plo;
-    const int P = a.Plo + (MDQT_N3B_ORDER ? (int)blockIdx.x % nP : (int)blockIdx.x / a.R);
-    const int run = MDQT_N3B_ORDER ? (int)blockIdx.x / nP : (int)blockIdx.x % a.R;
+    const int P = a.Plo + (int)blockIdx.x % nP;     // run-major (k_pairs_n3b)
+    const int run = (int)blockIdx.x / nP;
     const int d0 = run * a.runlen, d1 = min(a.nd, d0 + a.runlen);
     const PairC c = {a.L, a.micT, a.micGuard, a.Rcut, a.lDeb, a.invlDeb, 1. / a.L, a.rc2, etab};
     const int T = a.T, N = a.N, S = a.S;
@@ -1126,7 +953,7 @@ void k_pairs_n3b_pw(N3BArgs a) {
     const int PS = srt ? a.Npad : S;
     auto tile_ptr = [&](int tile) { return srt ? a.Rs + tile * 64 : tile_base(a.Rall, tile, S); };
     const double pad = (double)(l + 1) * 0x1p-10;  // pad ions: distinct points (pair_ft_cut: r > 0)
-    constexpr bool FARF = VARIANT == 1 && !GUARD && VARIANT == 1 && MDQT_N3_CUT;
+    constexpr bool FARF = VARIANT == 1 && !GUARD;
     const N3BRadii rad = n3b_radii<VARIANT, POT>(a);
     auto sgpr_f = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
     const float cf32 = sgpr_f((float)(a.invlDeb * kNegLog2e)), invl32 = sgpr_f((float)a.invlDeb),
@@ -1189,7 +1016,7 @@ void k_pairs_n3b_pw(N3BArgs a) {
                 sh.pj[0][li] = xj; sh.pj[0][li + 16] = xj;
                 sh.pj[1][li] = yj; sh.pj[1][li + 16] = yj;
                 sh.pj[2][li] = zj; sh.pj[2][li + 16] = zj;
-                if constexpr (FARF && MDQT_UFAR32) {
+                if constexpr (FARF) {
                     const float x32 = (float)(xj - uniform_f64(xj)), y32 = (float)(yj - uniform_f64(yj)),
                                 z32 = (float)(zj - uniform_f64(zj));
                     sh.pj32[0][li] = x32; sh.pj32[0][li + 16] = x32;
@@ -1211,9 +1038,7 @@ void k_pairs_n3b_pw(N3BArgs a) {
                     }
                 }
             }
-#if !defined(MDQT_EXPT_NOBAR)                       // (diagnostic build: no J-step barriers, wrong results)
             __syncthreads();
-#endif
             const double (*pj)[128] = sh.pj;
             const double* mj = sh.mjs[J == T - 1];
 #pragma unroll 1
@@ -1233,9 +1058,7 @@ void k_pairs_n3b_pw(N3BArgs a) {
                     else { bxA += tx; byA += ty; bzA += tz; }
                 }
             }
-#if !defined(MDQT_EXPT_NOBAR)
             __syncthreads();
-#endif
             if (q < (POT ? 1 : 3)) {                // j side of J's rows -> j-slot db: the 4 waves' two copies
                 const int l = lane_opaque(l0);
                 const int li = n3b_lds(l);
@@ -1449,7 +1272,7 @@ __global__ __launch_bounds__(256) void k_n3b_census(N3BArgs a, unsigned long lon
         const double4 t4 = n3b_classify<true>(a, 1. / a.L, rad, I, J, g2, &sm);
         const bool diag = db == 0 && J == I;
         // (a per-pair image on one axis, AXP instance: levels 4 and 5 in the f64 ultra-far form, class 14)
-        constexpr bool AX1U = MDQT_N3B_AX1 != 0 && (MDQT_N3B_AX1_LEVELS & 16u) != 0;
+        constexpr bool AX1U = (kAx1Levels & 16u) != 0;
         const bool ax1p = AX1U && n3b_axp(a) && ((n3b_pack_class(t4, sm) >> 28) & 3);
         const double nI = (double)min(64, a.N - I * 64), nJ = (double)min(64, a.N - J * 64);
         const bool rag = (a.N & 63) && (I == a.T - 1 || J == a.T - 1);
@@ -1617,22 +1440,13 @@ __global__ __launch_bounds__(256) void k_n3b_census(N3BArgs a, unsigned long lon
 // the plan kernel's occupancy (round 6, A/B r06p_plan_ab.txt, bit-identical): 3 waves per SIMD (168 VGPRs,
 // 2 spilled) with the LDS boxes: plan stage N = 1M 9.4 -> 7.8 ms, C5 0.75 -> 0.58 ms; 4 (128 VGPRs, 37
 // spilled) is slower than 2
-#ifndef MDQT_PLAN_WPE
-#define MDQT_PLAN_WPE 3
-#endif
-#ifndef MDQT_PLAN_LDS
-#define MDQT_PLAN_LDS 1
-#endif
-#ifndef MDQT_EXPT_PLAN
-#define MDQT_EXPT_PLAN 0                            // diagnostic builds only (wrong plans): bit 0 no tail terms, 1 no pairing sort,
-                                                    // 2 no sub-tile work
-#endif
+constexpr int kPlanWpe = 3;
 template <int VARIANT, bool GUARD>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MDQT_PLAN_WPE)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kPlanWpe)))
 void k_n3b_plan(N3BArgs a, uint2* __restrict__ plan) {
     __shared__ double ti[BW][4], tj[BW][4];
     __shared__ unsigned jm;
-    constexpr bool FARF = VARIANT == 1 && !GUARD && MDQT_N3_CUT;
+    constexpr bool FARF = VARIANT == 1 && !GUARD;
     const int t = threadIdx.x, q = t & (BW - 1), b = t / BW;
     const int Pl = (int)blockIdx.x / a.nd, db = (int)blockIdx.x % a.nd;
     const int P = a.Plo + Pl, Q = (P + db) % a.NB;
@@ -1640,11 +1454,11 @@ void k_n3b_plan(N3BArgs a, uint2* __restrict__ plan) {
     const bool tmeas = a.tailb != nullptr;
     if (tmeas && t < 4 * BW) { ti[t >> 2][t & 3] = 0.; tj[t >> 2][t & 3] = 0.; }
     if (t == 0) jm = 0u;
-    // the workgroup's boxes in LDS (MDQT_PLAN_LDS): the BW I tiles' and BW J tiles' [12] box columns and
+    // the workgroup's boxes in LDS: the BW I tiles' and BW J tiles' [12] box columns and
     // their 4 BW sub-tiles' [6] — each read once, coalesced, instead of per tile pair from L2 (the kernel's
     // ~190 global loads held ~200 VGPRs: 2 waves per SIMD); the same values, the same operations
     __shared__ double bI[12][BW], bJ[12][BW], sI[6][4 * BW], sJ[6][4 * BW];
-    if constexpr (MDQT_PLAN_LDS) {
+    {
         const int T4 = 4 * a.T;
         for (int k = t; k < 12 * BW; k += BW * BW) {
             const int row = k / BW, c = k % BW;
@@ -1659,13 +1473,16 @@ void k_n3b_plan(N3BArgs a, uint2* __restrict__ plan) {
             }
     }
     __syncthreads();
-    // box column accessors: LDS (row stride BW / 4 BW) or global ([12][T] / [6][4T])
-    const double* const Bi = MDQT_PLAN_LDS ? &bI[0][q] : a.boxes + I;
-    const double* const Bj = MDQT_PLAN_LDS ? &bJ[0][b] : a.boxes + J;
-    const int bld = MDQT_PLAN_LDS ? BW : a.T;
-    auto SBi = [&](int sa) -> const double* { return MDQT_PLAN_LDS ? &sI[0][4 * q + sa] : a.subboxes + 4 * I + sa; };
-    auto SBj = [&](int sb) -> const double* { return MDQT_PLAN_LDS ? &sJ[0][4 * b + sb] : a.subboxes + 4 * J + sb; };
-    const int sld = MDQT_PLAN_LDS ? 4 * BW : 4 * a.T;
+    // box column accessors into LDS (row stride BW / 4 BW)
+    const double* const Bi = &bI[0][q];
+    const double* const Bj = &bJ[0][b];
+    constexpr int bld = BW;
+    // (the closures also hold I and J by reference, as they did while the accessors had a global-memory
+    // form: the kernel's register allocation — 168 VGPRs, 2 spilled, above — was tuned with them, and the
+    // compiler schedules the kernel differently without)
+    auto SBi = [&](int sa) -> const double* { (void)I; return &sI[0][4 * q + sa]; };
+    auto SBj = [&](int sb) -> const double* { (void)J; return &sJ[0][4 * b + sb]; };
+    constexpr int sld = 4 * BW;
     uint2 w = make_uint2(1u, 0xFFu);                // class -1 where the block kernel never looks
     double gi[4] = {0., 0., 0., 0.}, gj[4] = {0., 0., 0., 0.};   // this tile pair's tail terms per sub-tile
     const bool half = !(a.NB & 1) && db == a.NB / 2 && P >= a.NB / 2;
@@ -1684,7 +1501,7 @@ void k_n3b_plan(N3BArgs a, uint2* __restrict__ plan) {
         const bool rag = (a.N & 63) && (I == a.T - 1 || J == a.T - 1);
         const bool uni = cls >= 0 && (cls & 1);
         if (db == 0 && J == I && !(g2 > rad.rc2)) cest = (rag ? 52u : uni ? 39u : 48u) * 40u;
-        if ((db > 0 || J > I) && (cls >= 0 || (tmeas && cls == -2)) && !(MDQT_EXPT_PLAN & 4)) {   // (bit 2: timing only)
+        if ((db > 0 || J > I) && (cls >= 0 || (tmeas && cls == -2))) {
             double sg[4][4];
 #pragma unroll
             for (int sa = 0; sa < 4; ++sa)
@@ -1723,10 +1540,10 @@ void k_n3b_plan(N3BArgs a, uint2* __restrict__ plan) {
                 }
             }
             if (cls >= 0) w.y = groups | (lvm << 4);
-            if (tmeas && !(MDQT_EXPT_PLAN & 1)) {        // (EXPT_PLAN bit 0: timing only)
+            if (tmeas) {
                 const double rcut2 = a.Rcut * a.Rcut;
                 const float invl = (float)a.invlDeb, cf = (float)(a.invlDeb * kNegLog2e);
-                constexpr bool AX1U = FARF && MDQT_N3B_AX1 != 0 && (MDQT_N3B_AX1_LEVELS & 16u) != 0;
+                constexpr bool AX1U = FARF && (kAx1Levels & 16u) != 0;
                 const bool ax1p = AX1U && n3b_axp(a) && ((pw >> 28) & 3);
 #pragma unroll
                 for (int sa = 0; sa < 4; ++sa)
@@ -1795,7 +1612,7 @@ void k_n3b_plan(N3BArgs a, uint2* __restrict__ plan) {
         for (int off = 1; off < BW; off <<= 1) pr |= __shfl_xor(pr, off);
     }
     __syncthreads();
-    if (t == 0 && !(MDQT_EXPT_PLAN & 2))          // (EXPT_PLAN bit 1: timing only)
+    if (t == 0)
         plan[(size_t)(a.Phi - a.Plo) * a.nd * (BW * BW) + (size_t)Pl * a.nd + db] = make_uint2(jm, pr);
     // the reduction's per-J-tile masks: J step b has work -> the block kernel writes J's j-slot db
     if (a.tmask && t < BW && ((jm >> t) & 1u))
@@ -1903,14 +1720,6 @@ hipError_t launch_reduce_segments(const double* Fpart, double* F, int nseg, int 
 hipError_t launch_forces_n3(const N3Args& a, int variant, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (a.npairs <= 0) return hipSuccess;
     dim3 grid(a.npairs);
-#if defined(MDQT_EXPT_N3LDS)
-    // diagnostic build only: extra dynamic LDS per workgroup (bytes) to cap workgroups per CU
-    if (variant == 1 && !a.guard) {
-        if (ev0) hipExtLaunchKernelGGL(k_pairs_n3<1, false>, grid, dim3(64 * N3W), MDQT_EXPT_N3LDS, s, ev0, ev1, 0, a);
-        else hipLaunchKernelGGL((k_pairs_n3<1, false>), grid, dim3(64 * N3W), MDQT_EXPT_N3LDS, s, a);
-        return hipGetLastError();
-    }
-#endif
     if (variant == 2) {
         if (a.guard) launch_timed(k_pairs_n3<2, true>, grid, dim3(64 * N3W), s, ev0, ev1, a);
         else launch_timed(k_pairs_n3<2, false>, grid, dim3(64 * N3W), s, ev0, ev1, a);
@@ -1967,12 +1776,12 @@ hipError_t launch_forces_n3b(const N3BArgs& a, int variant, double* out, hipStre
     if (marks && hipEventRecord(marks[0], s) != hipSuccess) return hipGetLastError();
     if (nblk > 0) {
         if (variant == 1 && !a.guard && a.pairs) {   // the paired-wave kernel (option force_n3b_pairs)
-            if (n3b_axp(a)) launch_timed(k_pairs_n3b_pw<1, false, false, MDQT_N3B_AX1 != 0>, dim3(nblk), dim3(NWP * 64), s, ev0, ev1, a);
+            if (n3b_axp(a)) launch_timed(k_pairs_n3b_pw<1, false, false, true>, dim3(nblk), dim3(NWP * 64), s, ev0, ev1, a);
             else launch_timed(k_pairs_n3b_pw<1, false>, dim3(nblk), dim3(NWP * 64), s, ev0, ev1, a);
         } else if (variant == 1) {
             const bool axp = n3b_axp(a);
             if (a.guard) launch_timed(k_pairs_n3b<1, true>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, a);
-            else if (axp) launch_timed(k_pairs_n3b<1, false, false, MDQT_N3B_AX1 != 0>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, a);
+            else if (axp) launch_timed(k_pairs_n3b<1, false, false, true>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, a);
             else launch_timed(k_pairs_n3b<1, false>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, a);
         } else {
             if (a.guard) launch_timed(k_pairs_n3b<0, true>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, a);
@@ -1988,29 +1797,6 @@ hipError_t launch_forces_n3b(const N3BArgs& a, int variant, double* out, hipStre
     if (marks && hipEventRecord(marks[1], s) != hipSuccess) return hipGetLastError();
     hipLaunchKernelGGL(k_n3b_reduce, dim3((a.N + 255) / 256, 3), dim3(256), 0, s, r, out);
     if (marks && hipEventRecord(marks[2], s) != hipSuccess) return hipGetLastError();
-#if defined(MDQT_EXPT_TMASK_DEBUG)
-    if (a.plan && a.tmask) {                        // diagnostic build: the masks' bit counts
-        (void)hipStreamSynchronize(s);
-        const size_t nj = (size_t)(a.Phi - a.Plo) * a.nd;
-        std::vector<uint2> js(nj);
-        std::vector<unsigned long long> tm((size_t)a.T * a.tmw);
-        (void)hipMemcpy(js.data(), a.plan + nj * (BW * BW), nj * sizeof(uint2), hipMemcpyDeviceToHost);
-        (void)hipMemcpy(tm.data(), a.tmask, tm.size() * 8, hipMemcpyDeviceToHost);
-        long cj = 0, ct = 0, miss = 0;
-        for (size_t k = 0; k < nj; ++k) cj += __builtin_popcount(js[k].x);
-        for (auto v : tm) ct += __builtin_popcountll(v);
-        for (size_t k = 0; k < nj; ++k) {
-            const int P = a.Plo + (int)(k / a.nd), db = (int)(k % a.nd), Q = (P + db) % a.NB;
-            for (int b = 0; b < BW; ++b)
-                if ((js[k].x >> b) & 1u) {
-                    const int J = Q * BW + b;
-                    if (!((tm[(size_t)J * a.tmw + (db >> 6)] >> (db & 63)) & 1ull)) ++miss;
-                }
-        }
-        fprintf(stderr, "tmask debug: jstep bits %ld, tmask bits %ld, jstep bits missing in tmask %ld (T %d tmw %d nd %d NB %d)\n",
-                cj, ct, miss, a.T, a.tmw, a.nd, a.NB);
-    }
-#endif
     return hipGetLastError();
 }
 
@@ -2058,12 +1844,12 @@ hipError_t launch_potential_n3b(const N3BArgs& a, int variant, double* out, hipS
     if (nblk > 0) {
         if (variant == 1 && !a.guard && a.pairs) {   // the paired-wave kernel (option force_n3b_pairs)
             if (planned && n3b_axp(a))
-                launch_timed(k_pairs_n3b_pw<1, false, true, MDQT_N3B_AX1 != 0>, dim3(nblk), dim3(NWP * 64), s, ev0, ev1, r);
+                launch_timed(k_pairs_n3b_pw<1, false, true, true>, dim3(nblk), dim3(NWP * 64), s, ev0, ev1, r);
             else launch_timed(k_pairs_n3b_pw<1, false, true>, dim3(nblk), dim3(NWP * 64), s, ev0, ev1, r);
         } else if (variant == 1) {
             if (a.guard) launch_timed(k_pairs_n3b<1, true, true>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, r);
             else if (planned && n3b_axp(a))
-                launch_timed(k_pairs_n3b<1, false, true, MDQT_N3B_AX1 != 0>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, r);
+                launch_timed(k_pairs_n3b<1, false, true, true>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, r);
             else launch_timed(k_pairs_n3b<1, false, true>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, r);
         } else {
             if (a.guard) launch_timed(k_pairs_n3b<0, true, true>, dim3(nblk), dim3(BW * 64), s, ev0, ev1, r);

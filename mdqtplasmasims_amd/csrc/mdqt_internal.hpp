@@ -261,9 +261,8 @@ constexpr double kFarRelErr = 3e-9;
 // kTab4RelErr of itself (mdqt_force_plan.cpp far_err, level 5).
 constexpr double kRsq1RelErr = 2.2e-14;
 // 2^t of the exact (and mid) pair forms by the 64-entry LDS table (mdqt_pairs.hpp exp2_neg_cut_tab)
-#ifndef MDQT_EXP_TAB
-#define MDQT_EXP_TAB 1   // A/B round 4 (plan-based block kernel): C3 -3.5 %, C5 -0.8 %, N = 1M +0.3 %; round 3: C2 MD step -0.2 us
-#endif
+// (A/B round 4 against the polynomial 2^t, plan-based block kernel: C3 -3.5 %, C5 -0.8 %, N = 1M +0.3 %; round 3:
+// C2 MD step -0.2 us)
 constexpr double kTab4RelErr = 4e-15;
 __device__ __forceinline__ double rsq1(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -287,7 +286,7 @@ constexpr double kExp5RelErr = 1.1e-7;
 // kExp2fRelErr of itself (kExp2fRelErr: twice what tools/exp2f_precision measures, re-checked by a
 // GPU test).  f32's range holds 2^t down to t = -126: r <= 87 lDeb, beyond every L/2 it serves.
 constexpr double kExp2fRelErr = 0x1p-22;
-// The ultra-far tier in f32 (MDQT_UFAR32, round 3; round 5: relative to J's first ion, packed): a
+// The ultra-far tier in f32 (round 3; round 5: relative to J's first ion, packed): a
 // uniform-image tile pair's sub-tile group whose sub-boxes are >= r_ufar32 apart — and whose gap g is
 // at least the J tile's raw box diagonal D (k_n3b_plan) — evaluates its pair terms in f32: the J tile
 // staged as fl32(xj - c_J), c_J its first ion, the lane's ion as fl32(xi - n L - c_J), dx their f32
@@ -306,9 +305,6 @@ constexpr double kExp2fRelErr = 0x1p-22;
 // 10^-k (C5: N g(L/2) is ~1e-8; N = 1e6 at C2's parameters: ~5e-16).  force_form_mode 1 (round 6) has
 // no such term: the plan gives a group the f32 form only if its far distance is below Rcut (1 - 2^-20)
 // (N3BArgs::u32lim2), so its f32 r^2 never decides a cutoff.
-#ifndef MDQT_UFAR32
-#define MDQT_UFAR32 1
-#endif
 constexpr double kRsqF32RelErr = 0x1p-23;
 constexpr double kUfar32A = 22. * 0x1p-24;
 constexpr double kUfar32B = 52. * 0x1p-24;
@@ -338,26 +334,6 @@ __device__ __forceinline__ double exp2_neg_cut6(double t, bool keep) {
     p = fma(p, f, 0x1.c6aecc669b6ddp-5);
     p = fma(p, f, 0x1.ebfbe045f4d3cp-3);
     p = fma(p, f, 0x1.62e430d034702p-1);
-    p = fma(p, f, 1.0);
-    return ldexp(p, keep ? (int)n : -1100);
-}
-// exp2_neg with a cutoff folded into the exponent shift: 0 (2^-1100 underflows) unless keep —
-// one 32-bit select instead of a 64-bit one on the result.  For finite t only (the caller's
-// r = 0 case must not occur: the Newton-3 tile kernels have no self pairs, distinct pad ions).
-__device__ __forceinline__ double exp2_neg_cut(double t, bool keep) {
-    const double n = __builtin_rint(t);
-    const double f = t - n;
-    double p = 0x1.e9ec1fcb69a7fp-32;
-    p = fma(p, f, 0x1.e6228acd1c6e5p-28);
-    p = fma(p, f, 0x1.b524ebd13a55fp-24);
-    p = fma(p, f, 0x1.62bfc2c86d700p-20);
-    p = fma(p, f, 0x1.ffcbfc6da6ed1p-17);
-    p = fma(p, f, 0x1.430913112c61bp-13);
-    p = fma(p, f, 0x1.5d87fe78a3f9cp-10);
-    p = fma(p, f, 0x1.3b2ab6fb9f1a5p-7);
-    p = fma(p, f, 0x1.c6b08d704a0c6p-5);
-    p = fma(p, f, 0x1.ebfbdff82c5aep-3);
-    p = fma(p, f, 0x1.62e42fefa39efp-1);
     p = fma(p, f, 1.0);
     return ldexp(p, keep ? (int)n : -1100);
 }
@@ -439,12 +415,12 @@ struct N3BArgs {
     const int* perm;    // sorted index -> ion
     const double* boxes;// [12][T]: tile center (x, y, z), half extents, raw coordinate min, max
     double Rmid;        // sub-tile groups >= Rmid apart take the mid pair form (rsq1 + table 2^t, ~2e-14
-                        // relative; forces only, MDQT_EXP_TAB); >= Rcut: never
+                        // relative; forces only); >= Rcut: never
     double Rfar;        // tile pairs whose boxes are >= Rfar apart take the far pair form (kFarRelErr;
                         // forces only, use_sort 1 or 2); >= Rcut: never
     double Rvfar;       // >= Rvfar apart: the very-far form (raw rsq, degree-5 2^f); >= Rcut: never
     double Rufar;       // >= Rufar apart: the ultra-far form (raw rsq, v_exp_f32); >= Rcut: never
-    double Rufar32;     // >= Rufar32 apart (uniform image): the ultra-far form in f32 (MDQT_UFAR32)
+    double Rufar32;     // >= Rufar32 apart (uniform image): the ultra-far form in f32
     double rc2;         // Rcut^2: the very-far and ultra-far forms keep a pair iff r^2 < rc2 (r^2 in f64,
                         // as exact as the exact form's r < Rcut), not on their low-precision r
     double Rskip;       // force tile pairs whose boxes are >= Rskip apart are skipped (use_sort 1):
@@ -500,10 +476,7 @@ constexpr int kCensus = 15;                 // (round 6: + 14 ufar_image)
 // tiles per block of the Newton-3 block kernel (= its waves per workgroup): 8 (round 4, A/B vs 16:
 // C3 -2.7 %, C5 -2.5 %, N = 1M -4.3 % per force call — three 8-wave workgroups per CU at 80 VGPRs
 // instead of two 16-wave ones at 64: shorter J-step barriers, fewer spills; 4: slower)
-#ifndef MDQT_N3B_BW
-#define MDQT_N3B_BW 8
-#endif
-constexpr int kN3BBlock = MDQT_N3B_BW;
+constexpr int kN3BBlock = 8;
 hipError_t launch_n3b_census(const N3BArgs& a, unsigned long long* out, hipStream_t s, unsigned long long* bw = nullptr,
                              unsigned long long* bal = nullptr);
 hipError_t launch_sum_rank_chunks(const double* const* parts, int world, int rank, int S, double* F, hipStream_t s);

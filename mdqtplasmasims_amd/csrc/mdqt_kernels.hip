@@ -366,9 +366,6 @@ __global__ __launch_bounds__(256) void k_substeps_lanes(SubstepArgs a, const Lan
     const QTConst& qc = a.qc;
     const int S = a.S;
     // per-lane row structure of M and kick weights
-#if !MDQT_GATHER_LDS
-    const int srcA = g0 + tab->colA[k], srcB = g0 + tab->colB[k], srcC = g0 + tab->colC[k];
-#endif
     const int order = tab->order[k], hasB = tab->hasB[k], hasC = tab->hasC[k];
     const int dynB = tab->dynB[k], dynC = tab->dynC[k];
     const cxd cA = {tab->cAre[k], tab->cAim[k]};
@@ -408,7 +405,6 @@ __global__ __launch_bounds__(256) void k_substeps_lanes(SubstepArgs a, const Lan
         }
     }
     __syncthreads();
-#if MDQT_GATHER_LDS
     __shared__ double2 xg[256];
     const int ldsA = (threadIdx.x & ~15) + tab->colA[k], ldsB = (threadIdx.x & ~15) + tab->colB[k],
               ldsC = (threadIdx.x & ~15) + tab->colC[k];
@@ -419,11 +415,6 @@ __global__ __launch_bounds__(256) void k_substeps_lanes(SubstepArgs a, const Lan
         const double2 ta = xg[ldsA], tb = xg[ldsB], tc = xg[ldsC];
         A = {ta.x, ta.y}; B = {tb.x, tb.y}; C = {tc.x, tc.y};
     };
-#else
-    auto exchange = [&](cxd v, cxd& A, cxd& B, cxd& C) {
-        A = gatc(v, srcA); B = gatc(v, srcB); C = gatc(v, srcC);
-    };
-#endif
     for (int s = 0; s < a.nsub; ++s) {
         if (a.do_step) {                              // step(), as in k_substeps
             const bool moving = a.t[s] > 0;

@@ -20,7 +20,7 @@ static const TierConst kTierConsts[] = {
 // Newton-3 blocks in spatial order with the fast pair form and no range guard; the mid form needs its table
 static double tier_const(const mdqt_ctx* s, int k, int level, double* bound) {
     *bound = 0.;
-    const bool on = (level != 5 || MDQT_EXP_TAB) && s->use_n3b && s->sort_mode != 0 && s->force_variant == 1 && !s->guard;
+    const bool on = s->use_n3b && s->sort_mode != 0 && s->force_variant == 1 && !s->guard;
     return on ? tier_radius(s, k, level, bound) : s->L / 2.;
 }
 
@@ -109,7 +109,7 @@ extern "C" double mdqt_get_const(const mdqt_ctx* s, const char* n) {
         if (tc.level == 3) {                           // ultra far: never beyond f32's normal range (tier_radii)
             if (r < s->L / 2. && s->L / 2. > 80. * s->lDeb) { r = s->L / 2.; bound = 0.; }
             double b32 = 0.;                           // + the f32 shell beyond force_ufar32_radius
-            if (r < s->L / 2. && MDQT_UFAR32) tier_radius(s, s->ufar_exp, 4, &b32);
+            if (r < s->L / 2.) tier_radius(s, s->ufar_exp, 4, &b32);
             bound += b32;
         }
         return radius ? r : bound;
@@ -117,7 +117,7 @@ extern "C" double mdqt_get_const(const mdqt_ctx* s, const char* n) {
     if (!strcmp(n, "force_ufar32_radius")) {          // the f32 ultra-far form's radius (L/2: off)
         double bound;
         const double r3 = mdqt_get_const(s, "force_ufar_radius");
-        return (r3 < s->L / 2. && MDQT_UFAR32) ? tier_radius(s, s->ufar_exp, 4, &bound) : s->L / 2.;
+        return r3 < s->L / 2. ? tier_radius(s, s->ufar_exp, 4, &bound) : s->L / 2.;
     }
     if (!strcmp(n, "fused_step")) return s->fused_opt;
     if (!strcmp(n, "qt_im01")) return s->qc.im01;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B kernel timing of library variants built by tools/expt_build.sh (C2 line only):
-#   bash tools/gpu/ab.sh base nojacc w8 ...   (base = the product library)
+#   bash tools/gpu/ab.sh base name1 name2 ...   (base = the product library, others expt/<name>)
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
