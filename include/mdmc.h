@@ -130,9 +130,18 @@ int mdmc_set_psi(mdmc_ctx* c, const double* psi);
  * `srun tagQuad $SLURM_ARRAY_TASK_ID`).  An ensemble holds njobs such jobs in one process: member k has
  * job + k and seed + k, and its state and files are bit for bit those of its own run.  A single job's
  * Metropolis anneal is one workgroup on one CU (the chain is sequential); the ensemble anneals all members
- * with ONE launch of njobs workgroups, so N <= 6144 (the LDS-resident kernel).  The MD stages queue every
- * member's own launches on its own stream, so they overlap on the chip.  Members need no lockstep: any
- * mdmc_* call on a member between ensemble calls is legal and the member simply carries its state. */
+ * with ONE launch of njobs workgroups, so N <= 6144 (the LDS-resident kernel).  The MD stages run one of two
+ * ways (mdmc_ensemble_set_md_batch), with the same bits either way:
+ *   md_batch 0 (default)  every member's own launches queued on its own stream, so they overlap on the chip;
+ *   md_batch 1            one force launch and one velocity-Verlet launch per step for ALL members (plus one
+ *                         collision scatter on a step where a member has a hit), and one launch per kind for
+ *                         the per-step observables of the recorded stages, on the ensemble's stream: the
+ *                         single-job kernels' bodies on each member's own argument block in device memory.
+ *                         mdmc_ensemble_md_steps and, in mdmc_ensemble_run, every MD stage but the QT programs'
+ *                         pump and recorded stage go this way; g(r) and the autocorrelations stay per member.
+ * Members need no lockstep: any mdmc_* call on a member between ensemble calls is legal and the member simply
+ * carries its state (its buffer parity, its stale pre-advanced positions, its own collision frequency and
+ * laser force included). */
 typedef struct mdmc_ensemble mdmc_ensemble;
 int       mdmc_ensemble_job_params(const mdmc_params* base, int k, mdmc_params* out); /* job+k, seed+k only; k in [0,1024) */
 int       mdmc_ensemble_create(const mdmc_params* p, int njobs, mdmc_ensemble** out); /* njobs x mdmc_create; 1..1024 */
@@ -143,11 +152,19 @@ int       mdmc_ensemble_init(mdmc_ensemble* e);            /* mdmc_init of every
 /* mdmc_monte_carlo of every member in batched launches; accepted [njobs] or NULL */
 int       mdmc_ensemble_monte_carlo(mdmc_ensemble* e, int nsteps, long long* accepted);
 int       mdmc_ensemble_md_steps(mdmc_ensemble* e, int nsteps);  /* mdmc_md_steps of every member, step by step */
+int       mdmc_ensemble_set_md_batch(mdmc_ensemble* e, int mode); /* 0: member by member, 1: batched; else an error */
+int       mdmc_ensemble_md_batch(const mdmc_ensemble* e);         /* the mode (< 0: error) */
+/* kernel launches the batched MD path has issued since creation (md_batch 0 leaves it unchanged): 2 per
+ * collisionless step whatever njobs is, + 1 on a step with a hit, + 1 per observable kind and step, + 1 per
+ * member whose pre-advanced positions were stale at the start of a call */
+int       mdmc_ensemble_md_launches(mdmc_ensemble* e, unsigned long long* out);
 int       mdmc_ensemble_run(mdmc_ensemble* e, int verbose);      /* mdmc_run of every member, stage by stage */
-int       mdmc_ensemble_enable_timing(mdmc_ensemble* e, int on); /* timestamps on the anneal launches, stage timers */
+int       mdmc_ensemble_enable_timing(mdmc_ensemble* e, int on); /* timestamps on the batched launches, stage timers */
 /* out[0..5): the anneal launches since the last call: sum (ms), count, median, min, max (ms);
  * out[5..11): wall ms of the last run's stages (timing on): anneal, pre-record MD, QT pump, recorded MD,
- * autocorrelations, the rest.  Fills min(n, 11) entries, n >= 3 */
+ * autocorrelations, the rest; out[11..16), out[16..21): the same five figures of the batched force and of the
+ * batched velocity-Verlet launches (md_batch 1, timing on; the launches' own timestamps).
+ * Fills min(n, 21) entries, n >= 3 */
 int       mdmc_ensemble_kernel_times(mdmc_ensemble* e, double* out, int n);
 
 #ifdef __cplusplus

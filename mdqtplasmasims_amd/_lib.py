@@ -123,6 +123,9 @@ MDMC_SIGNATURES = [
     ("mdmc_ensemble_init", C.c_int, [C.c_void_p]),
     ("mdmc_ensemble_monte_carlo", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),
     ("mdmc_ensemble_md_steps", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdmc_ensemble_set_md_batch", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdmc_ensemble_md_batch", C.c_int, [C.c_void_p]),
+    ("mdmc_ensemble_md_launches", C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     ("mdmc_ensemble_run", C.c_int, [C.c_void_p, C.c_int]),
     ("mdmc_ensemble_enable_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("mdmc_ensemble_kernel_times", C.c_int, [C.c_void_p, _dp, C.c_int]),

@@ -10,7 +10,8 @@
 //
 //   --njobs=J runs the jobs <job> .. <job>+J-1 of the reference's Slurm array (exampleSlurmFile.slurm:3,16)
 //   as one ensemble (mdmc_ensemble_run: the J Metropolis chains annealed by one launch), job k seeded
-//   seed + k; each job's files are those of `mdmc <job>+k --seed=<seed>+k`.
+//   seed + k; each job's files are those of `mdmc <job>+k --seed=<seed>+k`.  --md_batch=1 steps the jobs' MD stages
+//   in batched launches (mdmc_ensemble_set_md_batch), --md_batch=0 member by member: the same files either way.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -31,7 +32,9 @@ static void usage(void) {
             "                  [--device=-1] [--force_kernel=1] [--quiet=0]\n"
             "                  [--qt_model=0|1|2|3] [--tpumpreal=2e-7] [--detuning=-2.5] [--Om=0.7]\n"
             "       mdmc <job> --njobs=J [... as above]   jobs <job> .. <job>+J-1 as one ensemble (J in 1 .. 1024;\n"
-            "                  seeds seed .. seed+J-1; N <= 6144)\n");
+            "                  seeds seed .. seed+J-1; N <= 6144)\n"
+            "                  [--md_batch=0|1]   with --njobs only: the MD stages member by member (0, default) or\n"
+            "                  in batched launches, one force and one velocity-Verlet launch per step for all jobs (1)\n");
 }
 
 int main(int argc, char** argv) {
@@ -49,6 +52,7 @@ int main(int argc, char** argv) {
     p.job = (uint32_t)job;
     int seed_given = 0, quiet = 0;
     long njobs = -1;                                        // --njobs: the jobs of an ensemble (-1: not given)
+    int md_batch = -1;                                      // --md_batch (-1: not given)
     for (int i = 2; i < argc; ++i) {
         const char* a = argv[i];
         if (strncmp(a, "--", 2) != 0 || !strchr(a, '=')) { usage(); return 2; }
@@ -76,6 +80,11 @@ int main(int argc, char** argv) {
             if (end == v || *end || njobs < 1 || njobs > 1024) { usage(); return 2; }
             continue;
         }
+        if (!strcmp(key, "md_batch")) {
+            if (strcmp(v, "0") != 0 && strcmp(v, "1") != 0) { usage(); return 2; }
+            md_batch = v[0] - '0';
+            continue;
+        }
         if (!strcmp(key, "seed")) { p.seed = (uint32_t)strtoul(v, NULL, 10); seed_given = 1; continue; }
         if (!strcmp(key, "saveDirectory")) {
             strncpy(p.saveDirectory, v, sizeof(p.saveDirectory) - 1);
@@ -84,11 +93,17 @@ int main(int argc, char** argv) {
         fprintf(stderr, "mdmc: unknown parameter %s\n", key);
         return 2;
     }
+    if (md_batch >= 0 && njobs < 1) { usage(); return 2; }    // the mode of an ensemble's MD stages
     if (!seed_given) p.seed = (uint32_t)(time(NULL) + job);   // the reference: std::random_device (:52)
     if (njobs > 0) {
         mdmc_ensemble* e = NULL;
         if (mdmc_ensemble_create(&p, (int)njobs, &e) != 0) {
             fprintf(stderr, "mdmc: %s\n", mdqt_last_error());
+            return 1;
+        }
+        if (md_batch >= 0 && mdmc_ensemble_set_md_batch(e, md_batch) != 0) {
+            fprintf(stderr, "mdmc: %s\n", mdqt_last_error());
+            mdmc_ensemble_destroy(e);
             return 1;
         }
         const int rc = mdmc_ensemble_run(e, !quiet);

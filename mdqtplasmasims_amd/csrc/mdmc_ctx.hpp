@@ -59,8 +59,20 @@ struct mdmc_ctx {
     unsigned short x48[3] = {0x330E, 0xABCD, 0x1234};   // drand48's default state (no srand48 in QTT)
 };
 
+// A pinned ring of equal slots for argument blocks on their way to the device: the host fills a slot, one
+// hipMemcpyAsync reads it in stream order, and the event recorded behind the copy says when the slot may be
+// written again (the host queues far ahead of the device, so a slot is not free when the call returns).
+struct mdmc_pin_ring {
+    char* base = nullptr;
+    size_t slot = 0;
+    int next = 0;
+    std::vector<hipEvent_t> ev;        // one per slot
+    std::vector<char> busy;            // a copy of the slot has been queued
+};
+
 // J contexts (job + k, seed + k) annealed by one launch (mdmc_ensemble.cpp).  Every member keeps its own
-// stream for everything else; the ensemble's stream carries the batched anneal and its argument blocks.
+// stream for everything that is its own; the ensemble's stream carries the batched anneal, the batched MD
+// steps and per-step observables (md_batch 1), and their argument blocks.
 struct mdmc_ensemble {
     std::vector<mdmc_ctx*> jobs;
     int dev = 0;
@@ -76,6 +88,27 @@ struct mdmc_ensemble {
     // autocorrelations, the rest
     static constexpr int kStages = 6;
     double stage_ms[kStages] = {};
+    // ---- batched MD (mdmc_ensemble.cpp, "batched MD stretches") ----
+    int mdBatch = 0;                   // mdmc_ensemble_set_md_batch: 0 member by member, 1 batched
+    unsigned long long mdLaunches = 0; // kernel launches the batched path has issued
+    // device blocks of a stretch, one allocation: N3Args [2][J], VVArgs [2][J] (the two buffer parities of
+    // the collisionless step), MDObsArgs [J], then VVArgs [J] of a step with collision draws
+    char* dBlocks = nullptr;
+    mdqt::N3Args* dN3 = nullptr;
+    mdqt::VVArgs* dVV = nullptr;
+    mdqt::MDObsArgs* dObs = nullptr;
+    mdqt::VVArgs* dVVc = nullptr;
+    size_t hdrBytes = 0;               // of the first three
+    mdmc_pin_ring hdrRing, vvRing;     // a stretch's blocks; a collisional step's VVArgs [J]
+    bool open = false;                 // inside a stretch: the members' streams are fenced behind `stream`
+    int parity = 0;                    // which of the two block sets the next step takes
+    int obsCap = 0;                    // rows of the members' dTemp / dMom at the stretch's start
+    std::vector<char> coll;            // [J] the member draws collisions in this stretch
+    std::vector<unsigned long long> skip;   // [J] mt19937 words of collisionless steps still to discard
+    std::vector<hipEvent_t> evMember;  // [J] fences: a member's stream -> `stream`
+    hipEvent_t evEns = nullptr;        // `stream` -> the members' streams
+    std::vector<hipEvent_t> evForce, evVV;   // the batched force / velocity-Verlet launches' timestamps (pairs)
+    int usedForce = 0, usedVV = 0;
 };
 
 namespace mdmc {
@@ -86,11 +119,29 @@ constexpr int kBatchedMaxN = 6144;     // positions in LDS: k_monte_carlo_lds<6>
 // mdmc_engine.cpp
 void mc_args(const mdmc_ctx* c, mdqt::MCArgs& a);   // the anneal's argument block (nsteps left to the caller)
 int md_step_async(mdmc_ctx* c);                     // one MDStep() queued on the member's stream
+// the pieces of md_step_async, shared with the batched step: the force and velocity-Verlet argument blocks
+// of the member's current buffers, and the step's collision rolls and Maxwellians from the member's rng into
+// its pinned ring (`drain`: the stream whose queued launches read the ring)
+void n3_args(const mdmc_ctx* c, mdqt::N3Args& a);
+void vv_args(const mdmc_ctx* c, const double* hits, int nhits, mdqt::VVArgs& v);
+int collision_draws(mdmc_ctx* c, hipStream_t drain, double** hits, int* nhits);
+int pair_corr_queue(mdmc_ctx* c);                   // g(r) of the member queued on its stream, evDrain behind the copy
 int qsteps_async(mdmc_ctx* c, int n);
 // main() of the program for J contexts in lockstep: J = 1 without an ensemble is mdmc_run
 int run_members(mdmc_ctx* const* cs, int J, mdmc_ensemble* ens, int verbose);
 
 // mdmc_ensemble.cpp: nsteps Metropolis steps of every member, chunked launches on the ensemble's stream
 int ensemble_anneal(mdmc_ensemble* e, int nsteps, long long* accepted);
+// batched MD stretches (md_batch 1): begin fences `stream` behind every member's stream and uploads the
+// members' blocks; a step is one force and one velocity-Verlet launch for all members (+ one collision
+// scatter when a member has a hit); the observables of step k are one launch per kind; end fences the
+// members' streams behind `stream` and settles the members' rng
+int ensemble_md_begin(mdmc_ensemble* e);
+int ensemble_md_step(mdmc_ensemble* e);
+int ensemble_md_end(mdmc_ensemble* e);
+int ensemble_md_temperatures(mdmc_ensemble* e, int k);
+int ensemble_md_tag_moments(mdmc_ensemble* e, int k);
+int ensemble_md_store_velocities(mdmc_ensemble* e, int t);
+int ensemble_md_pair_corr_queue(mdmc_ensemble* e);   // every member's g(r) on its own stream, fenced both ways
 
 }  // namespace mdmc

@@ -59,12 +59,7 @@ int rng_from_device(mdmc_ctx* c) {
 // summed into A by k_vv_step
 int accelerations(mdmc_ctx* c) {
     N3Args a;
-    memset(&a, 0, sizeof a);
-    a.R = c->dR; a.P = c->dSlots; a.pairs = c->dPairs;
-    a.N = c->N; a.S = c->S; a.ntiles = c->nt; a.npairs = c->npairs;
-    a.L = c->L; a.lDeb = 1. / c->p.kappa; a.Rcut = c->rCut; a.invlDeb = c->p.kappa;
-    a.micT = mic_threshold(c->L); a.micGuard = 1.25 * c->L; a.guard = 0;
-    a.rc2 = sqrt_threshold(c->rCut);
+    mdmc::n3_args(c, a);
     // force_kernel 1: variant 2 (fast values, the reference's exact pair set), 0: exact
     HIPCHK(launch_forces_n3(a, c->p.force_kernel == 1 ? 2 : 0, c->st));
     return 0;
@@ -350,31 +345,59 @@ int mdmc::md_step_async(mdmc_ctx* c) {
     if (dt * c->collisionFreq <= 0) {
         // every roll misses (uni >= 0): each is one generate_canonical, i.e. two mt19937 words
         c->rng.discard(2ull * N);
-    } else {
-        if (c->hitOff + N > c->hitCap) {           // ring wrap: the queued readers must be done
-            HIPCHK(hipStreamSynchronize(c->st));
-            c->hitOff = 0;
-        }
-        hits = c->hHits + (size_t)4 * c->hitOff;
-        for (int i = 0; i < N; i++) {
-            const double collRoll = c->uni(c->rng);
-            if (collRoll < dt * c->collisionFreq) {
-                double* e = hits + 4 * (size_t)nh++;
-                e[0] = i;
-                e[1] = c->vd(c->rng);
-                e[2] = c->vd(c->rng);
-                e[3] = c->vd(c->rng);
-            }
-        }
-        c->hitOff += nh;
+    } else if (collision_draws(c, c->st, &hits, &nh)) {
+        return -1;
     }
     VVArgs v;
-    v.V = c->dV; v.A = c->dA; v.slots = c->dSlots; v.nslots = c->nt; v.R = c->dR; v.Rn = c->dRn; v.L = c->L;
-    v.hits = hits; v.nhits = nh; v.N = N; v.S = c->S;
-    v.laser = c->addLaserForce; v.oneAxis = c->p.applyForceAlongOneAxisOnly;
-    v.dt = dt; v.p6 = pow(10, -6); v.beta = c->p.beta; v.sqrtn = sqrt(c->p.n);
+    vv_args(c, hits, nh, v);
     HIPCHK(launch_vv_velocities(v, c->st));                                                   // :469-502
     c->rnValid = true;
+    return 0;
+}
+
+// calculateAccelerations' argument block on the member's current positions (:387-448; lDeb = 1/kappa)
+void mdmc::n3_args(const mdmc_ctx* c, N3Args& a) {
+    memset(&a, 0, sizeof a);
+    a.R = c->dR; a.P = c->dSlots; a.pairs = c->dPairs;
+    a.N = c->N; a.S = c->S; a.ntiles = c->nt; a.npairs = c->npairs;
+    a.L = c->L; a.lDeb = 1. / c->p.kappa; a.Rcut = c->rCut; a.invlDeb = c->p.kappa;
+    a.micT = mic_threshold(c->L); a.micGuard = 1.25 * c->L; a.guard = 0;
+    a.rc2 = sqrt_threshold(c->rCut);
+}
+
+// stepVelocities' argument block (:469-502) on the member's current buffers, laser force and collision list
+void mdmc::vv_args(const mdmc_ctx* c, const double* hits, int nhits, VVArgs& v) {
+    memset(&v, 0, sizeof v);
+    v.V = c->dV; v.A = c->dA; v.slots = c->dSlots; v.nslots = c->nt; v.R = c->dR; v.Rn = c->dRn; v.L = c->L;
+    v.hits = hits; v.nhits = nhits; v.N = c->N; v.S = c->S;
+    v.laser = c->addLaserForce; v.oneAxis = c->p.applyForceAlongOneAxisOnly;
+    v.dt = c->p.timeStep; v.p6 = pow(10, -6); v.beta = c->p.beta; v.sqrtn = sqrt(c->p.n);
+}
+
+// the collision rolls and Maxwellians of one step (:474-482, the reference's order) into the member's pinned
+// ring; `drain` is the stream whose queued launches read the ring
+int mdmc::collision_draws(mdmc_ctx* c, hipStream_t drain, double** hits_out, int* nhits) {
+    const int N = c->N;
+    const double dt = c->p.timeStep;
+    if (c->hitOff + N > c->hitCap) {           // ring wrap: the queued readers must be done
+        HIPCHK(hipStreamSynchronize(drain));
+        c->hitOff = 0;
+    }
+    double* hits = c->hHits + (size_t)4 * c->hitOff;
+    int nh = 0;
+    for (int i = 0; i < N; i++) {
+        const double collRoll = c->uni(c->rng);
+        if (collRoll < dt * c->collisionFreq) {
+            double* e = hits + 4 * (size_t)nh++;
+            e[0] = i;
+            e[1] = c->vd(c->rng);
+            e[2] = c->vd(c->rng);
+            e[3] = c->vd(c->rng);
+        }
+    }
+    c->hitOff += nh;
+    *hits_out = hits;
+    *nhits = nh;
     return 0;
 }
 
@@ -401,7 +424,7 @@ extern "C" int mdmc_set_laser_force(mdmc_ctx* c, int on) {
 
 // recordPairPairCorr (:584-635): the histogram on the device (queued, read back into the pinned landing
 // area, evDrain behind the copy), the normalisation here once the copy has landed
-static int pair_corr_queue(mdmc_ctx* c) {
+int mdmc::pair_corr_queue(mdmc_ctx* c) {
     const int nb = c->nbins;
     if (nb > 0) {
         HIPCHK(hipMemsetAsync(c->dHist, 0, nb * sizeof(unsigned), c->st));
@@ -411,6 +434,7 @@ static int pair_corr_queue(mdmc_ctx* c) {
     HIPCHK(hipEventRecord(c->evDrain, c->st));
     return 0;
 }
+using mdmc::pair_corr_queue;
 static void pair_corr_finish(const mdmc_ctx* c, std::vector<double>& g) {
     const int nb = c->nbins;
     g.assign(nb > 0 ? nb : 0, 0.);
@@ -731,7 +755,9 @@ extern "C" const char* mdmc_save_directory(const mdmc_ctx* c) { return c ? c->sa
 // ensemble's run J members.  Every stage queues all members' launches and copies of a step on
 // their own streams first and then drains member by member (wait for the copies, format,
 // write), so a step with a host round trip costs one wait, not J in a row, and the host
-// formats one member's rows while the device runs the others' MD step.
+// formats one member's rows while the device runs the others' MD step.  An ensemble with
+// md_batch 1 queues the MD steps and per-step observables of stage_md, stage_md_temp_axes and
+// stage_record_mcmd as batched launches on the ensemble's stream instead (batched()).
 // ------------------------------------------------------------------------------------------
 namespace {
 
@@ -838,23 +864,39 @@ int stage_anneal(Run& r) {
 }
 
 // n MDStep()s of every member; `count` prints the step counter every 100 (:1081-1089, :1126-1135)
+// An ensemble with md_batch 1 steps its members in batched launches on the ensemble's stream (mdmc_ensemble.cpp,
+// "batched MD stretches"): every MD stage below but the QT programs' pump and recorded stage is one stretch.
+bool batched(const Run& r) { return r.ens && r.ens->mdBatch == 1; }
+
 int stage_md(Run& r, int n, bool count) {
+    if (batched(r) && mdmc::ensemble_md_begin(r.ens)) return -1;
     for (int k = 0; k < n; k++) {
         if (count && r.verbose && k % 100 == 0) printf("%d\n", k);
+        if (batched(r)) {
+            if (mdmc::ensemble_md_step(r.ens)) return -1;
+            continue;
+        }
         for (int j = 0; j < r.J; ++j)
             if (mdmc::md_step_async(r.c[j])) return -1;
     }
-    return 0;
+    return batched(r) ? mdmc::ensemble_md_end(r.ens) : 0;
 }
 
 // n MDStep()s with the axis temperatures of every step, written to `name` (:1115-1123, :1141-1165)
 int stage_md_temp_axes(Run& r, int n, const char* name) {
-    for (int k = 0; k < n; k++)
-        for (int j = 0; j < r.J; ++j) {
-            mdmc_ctx* c = r.c[j];
-            HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dTemp + (size_t)4 * k, c->st));
-            if (mdmc::md_step_async(c)) return -1;
-        }
+    if (batched(r)) {
+        if (mdmc::ensemble_md_begin(r.ens)) return -1;
+        for (int k = 0; k < n; k++)
+            if (mdmc::ensemble_md_temperatures(r.ens, k) || mdmc::ensemble_md_step(r.ens)) return -1;
+        if (mdmc::ensemble_md_end(r.ens)) return -1;
+    } else {
+        for (int k = 0; k < n; k++)
+            for (int j = 0; j < r.J; ++j) {
+                mdmc_ctx* c = r.c[j];
+                HIPCHK(launch_temperatures(c->dV, c->N, c->S, c->dTemp + (size_t)4 * k, c->st));
+                if (mdmc::md_step_async(c)) return -1;
+            }
+    }
     for (int j = 0; j < r.J; ++j)
         if (write_temp_axes(r.c[j], name, n)) return -1;
     return 0;
@@ -897,10 +939,19 @@ int stage_record_mcmd(Run& r) {
         if (ensure_step_buffers(c, std::max(T, std::max(p.numInstantaneousAnisotropySteps,
                                                         std::max(p.anisotropyFromForcesRelaxSteps, 1 << 16))))) return -1;
     }
+    if (batched(r) && mdmc::ensemble_md_begin(r.ens)) return -1;
     for (int k = 0; k < T; k++) {
         const bool gr = k % 100 == 0;
         if (gr && r.verbose) printf("%d\n", k);
-        for (int j = 0; j < r.J; ++j) {
+        if (batched(r)) {
+            // one launch per kind for all members; g(r) stays each member's own, on its own stream
+            mdmc_ensemble* e = r.ens;
+            if (mdmc::ensemble_md_tag_moments(e, k) || (gr && mdmc::ensemble_md_pair_corr_queue(e)) ||
+                mdmc::ensemble_md_temperatures(e, k) || mdmc::ensemble_md_step(e) ||
+                mdmc::ensemble_md_store_velocities(e, k))
+                return -1;
+        }
+        for (int j = 0; j < r.J && !batched(r); ++j) {
             mdmc_ctx* c = r.c[j];
             HIPCHK(launch_tag_moments(c->dV, c->dTags, c->N, c->dMom + (size_t)20 * k, c->st));
             if (gr && pair_corr_queue(c)) return -1;
@@ -914,6 +965,7 @@ int stage_record_mcmd(Run& r) {
                 if (write_pair_corr_file(r.c[j], k)) return -1;
             }
     }
+    if (batched(r) && mdmc::ensemble_md_end(r.ens)) return -1;
     for (int j = 0; j < r.J; ++j)
         if (write_recorded_mcmd(r.c[j])) return -1;
     return 0;

@@ -3,8 +3,11 @@
 // $SLURM_ARRAY_TASK_ID`); a single job's Metropolis anneal is one workgroup on one CU, because the chain is
 // sequential, so the array's anneals run here as ONE launch of J workgroups (k_monte_carlo_lds_ens: the
 // single-job kernel's body on each member's own argument block, which is the bit-identity argument).  The MD
-// stages queue every member's own launches on its own stream, one host thread, so they overlap on the chip;
-// they are the single context's code on the single context's arguments.
+// stages run one of two ways (mdmc_ensemble_set_md_batch).  Mode 0 queues every member's own launches on its
+// own stream, one host thread, so they overlap on the chip: the single context's code on the single
+// context's arguments.  Mode 1 steps all members with one force and one velocity-Verlet launch per step on
+// the ensemble's stream ("batched MD stretches" below), again the single-job kernels' bodies on each member's
+// own argument block.
 #include <algorithm>
 #include <memory>
 
@@ -21,7 +24,228 @@ int sync_members(mdmc_ensemble* e) {
     return 0;
 }
 
+constexpr int kHdrSlots = 4;     // stretches whose blocks may be on their way at once
+constexpr int kVVSlots = 64;     // collisional steps whose blocks may be on their way at once
+
+int ring_create(mdmc_pin_ring& r, size_t slot, int n) {
+    r.slot = slot;
+    if (hipHostMalloc((void**)&r.base, slot * (size_t)n, hipHostMallocDefault) != hipSuccess)
+        return set_error("mdmc_ensemble_create: pinned allocation of the MD argument blocks failed");
+    r.busy.assign((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        r.ev.push_back(ev);
+    }
+    return 0;
+}
+
+// the next slot, once the copy that last read it has run (kHdrSlots stretches / kVVSlots steps ago)
+int ring_take(mdmc_pin_ring& r, char** slot, int* idx) {
+    const int i = r.next;
+    r.next = (i + 1) % (int)r.ev.size();
+    if (r.busy[(size_t)i]) HIPCHK(hipEventSynchronize(r.ev[(size_t)i]));
+    r.busy[(size_t)i] = 0;
+    *slot = r.base + r.slot * (size_t)i;
+    *idx = i;
+    return 0;
+}
+
+// one copy of the slot in stream order, the slot's event behind it
+int ring_send(mdmc_pin_ring& r, int idx, void* dst, size_t bytes, hipStream_t s) {
+    HIPCHK(hipMemcpyAsync(dst, r.base + r.slot * (size_t)idx, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(r.ev[(size_t)idx], s));
+    r.busy[(size_t)idx] = 1;
+    return 0;
+}
+
+int md_blocks_create(mdmc_ensemble* e) {
+    const size_t J = e->jobs.size();
+    const size_t n3 = 2 * J * sizeof(N3Args), vv = 2 * J * sizeof(VVArgs), ob = J * sizeof(MDObsArgs);
+    e->hdrBytes = n3 + vv + ob;
+    if (hipMalloc((void**)&e->dBlocks, e->hdrBytes + J * sizeof(VVArgs)) != hipSuccess)
+        return set_error("mdmc_ensemble_create: allocating the MD argument blocks of %zu jobs failed", J);
+    e->dN3 = reinterpret_cast<N3Args*>(e->dBlocks);
+    e->dVV = reinterpret_cast<VVArgs*>(e->dBlocks + n3);
+    e->dObs = reinterpret_cast<MDObsArgs*>(e->dBlocks + n3 + vv);
+    e->dVVc = reinterpret_cast<VVArgs*>(e->dBlocks + e->hdrBytes);
+    if (ring_create(e->hdrRing, e->hdrBytes, kHdrSlots) || ring_create(e->vvRing, J * sizeof(VVArgs), kVVSlots)) return -1;
+    e->coll.assign(J, 0);
+    e->skip.assign(J, 0ull);
+    for (size_t k = 0; k < J; ++k) {
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        e->evMember.push_back(ev);
+    }
+    HIPCHK(hipEventCreateWithFlags(&e->evEns, hipEventDisableTiming));
+    return 0;
+}
+
+int need_open(const mdmc_ensemble* e, const char* what) {
+    if (!e->open) return set_error("%s outside a batched MD stretch", what);
+    return 0;
+}
+
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------------------
+// Batched MD stretches (md_batch 1).  A stretch is a run of MD steps of all members between two points where
+// the members' own streams matter:
+//   begin   `stream` waits on one event per member stream.  A member whose pre-advanced positions are stale
+//           (rnValid false: set_state, an anneal, anisotropize) gets its own k_vv_positions on `stream`.  Then
+//           every member's blocks are built by the helpers md_step_async uses — N3Args and VVArgs for BOTH
+//           buffer parities (dR / dRn swap every step), MDObsArgs — and go over in one copy.  The blocks are
+//           per member, so a member stepped alone an odd number of times simply has its pointers the other
+//           way round.
+//   step    swap every member's dR / dRn on the host; one k_pairs_n3_ens on set `parity`; the collision rolls
+//           of the members that have a collision frequency, drawn per member from its own Mt32 in the
+//           reference's order into its own pinned ring; one k_vv_step_ens — on the resident set when no member
+//           draws, else on a fresh VVArgs [J] (one copy in stream order from the pinned ring); one
+//           k_collide_ens if a member has a hit.  A collisionless member's discard(2N) is additive and
+//           applied once, at the end.
+//   end     the members' streams wait on one event of `stream`; the discards are applied.
+// Inside a stretch nothing touches a member's stream but its g(r) (ensemble_md_pair_corr_queue).
+// ------------------------------------------------------------------------------------------------------------
+int mdmc::ensemble_md_begin(mdmc_ensemble* e) {
+    if (e->open) return set_error("ensemble_md_begin inside a batched MD stretch");
+    const size_t J = e->jobs.size();
+    HIPCHK(hipSetDevice(e->dev));
+    for (size_t k = 0; k < J; ++k) {
+        HIPCHK(hipEventRecord(e->evMember[k], e->jobs[k]->st));
+        HIPCHK(hipStreamWaitEvent(e->stream, e->evMember[k], 0));
+    }
+    char* h = nullptr;
+    int slot = 0;
+    if (ring_take(e->hdrRing, &h, &slot)) return -1;
+    N3Args* n3 = reinterpret_cast<N3Args*>(h);
+    VVArgs* vv = reinterpret_cast<VVArgs*>(h + 2 * J * sizeof(N3Args));
+    MDObsArgs* ob = reinterpret_cast<MDObsArgs*>(h + 2 * J * (sizeof(N3Args) + sizeof(VVArgs)));
+    e->obsCap = e->jobs[0]->capTemp;
+    for (size_t k = 0; k < J; ++k) {
+        mdmc_ctx* c = e->jobs[k];
+        if (!c->rnValid) {                                                                    // :452-467
+            HIPCHK(launch_vv_positions(c->dR, c->dV, c->dA, c->dRn, c->N, c->S, c->p.timeStep, c->L, e->stream));
+            ++e->mdLaunches;
+            c->rnValid = true;
+        }
+        for (int par = 0; par < 2; ++par) {      // set 0: the buffers as the first step sees them, after its swap
+            std::swap(c->dR, c->dRn);
+            mdmc::n3_args(c, n3[par * J + k]);
+            mdmc::vv_args(c, nullptr, 0, vv[par * J + k]);
+        }                                         // two swaps: the member's pointers are back
+        MDObsArgs& o = ob[k];
+        memset(&o, 0, sizeof o);
+        o.V = c->dV; o.tags = c->dTags; o.N = c->N; o.S = c->S; o.T = c->T;
+        o.temp = c->dTemp; o.mom = c->dMom; o.vs = c->dVS;
+        e->obsCap = std::min(e->obsCap, c->capTemp);
+        e->coll[k] = c->p.timeStep * c->collisionFreq > 0;
+        e->skip[k] = 0;
+    }
+    if (ring_send(e->hdrRing, slot, e->dBlocks, e->hdrBytes, e->stream)) return -1;
+    e->parity = 0;
+    e->open = true;
+    return 0;
+}
+
+int mdmc::ensemble_md_step(mdmc_ensemble* e) {
+    if (need_open(e, "ensemble_md_step")) return -1;
+    const size_t J = e->jobs.size();
+    const mdmc_ctx* c0 = e->jobs[0];
+    const int par = e->parity;
+    for (mdmc_ctx* c : e->jobs) std::swap(c->dR, c->dRn);
+    hipEvent_t f0 = nullptr, f1 = nullptr, v0 = nullptr, v1 = nullptr;
+    if (e->timing && (take_events(e->evForce, e->usedForce, &f0, &f1) || take_events(e->evVV, e->usedVV, &v0, &v1)))
+        return -1;
+    // force_kernel 1: variant 2 (fast values, the reference's exact pair set), 0: exact            :508
+    HIPCHK(launch_forces_n3_mdmc_ens(e->dN3 + par * J, (int)J, c0->npairs, c0->p.force_kernel == 1 ? 2 : 0, e->stream, f0, f1));
+    ++e->mdLaunches;
+    const VVArgs* blocks = e->dVV + par * J;
+    int max_hits = 0;
+    bool any = false;
+    for (size_t k = 0; k < J; ++k) any = any || e->coll[k];
+    if (any) {
+        char* h = nullptr;
+        int slot = 0;
+        if (ring_take(e->vvRing, &h, &slot)) return -1;
+        VVArgs* vv = reinterpret_cast<VVArgs*>(h);
+        for (size_t k = 0; k < J; ++k) {
+            mdmc_ctx* c = e->jobs[k];
+            double* hits = nullptr;
+            int nh = 0;
+            // every roll of a collisionless member misses (uni >= 0): one generate_canonical, two words, each
+            if (!e->coll[k]) e->skip[k] += 2ull * c->N;
+            else if (mdmc::collision_draws(c, e->stream, &hits, &nh)) return -1;
+            mdmc::vv_args(c, hits, nh, vv[k]);
+            max_hits = std::max(max_hits, nh);
+        }
+        if (ring_send(e->vvRing, slot, e->dVVc, J * sizeof(VVArgs), e->stream)) return -1;
+        blocks = e->dVVc;
+    } else {
+        for (size_t k = 0; k < J; ++k) e->skip[k] += 2ull * e->jobs[k]->N;
+    }
+    HIPCHK(launch_vv_step_ens(blocks, (int)J, c0->N, e->stream, v0, v1));                        // :469-502
+    ++e->mdLaunches;
+    if (max_hits > 0) {
+        HIPCHK(launch_collide_ens(blocks, (int)J, max_hits, e->stream));
+        ++e->mdLaunches;
+    }
+    e->parity = par ^ 1;
+    return 0;
+}
+
+int mdmc::ensemble_md_end(mdmc_ensemble* e) {
+    if (need_open(e, "ensemble_md_end")) return -1;
+    e->open = false;
+    HIPCHK(hipEventRecord(e->evEns, e->stream));
+    for (size_t k = 0; k < e->jobs.size(); ++k) {
+        mdmc_ctx* c = e->jobs[k];
+        HIPCHK(hipStreamWaitEvent(c->st, e->evEns, 0));
+        c->rng.discard(e->skip[k]);
+        e->skip[k] = 0;
+    }
+    return 0;
+}
+
+// the per-step observables of a recorded stage, one launch per kind: row k of every member's dTemp / dMom,
+// column t of its velocity store
+int mdmc::ensemble_md_temperatures(mdmc_ensemble* e, int k) {
+    if (need_open(e, "ensemble_md_temperatures")) return -1;
+    if (k < 0 || k >= e->obsCap) return set_error("ensemble_md_temperatures: step %d outside the %d buffered", k, e->obsCap);
+    HIPCHK(launch_temperatures_ens(e->dObs, (int)e->jobs.size(), k, e->stream));
+    ++e->mdLaunches;
+    return 0;
+}
+
+int mdmc::ensemble_md_tag_moments(mdmc_ensemble* e, int k) {
+    if (need_open(e, "ensemble_md_tag_moments")) return -1;
+    if (k < 0 || k >= e->obsCap) return set_error("ensemble_md_tag_moments: step %d outside the %d buffered", k, e->obsCap);
+    HIPCHK(launch_tag_moments_ens(e->dObs, (int)e->jobs.size(), k, e->stream));
+    ++e->mdLaunches;
+    return 0;
+}
+
+int mdmc::ensemble_md_store_velocities(mdmc_ensemble* e, int t) {                                // :513-523
+    if (need_open(e, "ensemble_md_store_velocities")) return -1;
+    const mdmc_ctx* c0 = e->jobs[0];
+    if (t < 0 || t >= c0->T) return set_error("ensemble_md_store_velocities: step %d outside [0, %d)", t, c0->T);
+    HIPCHK(launch_store_velocities_ens(e->dObs, (int)e->jobs.size(), c0->N, t, e->stream));
+    ++e->mdLaunches;
+    return 0;
+}
+
+// g(r) of every member inside a stretch: the histogram, its copy and evDrain stay on the member's stream,
+// which waits for the batched steps so far; the next batched step overwrites the buffer the histogram reads
+// (k_vv_step's Rn), so `stream` waits for every evDrain
+int mdmc::ensemble_md_pair_corr_queue(mdmc_ensemble* e) {
+    if (need_open(e, "ensemble_md_pair_corr_queue")) return -1;
+    HIPCHK(hipEventRecord(e->evEns, e->stream));
+    for (mdmc_ctx* c : e->jobs) {
+        HIPCHK(hipStreamWaitEvent(c->st, e->evEns, 0));
+        if (mdmc::pair_corr_queue(c)) return -1;
+        HIPCHK(hipStreamWaitEvent(e->stream, c->evDrain, 0));
+    }
+    return 0;
+}
 
 extern "C" int mdmc_ensemble_job_params(const mdmc_params* base, int k, mdmc_params* out) {
     if (!base || !out) return set_error("mdmc_ensemble_job_params: NULL argument");
@@ -38,6 +262,15 @@ extern "C" void mdmc_ensemble_destroy(mdmc_ensemble* e) {
     (void)hipSetDevice(e->dev);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (size_t k = e->jobs.size(); k-- > 0;) mdmc_destroy(e->jobs[k]);
+    if (e->dBlocks) (void)hipFree(e->dBlocks);
+    for (mdmc_pin_ring* r : {&e->hdrRing, &e->vvRing}) {
+        if (r->base) (void)hipHostFree(r->base);
+        for (hipEvent_t ev : r->ev) (void)hipEventDestroy(ev);
+    }
+    for (hipEvent_t ev : e->evMember) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->evForce) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->evVV) (void)hipEventDestroy(ev);
+    if (e->evEns) (void)hipEventDestroy(e->evEns);
     if (e->dArgs) (void)hipFree(e->dArgs);
     if (e->hArgs) (void)hipHostFree(e->hArgs);
     if (e->hMT) (void)hipHostFree(e->hMT);
@@ -79,6 +312,7 @@ extern "C" int mdmc_ensemble_create(const mdmc_params* p, int njobs, mdmc_ensemb
         hipHostMalloc((void**)&e->hMT, J * 625 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void**)&e->hAcc, J * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
         return set_error("mdmc_ensemble_create: allocating the argument blocks of %d jobs failed", njobs);
+    if (md_blocks_create(e.get())) return -1;
     *out = e.release();
     return 0;
 }
@@ -154,13 +388,22 @@ extern "C" int mdmc_ensemble_monte_carlo(mdmc_ensemble* e, int nsteps, long long
     return mdmc::ensemble_anneal(e, nsteps, accepted);
 }
 
-// MDStep() x n of every member (:504-511): each step queued member by member on the members' own streams
+// MDStep() x n of every member (:504-511): md_batch 0, each step queued member by member on the members' own
+// streams; md_batch 1, one batched stretch on the ensemble's stream
 extern "C" int mdmc_ensemble_md_steps(mdmc_ensemble* e, int nsteps) {
     if (!e) return set_error("NULL ensemble");
     HIPCHK(hipSetDevice(e->dev));
-    for (int k = 0; k < nsteps; ++k)
-        for (mdmc_ctx* c : e->jobs)
-            if (mdmc::md_step_async(c)) return -1;
+    if (e->mdBatch == 1 && nsteps > 0) {
+        bool ok = !mdmc::ensemble_md_begin(e);
+        for (int k = 0; ok && k < nsteps; ++k) ok = !mdmc::ensemble_md_step(e);
+        ok = ok && !mdmc::ensemble_md_end(e);
+        e->open = false;                       // a failed stretch is abandoned
+        if (!ok) return -1;
+    } else {
+        for (int k = 0; k < nsteps; ++k)
+            for (mdmc_ctx* c : e->jobs)
+                if (mdmc::md_step_async(c)) return -1;
+    }
     if (sync_members(e)) return -1;
     for (mdmc_ctx* c : e->jobs) c->hitOff = 0;
     return 0;
@@ -171,39 +414,76 @@ extern "C" int mdmc_ensemble_run(mdmc_ensemble* e, int verbose) {
     if (!e) return set_error("NULL ensemble");
     HIPCHK(hipSetDevice(e->dev));
     std::fill(e->stage_ms, e->stage_ms + mdmc_ensemble::kStages, 0.);
-    if (mdmc::run_members(e->jobs.data(), (int)e->jobs.size(), e, verbose)) return -1;
+    if (mdmc::run_members(e->jobs.data(), (int)e->jobs.size(), e, verbose)) {
+        e->open = false;                       // a failed stretch is abandoned
+        return -1;
+    }
     return sync_members(e);
 }
 
 extern "C" int mdmc_ensemble_enable_timing(mdmc_ensemble* e, int on) {
     if (!e) return set_error("NULL ensemble");
     e->timing = on > 0;
-    e->evused = 0;
+    e->evused = e->usedForce = e->usedVV = 0;
     return 0;
 }
 
-// the anneal launches' own durations (their dispatch timestamps) since the last call: out[0..5) = sum (ms),
-// launches, median, minimum, maximum (ms); out[5..11) = wall time (ms) of the last run's stages: anneal,
-// pre-record MD, QT pump, recorded MD, autocorrelations, the rest.  Fills what n holds (n >= 3); resets the
-// launch list
+extern "C" int mdmc_ensemble_set_md_batch(mdmc_ensemble* e, int mode) {
+    if (!e) return set_error("mdmc_ensemble_set_md_batch: NULL ensemble");
+    if (mode != 0 && mode != 1) return set_error("mdmc_ensemble_set_md_batch: mode must be 0 (member by member) or 1 (batched), not %d", mode);
+    e->mdBatch = mode;
+    return 0;
+}
+
+extern "C" int mdmc_ensemble_md_batch(const mdmc_ensemble* e) {
+    if (!e) return set_error("mdmc_ensemble_md_batch: NULL ensemble");
+    return e->mdBatch;
+}
+
+extern "C" int mdmc_ensemble_md_launches(mdmc_ensemble* e, unsigned long long* out) {
+    if (!e || !out) return set_error("mdmc_ensemble_md_launches: NULL argument");
+    *out = e->mdLaunches;
+    return 0;
+}
+
+namespace {
+
+// sum (ms), launches, median, minimum, maximum (ms) of the launches timed by pairs of events; resets the list
+int launch_stats(std::vector<hipEvent_t>& pool, int& used, double* v) {
+    std::vector<double> ms;
+    double tot = 0.;
+    for (int i = 0; i + 1 < used; i += 2) {
+        float x = 0.f;
+        HIPCHK(hipEventElapsedTime(&x, pool[(size_t)i], pool[(size_t)i + 1]));
+        ms.push_back(x);
+        tot += x;
+    }
+    std::sort(ms.begin(), ms.end());
+    v[0] = tot; v[1] = (double)ms.size();
+    v[2] = ms.empty() ? 0. : ms[ms.size() / 2];
+    v[3] = ms.empty() ? 0. : ms.front();
+    v[4] = ms.empty() ? 0. : ms.back();
+    used = 0;
+    return 0;
+}
+
+}  // namespace
+
+// the batched launches' own durations (their dispatch timestamps) since the last call: out[0..5) = the anneal's
+// sum (ms), launches, median, minimum, maximum (ms); out[5..11) = wall time (ms) of the last run's stages: anneal,
+// pre-record MD, QT pump, recorded MD, autocorrelations, the rest; out[11..16) and out[16..21) = the five figures
+// of the batched force and velocity-Verlet launches (md_batch 1).  Fills what n holds (n >= 3); resets the lists
 extern "C" int mdmc_ensemble_kernel_times(mdmc_ensemble* e, double* out, int n) {
     if (!e || !out) return set_error("mdmc_ensemble_kernel_times: NULL argument");
     if (n < 3) return set_error("mdmc_ensemble_kernel_times: need at least 3 doubles");
     HIPCHK(hipSetDevice(e->dev));
     HIPCHK(hipStreamSynchronize(e->stream));
-    std::vector<double> ms;
-    double tot = 0.;
-    for (int i = 0; i + 1 < e->evused; i += 2) {
-        float x = 0.f;
-        HIPCHK(hipEventElapsedTime(&x, e->evpool[i], e->evpool[i + 1]));
-        ms.push_back(x);
-        tot += x;
-    }
-    std::sort(ms.begin(), ms.end());
-    double v[5 + mdmc_ensemble::kStages] = {tot, (double)ms.size(), ms.empty() ? 0. : ms[ms.size() / 2],
-                                            ms.empty() ? 0. : ms.front(), ms.empty() ? 0. : ms.back()};
+    constexpr int kOut = 5 + mdmc_ensemble::kStages + 10;
+    double v[kOut] = {};
+    if (launch_stats(e->evpool, e->evused, v) || launch_stats(e->evForce, e->usedForce, v + 5 + mdmc_ensemble::kStages) ||
+        launch_stats(e->evVV, e->usedVV, v + 10 + mdmc_ensemble::kStages))
+        return -1;
     std::copy(e->stage_ms, e->stage_ms + mdmc_ensemble::kStages, v + 5);
-    for (int i = 0; i < n && i < 5 + mdmc_ensemble::kStages; ++i) out[i] = v[i];
-    e->evused = 0;
+    for (int i = 0; i < n && i < kOut; ++i) out[i] = v[i];
     return 0;
 }

@@ -7,6 +7,7 @@
 // Built with -ffp-contract=off and no fast-math: expressions keep the reference's operation
 // order, so the only device/host differences left are libm ulps (exp) and reduction orders.
 #include "mdqt_internal.hpp"
+#include "mdmc_device.hpp"   // the bodies shared with the ensemble's batched kernels
 
 #include <math.h>
 
@@ -44,10 +45,6 @@ __device__ __forceinline__ double mic_div(double d, double L) { return d - L * r
 __device__ __forceinline__ double mc_uij(double r, double kappa, double rCut) {                 // calcUIJ :153-159
     if (r < rCut) return exp(-1 * kappa * r) / r;
     return 0.;
-}
-__device__ __forceinline__ double wave_sum(double v) {      // butterfly: every lane holds the same sum
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
-    return v;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -417,87 +414,25 @@ __global__ __launch_bounds__(MCT) void k_monte_carlo_lds_ens(const MCArgs* __res
 }
 
 // ------------------------------------------------------------------------------------------
-// velocity Verlet (MDStep :504-511).  k_vv_positions is stepPositions :452-467 (R -> Rn).  After
-// the Newton-3 force kernel, k_vv_step sums the force slots (canonical order) into a(t + dt),
-// runs stepVelocities :469-502 (Verlet update + laser force) and pre-advances the positions of
-// the next MDStep, r + dt v + dt^2/2 a with the box wrap, into Rn: the same expression on the same
-// values stepPositions would read, so a step is two launches.  k_collide then overwrites the
-// collided particles of the step from the host-drawn list (and redoes their Rn).
+// velocity Verlet (MDStep :504-511): k_vv_positions is stepPositions :452-467 (R -> Rn); after the
+// Newton-3 force kernel, k_vv_step sums the force slots into a(t + dt), runs stepVelocities
+// :469-502 and pre-advances the positions of the next MDStep into Rn, so a step is two launches;
+// k_collide then overwrites the collided particles of the step.  The bodies are mdmc_device.hpp's,
+// shared with the batched kernels of an ensemble (mdmc_ensemble_kernels.hip).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double step_pos(double r, double v, double a, double dt, double L) {   // :455-464
-    r = r + dt * v + dt * dt / 2 * a;
-    if (r < 0) r += L;
-    if (r > L) r -= L;
-    return r;
-}
-
 __global__ __launch_bounds__(256) void k_vv_positions(const double* __restrict__ R, const double* __restrict__ V,
                                                       const double* __restrict__ A, double* __restrict__ Rn,
                                                       int N, int S, double dt, double L) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const size_t k = (size_t)c * S + i;
-        Rn[k] = step_pos(R[k], V[k], A[k], dt, L);
-    }
+    vv_positions_body(R, V, A, Rn, N, S, dt, L, blockIdx.x);
 }
 
-__device__ __forceinline__ void laser_kick(const VVArgs& a, double* v) {      // :488-498
-    if (a.oneAxis) {
-        v[0] += v[0] * a.dt * 1.234 * a.p6 * a.beta / a.sqrtn;
-    } else {
-        v[0] += v[0] * a.dt * 1.234 * a.p6 * a.beta / a.sqrtn / 2;
-        v[1] += v[1] * a.dt * 1.234 * a.p6 * a.beta / a.sqrtn / 4 * (-1);
-        v[2] += v[2] * a.dt * 1.234 * a.p6 * a.beta / a.sqrtn / 4 * (-1);
-    }
-}
-
-__device__ __forceinline__ double laser_term(const VVArgs& a, int c, double v) {   // :488-498, component c
-    if (a.oneAxis) return c == 0 ? v + v * a.dt * 1.234 * a.p6 * a.beta / a.sqrtn : v;
-    if (c == 0) return v + v * a.dt * 1.234 * a.p6 * a.beta / a.sqrtn / 2;
-    return v + v * a.dt * 1.234 * a.p6 * a.beta / a.sqrtn / 4 * (-1);
-}
-
-// workgroup = 64 particles x one component; wave q sums the slots q, q + 8, q + 16, ... of its
-// 64 particles (coalesced rows) = seg_sum's accumulator a[q], and wave 0 combines the eight in
-// seg_sum's tree: bit-identical to seg_sum, with 8x the loads in flight
 __global__ __launch_bounds__(512) void k_vv_step(VVArgs a) {
     __shared__ double acc[8][64];
-    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + lane;
-    const int c = blockIdx.y;
-    const size_t k = (size_t)c * a.S + i;
-    const size_t stride = (size_t)3 * a.S;
-    double sq = 0.;
-    if (i < a.N)
-        for (int sl = q; sl < a.nslots; sl += 8) sq += a.slots[(size_t)sl * stride + k];
-    acc[q][lane] = sq;
-    __syncthreads();
-    if (q != 0 || i >= a.N) return;
-    const double an = ((acc[0][lane] + acc[1][lane]) + (acc[2][lane] + acc[3][lane])) +
-                      ((acc[4][lane] + acc[5][lane]) + (acc[6][lane] + acc[7][lane]));
-    double v = a.V[k] + a.dt / 2 * (a.A[k] + an);                    // :484-486 (oldA + A)
-    if (a.laser) v = laser_term(a, c, v);
-    a.V[k] = v;
-    a.A[k] = an;
-    a.Rn[k] = step_pos(a.R[k], v, an, a.dt, a.L);
+    vv_step_body(a, blockIdx.x, blockIdx.y, acc);
 }
 
-// the collided particles of the step (:477-482): V = the host-drawn Maxwellian, then the laser term
 __global__ __launch_bounds__(64) void k_collide(VVArgs a) {
-    const int h = blockIdx.x * 64 + threadIdx.x;
-    if (h >= a.nhits) return;
-    const double* e = a.hits + 4 * (size_t)h;
-    const int i = (int)e[0];
-    double v[3] = {e[1], e[2], e[3]};
-    if (a.laser) laser_kick(a, v);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const size_t k = (size_t)c * a.S + i;
-        a.V[k] = v[c];
-        a.Rn[k] = step_pos(a.R[k], v[c], a.A[k], a.dt, a.L);
-    }
+    collide_body(a, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -589,65 +524,23 @@ __global__ __launch_bounds__(256) void k_autocorr_reduce(const double* __restric
 
 // ------------------------------------------------------------------------------------------
 // block reductions of the per-step observables: temperatures (:525-546, :560-581) and the
-// tagged-particle moments (:937-971); one workgroup, fixed order
+// tagged-particle moments (:937-971); one workgroup, fixed order (bodies: mdmc_device.hpp)
 // ------------------------------------------------------------------------------------------
-constexpr int RBT = 1024;
-
 __global__ __launch_bounds__(RBT) void k_temperatures(const double* __restrict__ V, int N, int S, double* __restrict__ out) {
     __shared__ double sp[4][RBT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    double a = 0., x = 0., y = 0., z = 0.;
-    for (int i = tid; i < N; i += RBT) {
-        const double vx = V[i], vy = V[S + i], vz = V[2 * S + i];
-        a = a + vx * vx; a = a + vy * vy; a = a + vz * vz;
-        x = x + vx * vx; y = y + vy * vy; z = z + vz * vz;
-    }
-    a = wave_sum(a); x = wave_sum(x); y = wave_sum(y); z = wave_sum(z);
-    if (lane == 0) { sp[0][w] = a; sp[1][w] = x; sp[2][w] = y; sp[3][w] = z; }
-    __syncthreads();
-    if (tid < 4) {
-        double s = 0.;
-        for (int q = 0; q < RBT / 64; ++q) s = s + sp[tid][q];
-        out[tid] = s;
-    }
+    temperatures_body(V, N, S, out, sp);
 }
 
 __global__ __launch_bounds__(RBT) void k_tag_moments(const double* __restrict__ V, const int* __restrict__ tags, int N,
                                                      double* __restrict__ out) {
     __shared__ double sp[kTagMomentSums][RBT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    double m[kTagMomentSums];
-#pragma unroll
-    for (int q = 0; q < kTagMomentSums; ++q) m[q] = 0.;
-    for (int i = tid; i < N; i += RBT) {
-        const double v = V[i];
-        const double v2 = v * v, v3 = v * v * v, v4 = v * v * v * v;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            if (tags[(size_t)t * N + i]) {
-                m[5 * t] += v; m[5 * t + 1] += v2; m[5 * t + 2] += v3; m[5 * t + 3] += v4; m[5 * t + 4] += 1.;
-            }
-    }
-#pragma unroll
-    for (int q = 0; q < kTagMomentSums; ++q) {
-        const double s = wave_sum(m[q]);
-        if (lane == 0) sp[q][w] = s;
-    }
-    __syncthreads();
-    if (tid < kTagMomentSums) {
-        double s = 0.;
-        for (int q = 0; q < RBT / 64; ++q) s = s + sp[tid][q];
-        out[tid] = s;
-    }
+    tag_moments_body(V, tags, N, out, sp);
 }
 
 // recordVelsForAutocorrelations (:513-523): vStore[c][i][t] = V[c][i]
 __global__ __launch_bounds__(256) void k_store_velocities(const double* __restrict__ V, int N, int S, int T, int t,
                                                           double* __restrict__ vs) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) vs[((size_t)c * N + i) * T + t] = V[(size_t)c * S + i];
+    store_velocities_body(V, N, S, T, t, vs, blockIdx.x);
 }
 
 // anisotropizeVelocities (:548-558)

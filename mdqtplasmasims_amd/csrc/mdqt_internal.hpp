@@ -529,6 +529,26 @@ constexpr int kTagMomentSums = 20;
 hipError_t launch_tag_moments(const double* V, const int* tags, int N, double* out, hipStream_t s);
 hipError_t launch_anisotropize(double* V, int N, int S, double tpd, hipStream_t s);
 hipError_t launch_store_velocities(const double* V, int N, int S, int T, int t, double* vs, hipStream_t s);
+// The MD stages of an ensemble of MC + MD jobs in batched launches (mdmc_ensemble_kernels.hip): `jobs` = device
+// array of the members' argument blocks, one launch for all njobs.  Forces: variant 2 or 0, never guarded;
+// ev0 / ev1 (or null) take the force and velocity-Verlet launches' own timestamps.  The collision scatter is a
+// launch of its own, only when a member has a hit (max_nhits > 0).
+struct MDObsArgs {      // a member's per-step observables: row k of temp / mom, column t of vs
+    const double* V;
+    const int* tags;    // [4][N]
+    int N, S, T;
+    double* temp;       // [steps][4]
+    double* mom;        // [steps][kTagMomentSums]
+    double* vs;         // [3][N][T]
+};
+hipError_t launch_forces_n3_mdmc_ens(const N3Args* jobs, int njobs, int max_npairs, int variant, hipStream_t s,
+                                     hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t launch_vv_step_ens(const VVArgs* jobs, int njobs, int max_N, hipStream_t s, hipEvent_t ev0 = nullptr,
+                              hipEvent_t ev1 = nullptr);
+hipError_t launch_collide_ens(const VVArgs* jobs, int njobs, int max_nhits, hipStream_t s);
+hipError_t launch_temperatures_ens(const MDObsArgs* jobs, int njobs, int k, hipStream_t s);
+hipError_t launch_tag_moments_ens(const MDObsArgs* jobs, int njobs, int k, hipStream_t s);
+hipError_t launch_store_velocities_ens(const MDObsArgs* jobs, int njobs, int max_N, int t, hipStream_t s);
 // error message of the C ABI (mdqt_last_error), shared by the mdmc_* and mdlc_* entry points
 int set_error(const char* fmt, ...);
 // the reference's "(unsigned)(x)" printed with %d (x86-64 runtime behaviour):

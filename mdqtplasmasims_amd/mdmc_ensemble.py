@@ -3,8 +3,10 @@
 The reference runs its MC + MD programs as a Slurm array of independent jobs (exampleSlurmFile.slurm:3,16,
 ``srun tagQuad $SLURM_ARRAY_TASK_ID``).  :class:`MonteCarloEnsemble` owns ``njobs`` such jobs — job k has
 ``job + k`` and ``seed + k`` — anneals all their Metropolis chains with one launch (one workgroup per chain)
-and queues their MD steps on the members' own streams (include/mdmc.h, "ensembles").  Every job's state and
-files are bit for bit what :class:`~mdqtplasmasims_amd.mdmc.MonteCarloMD` gives for that job alone.
+and steps their MD either member by member on the members' own streams (``md_batch=0``, the default) or with one
+force launch and one velocity-Verlet launch per step for all jobs (``md_batch=1``; include/mdmc.h, "ensembles").
+Every job's state and files are bit for bit what :class:`~mdqtplasmasims_amd.mdmc.MonteCarloMD` gives for that
+job alone, in either mode.
 
     =================================  ================================  ============================
     reference (MCMD), per job          here, all jobs                    C ABI (include/mdmc.h)
@@ -49,13 +51,33 @@ class MonteCarloEnsemble:
 
     STAGES = ("anneal", "pre_record_md", "qt_pump", "recorded_md", "autocorrelations", "rest")
 
-    def __init__(self, njobs: int, **params):
+    def __init__(self, njobs: int, md_batch=None, **params):
         self.p = default_params(**params)
         h = C.c_void_p()
         check(lib().mdmc_ensemble_create(C.byref(self.p), int(njobs), C.byref(h)), "mdmc_ensemble_create")
         self.h = h
         self.jobs = [_Member(self, lib().mdmc_ensemble_job(h, k), mdmc_job_params(self.p, k))
                      for k in range(lib().mdmc_ensemble_size(h))]
+        if md_batch is not None:
+            self.md_batch = md_batch
+
+    # ---- how the MD stages are stepped: 0 member by member, 1 batched launches (the same bits) ----
+    @property
+    def md_batch(self) -> int:
+        mode = lib().mdmc_ensemble_md_batch(self.h)
+        if mode < 0:
+            check(mode, "mdmc_ensemble_md_batch")
+        return mode
+
+    @md_batch.setter
+    def md_batch(self, mode: int):
+        check(lib().mdmc_ensemble_set_md_batch(self.h, int(mode)), "mdmc_ensemble_set_md_batch")
+
+    def md_launches(self) -> int:
+        """kernel launches the batched MD path has issued since creation (md_batch 0 leaves it unchanged)"""
+        n = C.c_ulonglong(0)
+        check(lib().mdmc_ensemble_md_launches(self.h, C.byref(n)), "mdmc_ensemble_md_launches")
+        return int(n.value)
 
     # ---- lifecycle ----
     def close(self):
@@ -99,16 +121,20 @@ class MonteCarloEnsemble:
 
     # ---- timing ----
     def enable_timing(self, on: bool = True):
-        """record the anneal launches' dispatch timestamps, and time the stages of run()"""
+        """record the batched launches' dispatch timestamps, and time the stages of run()"""
         check(lib().mdmc_ensemble_enable_timing(self.h, 1 if on else 0))
 
     def kernel_times(self):
         """{anneal_ms, n_anneal, anneal_median_ms, anneal_min_ms, anneal_max_ms} of the batched launches since
-        the last call (synchronises and resets), and stage_ms: the wall time of the last run()'s stages"""
-        out = (C.c_double * 11)()
-        check(lib().mdmc_ensemble_kernel_times(self.h, out, 11), "mdmc_ensemble_kernel_times")
+        the last call (synchronises and resets), the same five as md_force_* and md_vv_* for the batched force
+        and velocity-Verlet launches (md_batch 1), and stage_ms: the wall time of the last run()'s stages"""
+        out = (C.c_double * 21)()
+        check(lib().mdmc_ensemble_kernel_times(self.h, out, 21), "mdmc_ensemble_kernel_times")
         d = {"anneal_ms": out[0], "n_anneal": int(out[1]), "anneal_median_ms": out[2], "anneal_min_ms": out[3],
              "anneal_max_ms": out[4]}
+        for i, k in ((11, "md_force"), (16, "md_vv")):
+            d.update({k + "_ms": out[i], "n_" + k: int(out[i + 1]), k + "_median_ms": out[i + 2],
+                      k + "_min_ms": out[i + 3], k + "_max_ms": out[i + 4]})
         d["stage_ms"] = {k: out[5 + i] for i, k in enumerate(self.STAGES)}
         return d
 

@@ -14,8 +14,15 @@
     python tools/mdmc_ensemble_rate.py e2e --bin A/bin/mdmc --seq-bin B/bin/mdmc --njobs 8 [--qt_model 2] [--runs 3]
         wall clock with process start of `mdmc 1 --njobs=J --seed=777 --quiet=1` (build A) against J sequential
         `mdmc k --seed=777+k-1 --quiet=1` (build B), and `diff -r` of the two trees; --no-seq: the ensemble only; --plain: build A without --njobs (J = 1)
-    python tools/mdmc_ensemble_rate.py stages --njobs 8 [--qt_model 2]
-        wall time by stage of one ensemble run (host timers around the stage helpers)
+    python tools/mdmc_ensemble_rate.py stages --njobs 8 [--qt_model 2] [--md_batch 1]
+        wall time by stage of one ensemble run (host timers around the stage helpers); with --md_batch 1 also the
+        batched force and velocity-Verlet launches' own time
+    python tools/mdmc_ensemble_rate.py md [--jobs 1,8,64] [--md_batch 0|1] [--steps 300]
+        the MD step of the ensemble (N = 4096, force_kernel 1, collisionless, after 2,000 Metropolis steps): wall us
+        per ensemble step of one md_steps(--steps) call after a warm-up call of 50; with --md_batch 1 also, from a
+        second call with timing on, the batched force and velocity-Verlet launches' own median (min-max) and the force launch's FP64 roof
+        fraction (30 flop x N(N-1)/2 per member against 78.6 TF).  Without --md_batch the switch is left alone
+        (MDQT_LIB naming a build that predates it).  e2e and stages take --md_batch too
 """
 import argparse
 import csv
@@ -88,6 +95,41 @@ def cmd_trace(a):
                                                us_per_step=statistics.median(ms) * 1e3 / STEPS)}))
 
 
+MD_N, MD_WARM, ROOF_TF = 4096, 50, 78.6
+
+
+def cmd_md(a):
+    import mdqtplasmasims_amd as M
+    from mdqtplasmasims_amd._lib import LIB_PATH
+    rows = []
+    for J in [int(x) for x in a.jobs.split(",")]:
+        with M.MonteCarloEnsemble(J, md_batch=a.md_batch, N=MD_N, force_kernel=1, collisionFreq=0, numVelAutoCorrsSteps=8,
+                                  seed=777, job=1) as e:
+            e.init()
+            e.monte_carlo(2000)
+            e.md_steps(MD_WARM)
+            t0 = time.perf_counter()
+            e.md_steps(a.steps)                          # the wall window: timing off, no events on the launches
+            wall = time.perf_counter() - t0
+            r = dict(J=J, md_batch=a.md_batch, steps=a.steps, us_per_step=wall * 1e6 / a.steps,
+                     us_per_member_step=wall * 1e6 / a.steps / J)
+            if a.md_batch == 1:                          # a second window for the launches' own timestamps
+                e.enable_timing(True)
+                e.md_steps(a.steps)
+            if a.md_batch == 1:
+                t = e.kernel_times()
+                assert t["n_md_force"] == a.steps and t["n_md_vv"] == a.steps, t
+                flop = 30. * MD_N * (MD_N - 1) / 2 * J
+                r.update(force_us=[t["md_force_median_ms"] * 1e3, t["md_force_min_ms"] * 1e3, t["md_force_max_ms"] * 1e3],
+                         vv_us=[t["md_vv_median_ms"] * 1e3, t["md_vv_min_ms"] * 1e3, t["md_vv_max_ms"] * 1e3],
+                         force_roof=flop / (t["md_force_median_ms"] * 1e-3) / (ROOF_TF * 1e12))
+        rows.append(r)
+        print("J = {J:3d} md_batch {md_batch}: {us_per_step:9.1f} us / ensemble step  {us_per_member_step:7.2f} us / member-step".format(**r)
+              + ("  force {0[0]:.1f} ({0[1]:.1f}-{0[2]:.1f}) us  vv {1[0]:.1f} ({1[1]:.1f}-{1[2]:.1f}) us  roof {2:.3f}".format(
+                  r["force_us"], r["vv_us"], r["force_roof"]) if a.md_batch == 1 else ""))
+    print(json.dumps({"md": dict(lib=LIB_PATH, rows=rows)}))
+
+
 def timed(cmd, limit):
     t0 = time.perf_counter()
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
@@ -98,13 +140,14 @@ def timed(cmd, limit):
 
 def cmd_e2e(a):
     more = [f"--qt_model={a.qt_model}"] if a.qt_model else []
+    batch = [f"--md_batch={a.md_batch}"] if a.md_batch is not None and not a.plain else []
     work = tempfile.mkdtemp(prefix="mdmc_e2e_")
-    res = dict(njobs=a.njobs, qt_model=a.qt_model, ens_s=[], seq_s=[])
+    res = dict(bin=a.bin, njobs=a.njobs, qt_model=a.qt_model, md_batch=a.md_batch, ens_s=[], seq_s=[])
     try:
         for _ in range(a.runs):
             shutil.rmtree(work + "/ens", ignore_errors=True)
             res["ens_s"].append(timed([a.bin, "1"] + ([] if a.plain else [f"--njobs={a.njobs}"]) + ["--seed=777", "--quiet=1",
-                                       f"--saveDirectory={work}/ens/"] + more, a.limit))
+                                       f"--saveDirectory={work}/ens/"] + more + batch, a.limit))
         for _ in range(0 if a.no_seq else a.runs):
             shutil.rmtree(work + "/seq", ignore_errors=True)
             tot = 0.
@@ -127,7 +170,7 @@ def cmd_stages(a):
     work = tempfile.mkdtemp(prefix="mdmc_stages_")
     try:
         kw = dict(qt_model=a.qt_model) if a.qt_model else {}
-        with M.MonteCarloEnsemble(a.njobs, seed=777, job=1, saveDirectory=work + "/", **kw) as e:
+        with M.MonteCarloEnsemble(a.njobs, md_batch=a.md_batch, seed=777, job=1, saveDirectory=work + "/", **kw) as e:
             e.enable_timing(True)
             t0 = time.perf_counter()
             e.run()
@@ -135,8 +178,12 @@ def cmd_stages(a):
             t = e.kernel_times()
     finally:
         shutil.rmtree(work, ignore_errors=True)
-    print(json.dumps({"stages": dict(njobs=a.njobs, qt_model=a.qt_model, run_s=wall, stage_ms=t["stage_ms"],
-                                     anneal_launch_ms=t["anneal_ms"], n_anneal=t["n_anneal"])}))
+    res = dict(njobs=a.njobs, qt_model=a.qt_model, md_batch=a.md_batch, run_s=wall, stage_ms=t["stage_ms"],
+               anneal_launch_ms=t["anneal_ms"], n_anneal=t["n_anneal"])
+    if a.md_batch == 1:
+        res.update(md_force_ms=t["md_force_ms"], n_md_force=t["n_md_force"], md_force_median_us=t["md_force_median_ms"] * 1e3,
+                   md_vv_ms=t["md_vv_ms"], n_md_vv=t["n_md_vv"], md_vv_median_us=t["md_vv_median_ms"] * 1e3)
+    print(json.dumps({"stages": res}))
 
 
 def main():
@@ -149,10 +196,13 @@ def main():
     p.add_argument("--bin", required=True); p.add_argument("--seq-bin"); p.add_argument("--njobs", type=int, default=8)
     p.add_argument("--qt_model", type=int, default=0); p.add_argument("--runs", type=int, default=3)
     p.add_argument("--no-seq", action="store_true"); p.add_argument("--plain", action="store_true")
-    p.add_argument("--limit", type=float, default=300.)
+    p.add_argument("--limit", type=float, default=300.); p.add_argument("--md_batch", type=int, choices=[0, 1])
     p.set_defaults(f=cmd_e2e)
     p = sub.add_parser("stages"); p.add_argument("--njobs", type=int, default=8)
-    p.add_argument("--qt_model", type=int, default=0); p.set_defaults(f=cmd_stages)
+    p.add_argument("--qt_model", type=int, default=0); p.add_argument("--md_batch", type=int, choices=[0, 1])
+    p.set_defaults(f=cmd_stages)
+    p = sub.add_parser("md"); p.add_argument("--jobs", default="1,8,64"); p.add_argument("--md_batch", type=int, choices=[0, 1])
+    p.add_argument("--steps", type=int, default=300); p.set_defaults(f=cmd_md)
     a = ap.parse_args()
     a.f(a)
 
