@@ -135,7 +135,7 @@ struct mdqt_ctx {
     double* dRs = nullptr;         // [3][Npad] positions in sorted order
     double* dBoxes = nullptr;      // [12][T] tile boxes, raw coordinate bounds
     double* dSubBoxes = nullptr;   // [6][4T] the 16-ion sub-tiles' boxes (the block kernel's sub-tile groups)
-    uint2* dPlan = nullptr;        // [(Phi - Plo) nd][256] the block kernel's tile-pair words (k_n3b_plan)
+    uint2* dPlan = nullptr;        // [(Phi - Plo) nd][kN3BBlock^2] the block kernel's tile-pair words (k_n3b_plan)
     int tmask_mode = 1;            // option force_reduce_mask: k_n3b_reduce reads only the j-slots written
     int balance_opt = 1;           // option force_balance: sharded block ranges by census weight (1) or count (0)
     bool balanced = false;         // the block ranges of this N have been weighted (n3b_balance)

@@ -1,5 +1,5 @@
-// The host model of the Newton-3 block scheme (mdqt_forces.hip k_pairs_n3b and its plan): the error-bounded
-// tail and tier radii, their measurement and enforcement, the block kernel's arguments, the ranks' block
+// The host model of the Newton-3 block scheme (mdqt_n3b.hip k_pairs_n3b; its plan: mdqt_n3b_plan.hip): the
+// error-bounded tail and tier radii, their measurement and enforcement, the block kernel's arguments, the ranks' block
 // ranges by work, and the census queries.  Host arithmetic only; the launches are mdqt_step.cpp's.
 
 #include <math.h>
@@ -356,7 +356,7 @@ int mdqt::n3b_args(mdqt_ctx* s, N3BArgs& a) {
         // the per-sub-tile sums: where the tail skips pairs, or (force_form_mode 1) a tier is evaluated
         const bool tiers = a.formm && (a.Rmid < a.Rskip || a.Rfar < a.Rskip || a.Rvfar < a.Rskip || a.Rufar < a.Rskip);
         if ((tail_measured(s) && a.Rskip < a.Rcut) || tiers) a.tailb = s->dTail;
-        // the plan (k_n3b_plan): 256 tile-pair words per (P, db), then one J-step mask per (P, db)
+        // the plan (k_n3b_plan): kN3BBlock^2 tile-pair words per (P, db), then one J-step mask per (P, db)
         // and the per-J-tile masks of the block distances whose j-slots the block kernel writes (k_n3b_reduce
         // reads only those): T x ceil(nd / 64) words
         const size_t nplan = (size_t)std::max(a.Phi - a.Plo, 0) * a.nd * (kN3BBlock * kN3BBlock + 1);

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #if defined(__HIP__)
 #include <hip/hip_ext.h>
+#include <type_traits>
 #endif
 #include <stdint.h>
 
@@ -394,7 +395,7 @@ struct N3Args {
                                   // write-through slot stores — T per tile per launch; nullptr = off
 };
 
-// Newton-3 over block pairs (mdqt_forces.hip k_pairs_n3b): blocks of 16 tiles, cyclic half
+// Newton-3 over block pairs (mdqt_n3b.hip k_pairs_n3b): blocks of kN3BBlock tiles, cyclic half
 // shell of block distances, slots [nd + R][3][Npad] (j-slots by distance, i-slots by run).
 // A rank runs the workgroups of blocks [Plo, Phi); k_n3b_reduce sums the slots it wrote.
 struct N3BArgs {
@@ -437,7 +438,7 @@ struct N3BArgs {
                         // pair of it is closer (its boxes' far distance in the minimum image, sub_far2), so
                         // the f32 r^2 never decides the cutoff (no a-priori cutoff term)
     const double* subboxes;   // [6][4T]: the 16-ion sub-tiles' centers and half extents (use_sort)
-    uint2* plan;        // force calls in spatial order: [(Phi - Plo) nd][256] tile-pair words, then
+    uint2* plan;        // force calls in spatial order: [(Phi - Plo) nd][kN3BBlock^2] tile-pair words, then
                         // [(Phi - Plo) nd] J-step masks (.x), written by k_n3b_plan (launch_forces_n3b)
                         // and read by k_pairs_n3b; nullptr: classified in the block kernel (every
                         // sub-tile group exact; no tail sums)
@@ -463,7 +464,7 @@ size_t spatial_order_tmp_bytes(int N);
 // block kernel and after the slot reduction
 hipError_t launch_forces_n3b(const N3BArgs& a, int variant, double* out, hipStream_t s, hipEvent_t ev0 = nullptr,
                              hipEvent_t ev1 = nullptr, hipEvent_t* marks = nullptr);
-// force_tail_mode 1 (mdqt_forces.hip): the per-sub-tile tail sums [4T] against eps — st[0] running
+// force_tail_mode 1 (mdqt_n3b_plan.hip): the per-sub-tile tail sums [4T] against eps — st[0] running
 // max of the tiles within eps, st[1] of all, st[2] tiles over eps (cumulative), st[3] this call's
 // list length, st[4] measured calls — and the exact recomputation of the listed tiles' forces,
 // written into `out` ([world][3][S], by ion) on the rank that owns the tile (0 on the others); pot: their
@@ -471,7 +472,7 @@ hipError_t launch_forces_n3b(const N3BArgs& a, int variant, double* out, hipStre
 hipError_t launch_tail_max(const double* tailb, int T, double eps, unsigned long long* st, int* list, hipStream_t s);
 hipError_t launch_tail_fix(const N3BArgs& a, const unsigned long long* st, const int* list, double* out,
                            hipStream_t s, bool pot = false);
-// census of k_pairs_n3b's work by tile-pair class (mdqt_forces.hip k_n3b_census): out[2 kCensus]
+// census of k_pairs_n3b's work by tile-pair class (mdqt_n3b_plan.hip k_n3b_census): out[2 kCensus]
 constexpr int kCensus = 15;                 // (round 6: + 14 ufar_image)
 // tiles per block of the Newton-3 block kernel (= its waves per workgroup): 8 (round 4, A/B vs 16:
 // C3 -2.7 %, C5 -2.5 %, N = 1M -4.3 % per force call — three 8-wave workgroups per CU at 80 VGPRs
@@ -609,7 +610,7 @@ struct D48Args {
 };
 hipError_t launch_d48_resolve(const D48Args& a, hipStream_t s);
 
-// ---- launchers (mdqt_kernels.hip) ----
+// ---- launchers (mdqt_kernels.hip; the force kernels': mdqt_forces.hip, mdqt_n3b.hip) ----
 hipError_t launch_forces(const ForceArgs& a, hipStream_t s);
 hipError_t launch_forces_n3(const N3Args& a, int variant, hipStream_t s, hipEvent_t ev0 = nullptr,
                             hipEvent_t ev1 = nullptr);
@@ -638,6 +639,21 @@ inline void launch_timed(F kernel, dim3 grid, dim3 block, hipStream_t s, hipEven
                          Args... args) {
     if (ev0) hipExtLaunchKernelGGL(kernel, grid, block, 0, s, ev0, ev1, 0, args...);
     else hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+}
+// The (variant, guard) ladder of the force kernels' launchers: calls f(V, G) with the force variant
+// (0 .. NVAR - 1; one out of range goes to 0, as the ladders did) and the guard flag as
+// std::integral_constant values, so that f names its kernel as k<decltype(V)::value, decltype(G)::value>
+template <int NVAR, typename F>
+inline void by_variant_guard(int variant, bool guard, F&& f) {
+    auto g = [&](auto v) {
+        if (guard) f(v, std::true_type{});
+        else f(v, std::false_type{});
+    };
+    if constexpr (NVAR > 2) {
+        if (variant == 2) return g(std::integral_constant<int, 2>{});
+    }
+    if (variant == 1) g(std::integral_constant<int, 1>{});
+    else g(std::integral_constant<int, 0>{});
 }
 #endif
 

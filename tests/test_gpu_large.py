@@ -184,7 +184,7 @@ def test_spatial_order_tile_skipping_is_exact(orc):
 
 @pytest.mark.gpu
 def test_one_axis_image_instance_matches_per_pair_image():
-    """force_ax1 (mdqt_forces.hip n3b_pack_class, launch_forces_n3b): a tile pair whose minimum image
+    """force_ax1 (mdqt_n3b.hpp n3b_pack_class, mdqt_n3b.hip launch_forces_n3b): a tile pair whose minimum image
     varies on one axis only takes the image per pair on that axis alone and the other two axes'
     multiples once per tile pair, as a uniform-image tile pair does — the same pair terms (SpeedUp:
     218-224), the shifted axes rounded as in the uniform-image tile pairs.  At C3 (skip radius L/2,

@@ -125,7 +125,7 @@ def test_newton3_tiles_ragged_sizes(eng, orc, N0):
 
 @pytest.mark.parametrize("N0", [200, 1100, 2500, 5000])
 def test_newton3_blocks_sizes(eng, orc, N0):
-    """Newton-3 block pairs (half shell of 16-tile blocks): one block, even and odd block counts,
+    """Newton-3 block pairs (half shell of 8-tile blocks, kN3BBlock): one block, even and odd block counts,
     ragged last tile; then two MD steps"""
     s, o = pair(eng, orc, N0=N0, seed=23)
     s.set_option("force_scheme", 3)
@@ -137,6 +137,75 @@ def test_newton3_blocks_sizes(eng, orc, N0):
     s2.md_steps(2)
     o.md_steps(2)
     assert np.abs(s2.get_state()["V"] - o.get_state()["V"]).max() < 1e-10
+
+
+_BLOCKS_REF = {}
+
+
+def blocks_ref(eng, orc, N0):
+    """the init() state of N0 and the oracle's forces and compensated potential rows on it: computed once
+    per size, shared by the cases of test_newton3_blocks_instances, read-only"""
+    if N0 not in _BLOCKS_REF:
+        s, o = pair(eng, orc, N0=N0, seed=23)
+        o.forces()
+        st = o.get_state()
+        L, lDeb = s.const("L"), s.const("lDeb")
+        s.close()
+        ref = {"G": st["F"], "U": orc.potentials_index(st["R"], np.arange(st["R"].shape[1]), L, lDeb), "lDeb": lDeb}
+        for v in ref.values():
+            if isinstance(v, np.ndarray):
+                v.flags.writeable = False
+        _BLOCKS_REF[N0] = ref
+    return _BLOCKS_REF[N0]
+
+
+@pytest.mark.parametrize("ax1", [0, 1])
+@pytest.mark.parametrize("pairs", [0, 1])
+@pytest.mark.parametrize("N0", [1000, 1100])
+def test_newton3_blocks_instances(eng, orc, N0, pairs, ax1):
+    """the block kernels' instances that the defaults do not reach at a small size (mdqt_n3b.hip n3b_kernel):
+    the 8-wave kernel (force_n3b_pairs 0), the instances without the one-axis image (force_ax1 0; at these
+    sizes force_ax1 1 takes the AXP ones), the unsorted order and the sorted one without skipping (force_sort
+    0, 2), the potential without a plan (potential_plan 0) — every combination, at an even and an odd block
+    count (N0 = 1000: the half-covered block distance; 1100: a last block of one or two tiles), ragged last tile.
+    Forces at test_forces_match_oracle_after_init's gates, potential rows and Epot at
+    test_gpu_large.py test_epotential_on_the_plan's (all ions instead of a sample); force_sort 1 and 2 agree
+    bit for bit, as test_spatial_order_tile_skipping_is_exact asserts at C3"""
+    ref = blocks_ref(eng, orc, N0)
+    G, UG, lDeb = ref["G"], ref["U"], ref["lDeb"]
+    s = eng.Simulation(N0=N0, seed=23, rng_mode=1).init()
+    N = s.N
+    for k, v in (("force_scheme", 3), ("force_n3b_pairs", pairs), ("force_ax1", ax1)):
+        s.set_option(k, v)
+        assert s.const(k) == v
+    assert s.const("potential_n3") == 1
+    F = {}
+    for sort in (0, 1, 2):
+        s.set_option("force_sort", sort)
+        assert s.const("force_sort") == sort
+        bounds = sum(s.const(k) for k in ("force_mid_bound", "force_far_bound", "force_vfar_bound", "force_ufar_bound"))
+        gate = lDeb * max(1e-12 + bounds, s.const("force_error_eps")) + 1e-13 * np.abs(UG).max()
+        s.forces()
+        F[sort] = s.get_state()["F"]
+        err = rel(F[sort], G)
+        mom = np.abs(F[sort].sum(axis=1)).max() / (np.abs(F[sort]).sum() / N)
+        U, e = {}, {}
+        for plan in (1, 0):
+            s.set_option("potential_plan", plan)
+            U[plan], e[plan] = s.potential_rows(), s.Epotential()
+        d1, d0 = np.abs(U[1] - UG).max(), np.abs(U[0] - UG).max()
+        erel = abs(e[1] - e[0]) / abs(e[0])
+        print(f"N0={N0} N={N} pairs={pairs} ax1={ax1} sort={sort}: rel F {err:.3e}, |sum F|/mean|F| {mom:.3e}; "
+              f"max|dU| plan {d1:.3e} (gate {gate:.3e}) exact {d0:.3e}; Epot plan vs exact rel {erel:.2e}")
+        assert err < 1e-13
+        assert mom < 1e-11
+        assert d0 <= 1e-12 * np.abs(UG).max()
+        assert d1 <= gate
+        assert np.abs(U[1] - U[0]).max() <= gate + 1e-13 * np.abs(U[0]).max()
+        assert erel <= 1e-12
+        assert abs(e[1] - U[1].sum() / 2 / N) <= 1e-12 * abs(e[1])
+    assert np.array_equal(F[1], F[2])
+    s.close()
 
 
 @pytest.mark.parametrize("world,N0", [(2, 5000), (3, 5000), (2, 400), (3, 700)])

@@ -5,7 +5,7 @@ checked on the CPU — no GPU needed:
     [Plo, Phi) and over workgroups by runs of distances, evaluates every distinct tile pair exactly
     once, for world sizes 1-8 and even / odd block counts.  `n3b_plan` restates
     mdqt_engine.cpp:choose_segments and `n3b_tile_pairs` the loops of
-    mdqt_forces.hip:k_pairs_n3b (the same arithmetic, so a change there must be mirrored here);
+    mdqt_n3b.hip:k_pairs_n3b (the same arithmetic, so a change there must be mirrored here);
   * forces: a world-2 gloo group where each rank evaluates its tile pairs into a dense partial
     force array, the partials are summed across ranks (the reduce-scatter step; gloo all-reduce,
     then every rank keeps its slab) and compared with the oracle's full forces() within 1e-13.
@@ -43,7 +43,7 @@ def n3b_plan(N, world, rank, BW=8, target=65536, cuts=None):
 
 
 def n3b_tile_pairs(N, world, rank, BW=8, cuts=None):
-    """(I, J, diag) of every tile pair rank `rank` evaluates: mdqt_forces.hip:k_pairs_n3b's loops
+    """(I, J, diag) of every tile pair rank `rank` evaluates: mdqt_n3b.hip:k_pairs_n3b's loops
     over workgroups (block P, run), distances db of the run, J tiles of block Q = P + db, waves I"""
     p = n3b_plan(N, world, rank, BW, cuts=cuts)
     T, NB, nd = p["T"], p["NB"], p["nd"]
@@ -120,7 +120,7 @@ def test_block_ownership_covers_every_tile_pair_once(N, BW):
 
 
 def test_block_ownership_at_the_reference_sizes():
-    """block level at C3 / C5 / N = 1M with the kernel's 16-tile blocks: every unordered block pair
+    """block level at C3 / C5 / N = 1M with the kernel's 8-tile blocks (BW): every unordered block pair
     (and every block with itself) is owned by exactly one rank, world sizes 1-8"""
     for N in (99882, 249970, 1000258):
         for world in range(1, 9):
@@ -215,7 +215,7 @@ def test_block_partials_reduce_to_the_oracle_forces_gloo_world2(orc):
 # ---------------------------------------------------------------------------------------------
 # k_n3b_plan's pairing word (round 6): the lane-parallel form — each of lanes 0..BW-1 counts the tiles
 # ahead of its own (strictly more work, or equal work and a lower tile) and writes its 3-bit field —
-# against the serial stable insertion sort it replaced (mdqt_forces.hip k_n3b_plan)
+# against the serial stable insertion sort it replaced (mdqt_n3b_plan.hip k_n3b_plan)
 # ---------------------------------------------------------------------------------------------
 def _pairing_serial(row):
     BW = len(row)
