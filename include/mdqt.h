@@ -191,6 +191,10 @@ int         mdqt_tag_spin_up(mdqt_ctx* c, int* tags, int* n_up);
  * and the tags draw from the Philox stream (the reference's shared drand48 is racy).
  * world_size 1. */
 int         mdqt_run_pump(mdqt_ctx* c);
+/* n x (step(); c0++) of the pumping programs (step() :377-394: half drift, forces at the half-drifted
+ * positions, kick, half drift; at t == 0 forces() first and the DT^2 F term) at the context's t, which
+ * stays — mdqt_run_pump's MD step, for stepwise use.  world_size 1. */
+int         mdqt_pump_md_steps(mdqt_ctx* c, int n);
 /* the spin-up list of the pumping run (N ints; 0 before measureSpinUps) */
 int         mdqt_get_spin_up_list(mdqt_ctx* c, int* tags, int* n_up);
 
@@ -417,6 +421,43 @@ int         mdqt_ensemble_synchronize(mdqt_ensemble* e);       /* + the range fl
  * QT launch ms — since the last call; synchronises and resets.  Replaces no reference function */
 int         mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on);
 int         mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n);
+
+/* ---- ensembles of the optical-pumping programs ----
+ * J independent jobs of randomFrozenStartTag408Linear.cpp / 408Quad / 422Linear (qt_model 1-3) on one device,
+ * stepped in batched launches: job k has job = p.job + k and seed = p.seed + k (mdqt_ensemble_job_params), and
+ * every member's state and files are bit for bit / byte for byte those of the job run alone
+ * (mdqt_run_pump with those parameters): the batched kernels run the single-job kernels' bodies on each
+ * member's own arguments, tile-pair table and slots.  At t > 0 an MD step of all members is two launches —
+ * the batched force launch, then the slot sum, kick and half drift with the next step's leading half drift
+ * folded in where nothing reads R, V or F in between; the pump window's qsteps are one launch per <= 32.
+ * Limits: qt_model 1-3, world_size 1, rng_mode 1, 1 <= njobs <= 1024, qt_math 2, the lane QT kernel, every
+ * member on the Newton-3 tiles or the small-N rows (N <= 65,536); a refusal names the parameter.  Members
+ * below 128 ions keep the owner-computes rows (their own small force launch inside the batched call) unless
+ * force_scheme 2 is set.  Lockstep: every batched call first checks that all members agree on t (bitwise),
+ * the qstep index, c0 and whether they are tagged, and fails naming the first job index that differs, before
+ * launching anything.  mdqt_ensemble_create and `mdqt --njobs` keep refusing the pump programs: this is the
+ * interface of its own. */
+typedef struct mdqt_pump_ensemble mdqt_pump_ensemble;
+int         mdqt_pump_ensemble_create(const mdqt_params* p, int njobs, mdqt_pump_ensemble** out);
+void        mdqt_pump_ensemble_destroy(mdqt_pump_ensemble* e);
+int         mdqt_pump_ensemble_size(const mdqt_pump_ensemble* e);
+mdqt_ctx*   mdqt_pump_ensemble_job(mdqt_pump_ensemble* e, int k);       /* job k's context, owned by the ensemble */
+int         mdqt_pump_ensemble_set_option(mdqt_pump_ensemble* e, const char* name, int value);   /* on every member */
+int         mdqt_pump_ensemble_init(mdqt_pump_ensemble* e);             /* init() of every job; untagged          */
+int         mdqt_pump_ensemble_md_steps(mdqt_pump_ensemble* e, int n);  /* n x (step(); c0++) of every job        */
+int         mdqt_pump_ensemble_qsteps(mdqt_pump_ensemble* e, int n);    /* n x qstep() of every job (QT only)     */
+int         mdqt_pump_ensemble_tag_spin_up(mdqt_pump_ensemble* e);      /* measureSpinUps() of every job (no file):
+                                                                           the lists by mdqt_get_spin_up_list       */
+int         mdqt_pump_ensemble_output(mdqt_pump_ensemble* e);           /* output() of every job                   */
+int         mdqt_pump_ensemble_run(mdqt_pump_ensemble* e);              /* main() :981-1076 of every job, newRun 0
+                                                                           and 1                                    */
+int         mdqt_pump_ensemble_synchronize(mdqt_pump_ensemble* e);
+/* kernel launches the batched path has issued since creation (force launches, a row member's own included) */
+unsigned long long mdqt_pump_ensemble_launches(const mdqt_pump_ensemble* e);
+/* the batched kernels' own durations: out[9] = force ms (sum), force launches, QT ms, QT launches, kick-drift
+ * ms, kick-drift launches, then the three medians (ms) — since the last call; synchronises and resets */
+int         mdqt_pump_ensemble_enable_timing(mdqt_pump_ensemble* e, int on);
+int         mdqt_pump_ensemble_kernel_times(mdqt_pump_ensemble* e, double* out, int n);
 
 #ifdef __cplusplus
 }

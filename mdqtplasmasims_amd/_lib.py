@@ -216,6 +216,23 @@ SIGNATURES = [
     ("mdqt_ensemble_synchronize", C.c_int, [C.c_void_p]),
     ("mdqt_ensemble_enable_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("mdqt_ensemble_kernel_times", C.c_int, [C.c_void_p, _dp, C.c_int]),
+    # ensembles of the optical-pumping programs, and the single context's stepwise MD step
+    ("mdqt_pump_md_steps", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdqt_pump_ensemble_create", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.POINTER(C.c_void_p)]),
+    ("mdqt_pump_ensemble_destroy", None, [C.c_void_p]),
+    ("mdqt_pump_ensemble_size", C.c_int, [C.c_void_p]),
+    ("mdqt_pump_ensemble_job", C.c_void_p, [C.c_void_p, C.c_int]),
+    ("mdqt_pump_ensemble_set_option", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    ("mdqt_pump_ensemble_init", C.c_int, [C.c_void_p]),
+    ("mdqt_pump_ensemble_md_steps", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdqt_pump_ensemble_qsteps", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdqt_pump_ensemble_tag_spin_up", C.c_int, [C.c_void_p]),
+    ("mdqt_pump_ensemble_output", C.c_int, [C.c_void_p]),
+    ("mdqt_pump_ensemble_run", C.c_int, [C.c_void_p]),
+    ("mdqt_pump_ensemble_synchronize", C.c_int, [C.c_void_p]),
+    ("mdqt_pump_ensemble_launches", C.c_ulonglong, [C.c_void_p]),
+    ("mdqt_pump_ensemble_enable_timing", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdqt_pump_ensemble_kernel_times", C.c_int, [C.c_void_p, _dp, C.c_int]),
 ]
 
 _lib = None

@@ -8,6 +8,7 @@
 // order, so the only device/host differences left are libm ulps (exp) and reduction orders.
 #include "mdqt_internal.hpp"
 #include "mdmc_device.hpp"   // the bodies shared with the ensemble's batched kernels
+#include "mdqt_pump_device.hpp"   // the tagged distribution's bodies, shared with the pump ensemble's kernels
 
 #include <math.h>
 
@@ -558,47 +559,20 @@ __global__ __launch_bounds__(256) void k_anisotropize(double* __restrict__ V, in
 // V2 = 1/(2 0.002^2), / (6 sqrt(2 pi 0.002^2)).  Workgroup = 256 bins x one chunk of ions (LDS
 // staged, ascending); the chunk partials are summed in chunk order by k_tagged_kde_reduce.
 // ------------------------------------------------------------------------------------------
-constexpr int TKDE_CHUNK = 256;
-
+// The bodies are in mdqt_pump_device.hpp (tagged_kde_chunk, tagged_kde_reduce_1), shared with the pump
+// ensemble's batched kernels.
 __global__ __launch_bounds__(256) void k_tagged_kde(const double* __restrict__ V, const int* __restrict__ tags, int N,
                                                     int S, int bin0, double* __restrict__ part) {
     __shared__ double sv[3][TKDE_CHUNK];
     __shared__ int st[TKDE_CHUNK];
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    const int i0 = blockIdx.y * TKDE_CHUNK;
-    const int i = i0 + threadIdx.x;
-    if (i < N) {
-        sv[0][threadIdx.x] = V[i]; sv[1][threadIdx.x] = V[S + i]; sv[2][threadIdx.x] = V[2 * S + i];
-        st[threadIdx.x] = tags[i];
-    } else {
-        st[threadIdx.x] = 0;
-    }
-    __syncthreads();
-    const double vel = (double)(j + bin0) * 0.0025;                 // QTT:250 (bin0 = -2000)
-    const double V2 = kKdeV2;                                      // 1 / (2 * 0.002^2), QTT:1072
-    double p[3] = {0., 0., 0.};
-    const int m = min(TKDE_CHUNK, N - i0);
-    for (int k = 0; k < m; ++k) {
-        if (!st[k]) continue;                                      // uniform over the workgroup
-        // a component whose term is exactly +0 on every bin of the wave (|vel - v| >= 0.0773:
-        // V2 d^2 >= 746.9, below exp's underflow) adds exact zeros there and is skipped
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            if (__builtin_amdgcn_ballot_w64(!(fabs(vel - sv[c][k]) >= kKdeSkip)))
-                p[c] += exp(-V2 * (vel - sv[c][k]) * (vel - sv[c][k]));   // :1100-1102
-    }
-    if (j < TKDE_BINS)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) part[((size_t)blockIdx.y * 3 + c) * TKDE_BINS + j] = p[c];
+    tagged_kde_chunk(V, tags, N, S, bin0, part, blockIdx.x, blockIdx.y, sv, st);
 }
 
 __global__ __launch_bounds__(256) void k_tagged_kde_reduce(const double* __restrict__ part, int nch,
                                                            double* __restrict__ out) {
     const int k = blockIdx.x * 256 + threadIdx.x;                  // c * TKDE_BINS + j
     if (k >= 3 * TKDE_BINS) return;
-    double s = 0.;
-    for (int q = 0; q < nch; ++q) s = s + part[(size_t)q * 3 * TKDE_BINS + k];
-    out[k] = s / (6.0 * sqrt(2 * M_PI * 0.002 * 0.002));            // :1121-1123
+    tagged_kde_reduce_1(part, nch, out, k);
 }
 
 // ------------------------------------------------------------------------------------------

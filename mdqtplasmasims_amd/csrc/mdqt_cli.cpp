@@ -14,6 +14,10 @@
 //   --njobs=J runs the jobs <job> .. <job>+J-1 of the reference's Slurm array (exampleSlurmFile.slurm:3)
 //   as one ensemble (mdqt_ensemble_run: one force and one QT launch per MD step for all of them), job k
 //   seeded seed + k; each job's files are those of `mdqt <job>+k --seed=<seed>+k`; prints every N.
+//
+//   --pump_program=m --pump_jobs=J does the same for the pumping programs (mdqt_pump_ensemble_run): the jobs
+//   <job> .. <job>+J-1 stepped in batched launches, each job's tree byte for byte that of
+//   `mdqt <job>+k --pump_program=m --seed=<seed>+k`; prints every N.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -31,7 +35,9 @@ static void usage(void) {
             "                  [--qt=1] [--device=-1]\n"
             "       mdqt <job> --pump_program=1|2|3 [--tpumpreal=2e-7] [--tstartV0=15] [... as above]\n"
             "       mdqt <job> --njobs=J [... as above]   jobs <job> .. <job>+J-1 as one ensemble (J >= 1;\n"
-            "                  seeds seed .. seed+J-1; not with --pump_program)\n");
+            "                  seeds seed .. seed+J-1; not with --pump_program: --pump_jobs)\n"
+            "       mdqt <job> --pump_program=1|2|3 --pump_jobs=J [...]   the pump jobs <job> .. <job>+J-1 as one\n"
+            "                  ensemble (1 <= J <= 1024; seeds seed .. seed+J-1; not with --njobs)\n");
 }
 
 int main(int argc, char** argv) {
@@ -47,6 +53,7 @@ int main(int argc, char** argv) {
     p.job = (uint32_t)job;
     int seed_given = 0;
     long njobs = -1;                                        // --njobs: the jobs of an ensemble (-1: not given)
+    long pump_jobs = -1;                                    // --pump_jobs: the jobs of a pump ensemble
     for (int i = 2; i < argc; ++i) {
         const char* a = argv[i];
         if (strncmp(a, "--", 2) != 0 || !strchr(a, '=')) { usage(); return 2; }
@@ -72,6 +79,12 @@ int main(int argc, char** argv) {
             if (end == v || *end || njobs < 1 || njobs > 1024) { usage(); return 2; }
             continue;
         }
+        if (!strcmp(key, "pump_jobs")) {
+            char* end = NULL;
+            pump_jobs = strtol(v, &end, 10);
+            if (end == v || *end || pump_jobs < 1 || pump_jobs > 1024) { usage(); return 2; }
+            continue;
+        }
         if (!strcmp(key, "seed")) { p.seed = (uint32_t)strtoul(v, NULL, 10); seed_given = 1; continue; }
         if (!strcmp(key, "saveDirectory")) {
             strncpy(p.saveDirectory, v, sizeof(p.saveDirectory) - 1);
@@ -81,6 +94,7 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (njobs > 0 && pump) { usage(); return 2; }
+    if (pump_jobs > 0 && (!pump || njobs > 0)) { usage(); return 2; }
     if (!seed_given) p.seed = (uint32_t)(time(NULL) + job);   // SpeedUp:1219
     if (njobs > 0) {
         mdqt_ensemble* e = NULL;
@@ -93,6 +107,19 @@ int main(int argc, char** argv) {
         else
             for (int k = 0; k < (int)njobs; ++k) printf("%i\n", mdqt_get_N(mdqt_ensemble_job(e, k)));
         mdqt_ensemble_destroy(e);
+        return rc ? 1 : 0;
+    }
+    if (pump_jobs > 0) {
+        mdqt_pump_ensemble* e = NULL;
+        if (mdqt_pump_ensemble_create(&p, (int)pump_jobs, &e)) {
+            fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
+            return 1;
+        }
+        const int rc = mdqt_pump_ensemble_run(e);
+        if (rc) fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
+        else
+            for (int k = 0; k < (int)pump_jobs; ++k) printf("%i\n", mdqt_get_N(mdqt_pump_ensemble_job(e, k)));
+        mdqt_pump_ensemble_destroy(e);
         return rc ? 1 : 0;
     }
     mdqt_ctx* c = NULL;

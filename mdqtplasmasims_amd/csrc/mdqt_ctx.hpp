@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -244,6 +245,21 @@ struct mdqt_ensemble {
     bool timing = false;
     std::vector<hipEvent_t> evpool[2];             // 0 = force launches, 1 = QT launches (start, stop, ...)
     int evused[2] = {0, 0};
+    unsigned long long force_launches = 0;         // force launches issued by ens_forces (batched + the row members' own)
+};
+
+// J independent jobs of an optical-pumping program stepped in batched launches (mdqt_pump_ensemble.cpp): an
+// mdqt_ensemble's members, stream, argument ring, force launch and writer pool, and the pump kernels' blocks
+struct mdqt_pump_ensemble {
+    mdqt_ensemble* base = nullptr;
+    mdqt::PumpStepArgs* dStep[2] = {nullptr, nullptr};   // [J] the leading drift's blocks, the kick launch's blocks
+    std::vector<mdqt::PumpStepArgs> step_held[2];        // what they hold
+    mdqt::PumpTagArgs* dTag = nullptr;                   // [J]
+    mdqt::PumpKdeArgs* dKde = nullptr;                   // [J]
+    std::vector<int> kde_cap, tag_cap;                   // chunks / ints the ensemble allocated of each member's dTkde / dSpinUp
+    unsigned long long launches = 0;                     // the pump kernels' launches (the force launches: base)
+    std::vector<hipEvent_t> evkick;                      // the kick launches' timestamps (start, stop, ...)
+    int evkick_used = 0;
 };
 
 namespace mdqt {
@@ -311,6 +327,23 @@ int output_async(mdqt_ctx* s);
 int write_conditions_async(mdqt_ctx* s, int c0);
 int read_ions_conditions(mdqt_ctx* s, int c0, std::vector<double>& R, std::vector<double>& V);
 int fusable_substeps(const mdqt_ctx* s, double tend, long c0, int ts);
+
+// mdqt_pump.cpp: the pieces of the optical-pumping programs' main() the pump ensemble shares
+int pump_setup_directories(mdqt_ctx* s);
+int pump_md_step(mdqt_ctx* s);
+int pump_spin_ups_file(mdqt_ctx* s);
+int pump_output_buffers(mdqt_ctx* s);
+int pump_output_host(mdqt_ctx* s, const std::vector<double>& V, std::vector<double>& P,
+                     const std::function<int()>& tagged, FileWriter* pool);
+int pump_vaf_host(mdqt_ctx* s, const std::vector<double>& V, int c1V);
+int pump_write_conditions(mdqt_ctx* s, int c0);
+int pump_read_conditions(mdqt_ctx* s, int c0);
+
+// mdqt_ensemble.cpp: the ensemble's machinery the pump ensemble reuses
+int ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, const char* what, bool pump);
+int ens_ring_slot(mdqt_ensemble* e, char** slot, int* idx);
+int ens_upload(mdqt_ensemble* e, void* dst, const void* src_slot, size_t bytes, int idx);
+int ens_forces(mdqt_ensemble* e);
 
 // mdqt_options.cpp (timing events)
 int mark(mdqt_ctx* s, int k);

@@ -22,11 +22,11 @@
 using namespace mdqt;
 
 namespace {
-
 constexpr int kEnsembleMaxJobs = 1024;
+}  // namespace
 
 // a pinned slot nobody reads any more
-int ens_ring_slot(mdqt_ensemble* e, char** slot, int* idx) {
+int mdqt::ens_ring_slot(mdqt_ensemble* e, char** slot, int* idx) {
     const int i = (int)(e->ring_pos++ % mdqt_ensemble::kRing);
     if (e->ring_used[i]) HIPCHK(hipEventSynchronize(e->ring_ev[i]));
     *slot = e->ring + (size_t)i * e->slot_bytes;
@@ -34,12 +34,14 @@ int ens_ring_slot(mdqt_ensemble* e, char** slot, int* idx) {
     return 0;
 }
 
-int ens_upload(mdqt_ensemble* e, void* dst, const void* src_slot, size_t bytes, int idx) {
+int mdqt::ens_upload(mdqt_ensemble* e, void* dst, const void* src_slot, size_t bytes, int idx) {
     HIPCHK(hipMemcpyAsync(dst, src_slot, bytes, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipEventRecord(e->ring_ev[idx], e->stream));
     e->ring_used[idx] = true;
     return 0;
 }
+
+namespace {
 
 // Every batched call: the members still are what the batched kernels cover, and still in lockstep.
 // The pending-force state is NOT compared: it is per job by design (a one-tile job never has pending
@@ -105,21 +107,27 @@ int ens_force_launch(mdqt_ensemble* e, const EnsForce& f) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (e->timing && take_events(e->evpool[0], e->evused[0], &e0, &e1)) return -1;
     HIPCHK(launch_forces_n3_ens(e->dForce, (int)f.h.size(), f.maxp, f.variant, f.guard, e->stream, e0, e1));
+    e->force_launches++;
     return 0;
 }
 
+}  // namespace
+
 // forces() of every member: one launch over the members on the Newton-3 tiles; a member below 128 ions
 // (owner-computes rows by default, as on its own) gets its own small launch
-int ens_forces(mdqt_ensemble* e) {
+int mdqt::ens_forces(mdqt_ensemble* e) {
     EnsForce f;
     if (ens_force_blocks(e, f) || ens_force_launch(e, f)) return -1;
     size_t q = 0;
     for (mdqt_ctx* s : e->jobs) {
         if (s->use_n3) n3_forces_pending(s, f.h[q++]);
         else if (mdqt_forces(s)) return -1;
+        else e->force_launches++;
     }
     return 0;
 }
+
+namespace {
 
 // run_substeps(s, n, 1, 1, 1) of every member: chunks of at most MAXSUB, one launch per chunk
 int ens_substeps(mdqt_ensemble* e, int n) {
@@ -272,22 +280,26 @@ extern "C" void mdqt_ensemble_destroy(mdqt_ensemble* e) {
     delete e;
 }
 
-extern "C" int mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out) {
-    if (!p || !out) return set_error("mdqt_ensemble_create: NULL argument");
+// mdqt_ensemble_create, and the same members and machinery for mdqt_pump_ensemble_create (pump: qt_model 1-3)
+int mdqt::ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, const char* what, bool pump) {
+    if (!p || !out) return set_error("%s: NULL argument", what);
     *out = nullptr;
-    if (njobs < 1 || njobs > kEnsembleMaxJobs) return set_error("mdqt_ensemble_create: njobs must be 1 .. %d", kEnsembleMaxJobs);
-    if (p->world_size != 1) return set_error("mdqt_ensemble_create: world_size must be 1 (an ensemble's jobs are whole systems on one device)");
+    if (njobs < 1 || njobs > kEnsembleMaxJobs) return set_error("%s: njobs must be 1 .. %d", what, kEnsembleMaxJobs);
+    if (p->world_size != 1) return set_error("%s: world_size must be 1 (an ensemble's jobs are whole systems on one device)", what);
     if (p->rng_mode != 1)
-        return set_error("mdqt_ensemble_create: rng_mode must be 1 (Philox): the drand48 order needs one substep per launch "
-                         "and a resolve kernel per job");
-    if (p->qt_model != 0) return set_error("mdqt_ensemble_create: qt_model must be 0 (the SpeedUp program; the pump programs are not batched)");
+        return set_error("%s: rng_mode must be 1 (Philox): the drand48 order needs one substep per launch "
+                         "and a resolve kernel per job", what);
+    if (!pump && p->qt_model != 0)
+        return set_error("%s: qt_model must be 0 (the SpeedUp program; the pump programs have mdqt_pump_ensemble_create)", what);
+    if (pump && (p->qt_model < 1 || p->qt_model > 3))
+        return set_error("%s: qt_model must be 1, 2 or 3 (the optical-pumping programs)", what);
     std::unique_ptr<mdqt_ensemble, void (*)(mdqt_ensemble*)> e(new (std::nothrow) mdqt_ensemble(), mdqt_ensemble_destroy);
-    if (!e) return set_error("mdqt_ensemble_create: out of memory");
+    if (!e) return set_error("%s: out of memory", what);
     try {
         e->jobs.reserve((size_t)njobs);
         e->writer.reset(new FileWriter(std::min(16, 4 * njobs)));
     } catch (const std::exception& x) {
-        return set_error("mdqt_ensemble_create: %s", x.what());
+        return set_error("%s: %s", what, x.what());
     }
     for (int k = 0; k < njobs; ++k) {
         mdqt_params pk;
@@ -296,8 +308,8 @@ extern "C" int mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemb
         e->jobs.push_back(s);
         s->shared_writer = e->writer.get();
         if (k == 0) { e->dev = s->dev; e->stream = s->own; }
-        if (s->qt_math != 2) return set_error("mdqt_ensemble_create: qt_math must be 2");
-        if (s->overlap_opt || s->fused_opt) return set_error("mdqt_ensemble_create: the options overlap / fused_step are one system per launch");
+        if (s->qt_math != 2) return set_error("%s: qt_math must be 2", what);
+        if (s->overlap_opt || s->fused_opt) return set_error("%s: the options overlap / fused_step are one system per launch", what);
         mdqt_set_stream(s, (void*)e->stream);
     }
     HIPCHK(hipSetDevice(e->dev));
@@ -306,10 +318,14 @@ extern "C" int mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemb
     if (hipMalloc(&e->dForce, (size_t)njobs * sizeof(N3Args)) != hipSuccess ||
         hipMalloc(&e->dSub, (size_t)e->sub_blocks * sizeof(SubstepArgs)) != hipSuccess ||
         hipHostMalloc((void**)&e->ring, e->slot_bytes * mdqt_ensemble::kRing, hipHostMallocDefault) != hipSuccess)
-        return set_error("mdqt_ensemble_create: allocating the argument blocks of %d jobs failed", njobs);
+        return set_error("%s: allocating the argument blocks of %d jobs failed", what, njobs);
     for (hipEvent_t& ev : e->ring_ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence));
     *out = e.release();
     return 0;
+}
+
+extern "C" int mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out) {
+    return ensemble_create(p, njobs, out, "mdqt_ensemble_create", false);
 }
 
 extern "C" int mdqt_ensemble_size(const mdqt_ensemble* e) { return e ? (int)e->jobs.size() : -1; }

@@ -696,6 +696,46 @@ hipError_t launch_forces_n3_ens(const N3Args* jobs, int njobs, int max_npairs, i
 hipError_t launch_substeps_r_ens(const SubstepArgs* jobs, const SubstepArgs& a, int njobs, int max_n, const FastTab* tab,
                                  int wpe, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
                                  int* instance = nullptr);
+// An ensemble of optical-pumping jobs in batched launches (mdqt_pump_ensemble_kernels.hip; host:
+// mdqt_pump_ensemble.cpp): `jobs` = device array of the members' argument blocks, grid (largest member's
+// workgroups, njobs); every kernel runs its single-job kernel's body (mdqt_pump_device.hpp, lane_substeps).
+struct PumpStepArgs {   // one member's leapfrog half (step() :377-394)
+    double *R, *V, *F;  // [3][S]
+    const double* Fpart;// nseg > 1: the pending force partials [nseg][3][S]; F = their canonical sum
+    int nseg;           //   (slot_sum16, as k_reduce_segments), written back before it is used
+    int n, S;
+    double L;
+};
+struct PumpTagArgs {    // one member's measureSpinUps (k_tag_spin_up's arguments)
+    const double* psi;
+    int n, S;
+    uint64_t gid0, q;
+    int* tags;
+    QTConst qc;
+};
+struct PumpKdeArgs {    // one member's tagged distribution (launch_tagged_kde's arguments)
+    const double* V;
+    const int* tags;
+    int N, S, bin0;
+    double* part;       // [chunks][3][TKDE_BINS]
+    double* out;        // [3][TKDE_BINS]
+};
+// the pump models' lane QT instance (launch_substeps_r's mode 2, model 1-3) over members: `a` = host copy of
+// one member's block (every member has the same nsub, do_step, do_qt, movmask and model)
+hipError_t launch_substeps_pump_ens(const SubstepArgs* jobs, const SubstepArgs& a, int njobs, int max_n,
+                                    const FastTab* tab, hipStream_t s, hipEvent_t ev0 = nullptr,
+                                    hipEvent_t ev1 = nullptr, int* instance = nullptr);
+// the leading half drift of step(): k_leapfrog_half (kick 0) of every member, after settling pending forces
+hipError_t launch_pump_drift_ens(const PumpStepArgs* jobs, int njobs, int max_n, double DT, double DT2, int moving,
+                                 hipStream_t s);
+// the second half of step(): F = the canonical slot sum (written back), k_leapfrog_half's kick and half drift,
+// and with fold != 0 the next step's leading half drift (t > 0 form) as a second, separately rounded update
+hipError_t launch_pump_kick_ens(const PumpStepArgs* jobs, int njobs, int max_n, double DT, double DT2, int moving,
+                                double kick, int fold, hipStream_t s, hipEvent_t ev0 = nullptr,
+                                hipEvent_t ev1 = nullptr);
+hipError_t launch_tag_spin_up_ens(const PumpTagArgs* jobs, int njobs, int max_n, hipStream_t s);
+hipError_t launch_tagged_kde_ens(const PumpKdeArgs* jobs, int njobs, int max_N, hipStream_t s);
+
 // measureSpinUps (randomFrozenStartTag408Linear.cpp:600, :422Linear) / tagParticles
 // (MonteCarloFollowedByQTTagging408Linear.cpp:1022): tag[i] = 1 with probability of spin up
 hipError_t launch_tag_spin_up(const double* psi, int n, int S, uint64_t gid0, uint64_t q, const QTConst& qc,

@@ -9,6 +9,7 @@
 // the reference's operation order (x86-64 g++ -O3 contracts nothing), so the only
 // device/host differences left are libm ulps (exp, sin, cos).  See DESIGN.md §Parity.
 #include "mdqt_device.hpp"
+#include "mdqt_pump_device.hpp"   // the body k_leapfrog_half shares with the pump ensemble's batched kernels
 
 #include <math.h>
 
@@ -739,18 +740,7 @@ __global__ __launch_bounds__(256) void k_leapfrog_half(double* __restrict__ R, d
                                                        double DT, double DT2, int moving, double kick) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const size_t k = (size_t)c * S + i;
-        double v = V[k];
-        const double f = F[k];
-        if (kick != 0.) { v += kick * f; V[k] = v; }                 // V[c][i] += DT*F[c][i]   :366-370
-        double r = R[k];
-        r = moving ? r + DT * v : r + (DT * v + DT2 * f);            // :320-338
-        if (r < 0) r += L;                                           // :346-354
-        if (r > L) r -= L;
-        R[k] = r;
-    }
+    leapfrog_half_ion(R, V, F, i, S, L, DT, DT2, moving, kick);      // mdqt_pump_device.hpp
 }
 
 hipError_t launch_leapfrog_half(double* R, double* V, const double* F, int n, int S, double L, double DT, double DT2,

@@ -5,6 +5,8 @@
 
 #include <math.h>
 
+#include <functional>
+
 #include "mdqt_ctx.hpp"
 
 using namespace mdqt;
@@ -34,7 +36,7 @@ extern "C" int mdqt_tag_spin_up(mdqt_ctx* s, int* tags, int* n_up) {
     return 0;
 }
 
-static int setup_directories_pump(mdqt_ctx* s) {                // :985-999
+int mdqt::pump_setup_directories(mdqt_ctx* s) {                // :985-999
     const mdqt_params* p = &s->p;
     char name[256];
     snprintf(name, sizeof name, "PumpTime%dPumpStart%dDet%dOm%dDensity%dGe%dNumIons%d",
@@ -46,7 +48,7 @@ static int setup_directories_pump(mdqt_ctx* s) {                // :985-999
 
 // step() :377-394: step_R(dt/2) (at t == 0 with forces() first and the DT^2 F term), step_V(dt)
 // with forces() at the half-drifted positions, step_R(dt/2)
-static int md_step_pump(mdqt_ctx* s) {
+int mdqt::pump_md_step(mdqt_ctx* s) {
     const double dt = s->dtQ * s->ratio;                         // :389 dt=quantumTimestep*ratio
     const double DT = 0.5 * dt, DT2 = DT * DT;
     const int moving = s->t > 0 ? 1 : 0;
@@ -63,15 +65,19 @@ static int md_step_pump(mdqt_ctx* s) {
     return 0;
 }
 
-// measureSpinUps() :600-665 (tags from the Philox stream, mdqt_tag_spin_up)
-static int measure_spin_ups(mdqt_ctx* s) {
-    const int N = s->N;
-    s->spinUp.assign((size_t)(N > 0 ? N : 1), 0);
-    int n_up = 0;
-    if (mdqt_tag_spin_up(s, s->spinUp.data(), &n_up)) return -1;
-    s->nSpinUp = n_up;
-    if (!s->dSpinUp) HIPCHK(hipMalloc(&s->dSpinUp, (size_t)s->capS * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(s->dSpinUp, s->spinUp.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s->stream));
+extern "C" int mdqt_pump_md_steps(mdqt_ctx* s, int n) {         // n x (step(); c0++) at the context's t
+    if (!s) return set_error("NULL context");
+    if (n < 0) return set_error("negative step count");
+    if (s->p.world_size != 1) return set_error("mdqt_pump_md_steps: world_size 1 only");
+    for (int k = 0; k < n; ++k) {
+        if (pump_md_step(s)) return -1;
+        s->c0++;
+    }
+    return 0;
+}
+
+// measureSpinUps() :600-665: the file of the count (:651-662)
+int mdqt::pump_spin_ups_file(mdqt_ctx* s) {
     char b[96];
     snprintf(b, sizeof b, "spinUpIons_timestep%06d.dat", s->c0);
     FILE* fa = open_in(s, b, "w");
@@ -81,12 +87,37 @@ static int measure_spin_ups(mdqt_ctx* s) {
     return 0;
 }
 
-// output() :799-935: energies (EkinX without subtracting <vx>), the spin-up ions' moments and x
-// velocity distribution over 4001 bins, counter++; host sums in the reference's order
-static int output_pump(mdqt_ctx* s) {
+// measureSpinUps() :600-665 (tags from the Philox stream, mdqt_tag_spin_up)
+static int measure_spin_ups(mdqt_ctx* s) {
     const int N = s->N;
-    std::vector<double> V((size_t)3 * (N > 0 ? N : 1), 0.);
-    if (mdqt_get_state(s, nullptr, V.data(), nullptr, N, nullptr, nullptr, nullptr)) return -1;
+    s->spinUp.assign((size_t)(N > 0 ? N : 1), 0);
+    int n_up = 0;
+    if (mdqt_tag_spin_up(s, s->spinUp.data(), &n_up)) return -1;
+    s->nSpinUp = n_up;
+    if (!s->dSpinUp) HIPCHK(hipMalloc(&s->dSpinUp, (size_t)s->capS * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(s->dSpinUp, s->spinUp.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    return pump_spin_ups_file(s);
+}
+
+// output()'s device buffers: the tagged distribution's partials and result, the device copy of the tags
+int mdqt::pump_output_buffers(mdqt_ctx* s) {
+    const int nch = (s->N + 255) / 256;
+    if (!s->dTkde) HIPCHK(hipMalloc(&s->dTkde, ((size_t)(nch > 0 ? nch : 1) + 1) * 3 * TKDE_BINS * sizeof(double)));
+    if (!s->dSpinUp) {
+        HIPCHK(hipMalloc(&s->dSpinUp, (size_t)s->capS * sizeof(int)));
+        HIPCHK(hipMemsetAsync(s->dSpinUp, 0, (size_t)s->capS * sizeof(int), s->stream));
+    }
+    return 0;
+}
+
+// output() :799-935, the host part: energies (EkinX without subtracting <vx>; Epotential() is the
+// context's own call), the spin-up ions' moments, the files, counter++; host sums in the reference's
+// order.  V = the velocities [3][N], P = the tagged distribution [3][TKDE_BINS] (filled by `tagged`,
+// which runs after the energies as in output_pump, or beforehand by the caller: tagged == nullptr).
+// pool != nullptr: the 4001-line distribution file is formatted ("%lg", byte-identical) on that pool.
+int mdqt::pump_output_host(mdqt_ctx* s, const std::vector<double>& V, std::vector<double>& P,
+                           const std::function<int()>& tagged, FileWriter* pool) {
+    const int N = s->N;
     double EkinX = 0., EkinY = 0., EkinZ = 0.;
     for (int i = 0; i < N; i++) {                                // :812-817
         EkinX += 0.5 * (V[i] * V[i]);
@@ -101,20 +132,7 @@ static int output_pump(mdqt_ctx* s) {
     fprintf(fa, "%lg\t%lg\t%lg\t%lg\t%lg\t%lg\n", s->t, EkinX, EkinY, EkinZ, s->Epot,
             EkinX + EkinY + EkinZ + s->Epot - s->Epot0);
     fclose(fa);
-    // tagged x distribution on the device (:831-864 exp(-V2 (vel_j - v)^2) summed over spin-up ions)
-    const int nch = (N + 255) / 256;
-    if (!s->dTkde) HIPCHK(hipMalloc(&s->dTkde, ((size_t)(nch > 0 ? nch : 1) + 1) * 3 * TKDE_BINS * sizeof(double)));
-    if (!s->dSpinUp) {
-        HIPCHK(hipMalloc(&s->dSpinUp, (size_t)s->capS * sizeof(int)));
-        HIPCHK(hipMemsetAsync(s->dSpinUp, 0, (size_t)s->capS * sizeof(int), s->stream));
-    }
-    std::vector<double> P((size_t)3 * TKDE_BINS, 0.);
-    if (N > 0) {
-        HIPCHK(launch_tagged_kde(s->dV, s->dSpinUp, N, s->S, s->dTkde + (size_t)3 * TKDE_BINS, s->dTkde, s->stream,
-                                 s->pumpBin0));
-        HIPCHK(hipMemcpyAsync(P.data(), s->dTkde, P.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-    }
+    if (tagged && tagged()) return -1;
     // moments of the tagged x velocities (:836-851, :866-876)
     double m1 = 0, m2 = 0, m3 = 0, m4 = 0;
     unsigned nt = 0;
@@ -133,19 +151,47 @@ static int output_pump(mdqt_ctx* s) {
     fclose(fa);
     char b[96];
     snprintf(b, sizeof b, "vel_distX_timestep%06d.dat", s->c0);   // :887-901 (X only)
-    fa = open_in(s, b, "w");
-    if (!fa) return -1;
-    for (int j = 0; j < TKDE_BINS; j++) fprintf(fa, "%lg\t%lg\n", (double)(j + s->pumpBin0) * 0.0025, P[j]);
-    fclose(fa);
+    if (pool) {
+        const int bin0 = s->pumpBin0;
+        pool->submit(std::string(s->saveDirectory) + b, "w",
+                     [bin0, Px = std::vector<double>(P.begin(), P.begin() + TKDE_BINS)](LgText& t) {
+                         for (int j = 0; j < TKDE_BINS; j++) {
+                             t.num((double)(j + bin0) * 0.0025); t.ch('\t'); t.num(Px[j]); t.ch('\n');
+                         }
+                     });
+    } else {
+        fa = open_in(s, b, "w");
+        if (!fa) return -1;
+        for (int j = 0; j < TKDE_BINS; j++) fprintf(fa, "%lg\t%lg\n", (double)(j + s->pumpBin0) * 0.0025, P[j]);
+        fclose(fa);
+    }
     s->counter++;                                                // :929
     return 0;
 }
 
-// Zfunc(c1V) + printVAF(t) :938-975 (host, the reference's order)
-static int vaf_pump(mdqt_ctx* s, int c1V) {
+// output() :799-935: the velocities, then the host part with the tagged x distribution on the device
+// (:831-864 exp(-V2 (vel_j - v)^2) summed over spin-up ions, 4001 bins)
+static int output_pump(mdqt_ctx* s) {
     const int N = s->N;
     std::vector<double> V((size_t)3 * (N > 0 ? N : 1), 0.);
     if (mdqt_get_state(s, nullptr, V.data(), nullptr, N, nullptr, nullptr, nullptr)) return -1;
+    std::vector<double> P((size_t)3 * TKDE_BINS, 0.);
+    auto tagged = [&]() -> int {
+        if (pump_output_buffers(s)) return -1;
+        if (N > 0) {
+            HIPCHK(launch_tagged_kde(s->dV, s->dSpinUp, N, s->S, s->dTkde + (size_t)3 * TKDE_BINS, s->dTkde, s->stream,
+                                     s->pumpBin0));
+            HIPCHK(hipMemcpyAsync(P.data(), s->dTkde, P.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipStreamSynchronize(s->stream));
+        }
+        return 0;
+    };
+    return pump_output_host(s, V, P, tagged, nullptr);
+}
+
+// Zfunc(c1V) + printVAF(t) :938-975 (host, the reference's order) on the velocities V [3][N]
+int mdqt::pump_vaf_host(mdqt_ctx* s, const std::vector<double>& V, int c1V) {
+    const int N = s->N;
     if (c1V == 0) s->vaHold.assign(V.begin(), V.begin() + N);
     if ((int)s->vaHold.size() < N) s->vaHold.resize((size_t)N, 0.);
     double VAF = 0.0;
@@ -157,7 +203,14 @@ static int vaf_pump(mdqt_ctx* s, int c1V) {
     return 0;
 }
 
-static int write_conditions_pump(mdqt_ctx* s, int c0) {        // :667-707
+static int vaf_pump(mdqt_ctx* s, int c1V) {
+    const int N = s->N;
+    std::vector<double> V((size_t)3 * (N > 0 ? N : 1), 0.);
+    if (mdqt_get_state(s, nullptr, V.data(), nullptr, N, nullptr, nullptr, nullptr)) return -1;
+    return pump_vaf_host(s, V, c1V);
+}
+
+int mdqt::pump_write_conditions(mdqt_ctx* s, int c0) {        // :667-707
     const int N = s->N;
     std::vector<double> R((size_t)3 * (N > 0 ? N : 1), 0.), V(R.size(), 0.);
     if (mdqt_get_state(s, R.data(), V.data(), nullptr, N, nullptr, nullptr, nullptr)) return -1;
@@ -182,7 +235,7 @@ static int write_conditions_pump(mdqt_ctx* s, int c0) {        // :667-707
     return 0;
 }
 
-static int read_conditions_pump(mdqt_ctx* s, int c0) {         // :709-797
+int mdqt::pump_read_conditions(mdqt_ctx* s, int c0) {         // :709-797
     s->pumpBin0 = 0;                                             // :721-724 vel[i] = i 0.0025
     std::vector<double> R, V;
     const int N = read_ions_conditions(s, c0, R, V);             // :713-770
@@ -222,7 +275,7 @@ extern "C" int mdqt_run_pump(mdqt_ctx* s) {                     // main() :981-1
     if (!s) return set_error("NULL context");
     if (s->p.qt_model < 1 || s->p.qt_model > 3) return set_error("mdqt_run_pump: qt_model must be 1, 2 or 3");
     if (s->p.world_size != 1) return set_error("mdqt_run_pump: world_size 1 only");
-    if (setup_directories_pump(s)) return -1;
+    if (pump_setup_directories(s)) return -1;
     int recorded = 0;                                            // recordedSpinUps :81
     s->spinUp.clear();
     s->nSpinUp = 0;
@@ -230,7 +283,7 @@ extern "C" int mdqt_run_pump(mdqt_ctx* s) {                     // main() :981-1
     if (s->p.newRun == 1) {                                      // :1036-1046
         if (mdqt_init(s)) return -1;
     } else {
-        if (read_conditions_pump(s, s->p.c0)) return -1;
+        if (pump_read_conditions(s, s->p.c0)) return -1;
         recorded = 1;
     }
     const double tpump = s->p.tpumpreal * 813490 * sqrt(s->p.density);      // :79
@@ -265,7 +318,7 @@ extern "C" int mdqt_run_pump(mdqt_ctx* s) {                     // main() :981-1
         }
         if (tsc == ratio) {                                      // :1070-1074
             if (flush()) return -1;
-            if (md_step_pump(s)) return -1;
+            if (pump_md_step(s)) return -1;
             s->c0++;
             tsc = 0;
         }
@@ -282,5 +335,5 @@ extern "C" int mdqt_run_pump(mdqt_ctx* s) {                     // main() :981-1
     }
     if (flush()) return -1;
     if (flush_files(s)) return -1;
-    return write_conditions_pump(s, s->c0);                      // :1084
+    return pump_write_conditions(s, s->c0);                      // :1084
 }

@@ -1,0 +1,495 @@
+// mdqt_pump_ensemble — J independent jobs of an optical-pumping program (randomFrozenStartTag408Linear.cpp,
+// 408Quad, 422Linear; qt_model 1-3) stepped in batched launches (include/mdqt.h, "ensembles of the
+// optical-pumping programs").  It owns an mdqt_ensemble for the members (ordinary contexts on one stream), the
+// pinned argument ring, the batched force launch (ens_forces: k_pairs_n3_ens over the members on the Newton-3
+// tiles, a row member's own small launch) and the writer pool, and adds the pump programs' kernels over members
+// (mdqt_pump_ensemble_kernels.hip).  Each member's arguments come from the helpers its own path uses
+// (n3_force_args / n3_forces_pending inside ens_forces, substep_args(s, a, m, 0, 1, 1), mdqt_tag_spin_up's lo,
+// qstep index and qc) and the kernels run the single-job kernels' bodies: every member's state and files are
+// those of the job on its own, bit for bit.
+//
+// One MD step (step() :377-394) of every member at t > 0 is two launches: the batched force launch and
+// k_pump_kick_ens (the canonical slot sum, the kick, the trailing half drift and — when nothing reads R, V or F
+// before the next step — that step's leading half drift).  A step whose leading drift was not folded into the
+// launch before it (the first of a call, the one after an output or the measurement, the t == 0 step with its
+// forces() first) starts with k_pump_drift_ens.  The step blocks change only with a member's size or pending
+// state: they are uploaded when they differ from what the device holds; the QT and tagging blocks go through the
+// pinned ring.
+
+#include <math.h>
+
+#include <algorithm>
+
+#include "mdqt_ctx.hpp"
+
+using namespace mdqt;
+
+static_assert(sizeof(PumpTagArgs) <= sizeof(SubstepArgs) && sizeof(PumpKdeArgs) <= sizeof(SubstepArgs) &&
+                  sizeof(PumpStepArgs) <= sizeof(SubstepArgs),
+              "a ring slot holds one block per member of every kind");
+
+namespace {
+
+bool tagged(const mdqt_ctx* s) { return !s->spinUp.empty(); }
+
+// Every batched call: the members still are what the batched kernels cover, and in lockstep — t (bitwise), the
+// qstep index, c0 and the tagged / untagged flag.  Nothing is launched before this has passed.
+int pump_check(const mdqt_pump_ensemble* pe, const char* what) {
+    if (!pe || !pe->base) return set_error("%s: NULL ensemble", what);
+    const mdqt_ensemble* e = pe->base;
+    const mdqt_ctx* a = e->jobs[0];
+    for (size_t k = 0; k < e->jobs.size(); ++k) {
+        const mdqt_ctx* s = e->jobs[k];
+        if (s->stream != e->stream) return set_error("%s: job index %zu was moved to another stream", what, k);
+        if (s->overlap_opt || s->fused_opt)
+            return set_error("%s: job index %zu has the option overlap / fused_step set (one system per launch)", what, k);
+        if (s->qt_math != 2) return set_error("%s: job index %zu has qt_math %d (the pump models are qt_math 2)", what, k, s->qt_math);
+        if (s->substep_mode == 1) return set_error("%s: job index %zu has substep_kernel 1 (the batched QT kernel is the lane kernel)", what, k);
+        if (s->N < 1) return set_error("%s: job index %zu has no ions (mdqt_pump_ensemble_init or mdqt_set_state first)", what, k);
+        if (s->use_n3b || s->N > 65536)
+            return set_error("%s: job index %zu has N = %d: beyond the Newton-3 tile scheme (N <= 65,536)", what, k, s->N);
+        if (s->force_arrive || s->sub_stream || !s->local.empty()) return set_error("%s: job index %zu is part of another scheme", what, k);
+        if (memcmp(&s->t, &a->t, sizeof(double)) || s->qidx != a->qidx || s->c0 != a->c0 || tagged(s) != tagged(a))
+            return set_error("%s: job index %zu is out of step with job index 0 (t %.17g / %.17g, qstep %llu / %llu, c0 %d / %d, "
+                             "tagged %d / %d): a member stepped on its own ends the ensemble's stepping",
+                             what, k, s->t, a->t, (unsigned long long)s->qidx, (unsigned long long)a->qidx, s->c0, a->c0,
+                             (int)tagged(s), (int)tagged(a));
+    }
+    return 0;
+}
+
+// the members' leapfrog blocks from their pending-force state, uploaded to dStep[which] when they differ
+int step_blocks(mdqt_pump_ensemble* pe, int which, int* max_n) {
+    mdqt_ensemble* e = pe->base;
+    const int J = (int)e->jobs.size();
+    std::vector<PumpStepArgs> h((size_t)J);
+    int mx = 0;
+    for (int k = 0; k < J; ++k) {
+        const mdqt_ctx* s = e->jobs[k];
+        PumpStepArgs& a = h[k];
+        memset(&a, 0, sizeof a);
+        a.R = s->dR; a.V = s->dV; a.F = s->dF; a.Fpart = s->dFpart;
+        a.nseg = s->f_pending ? s->pend_nseg : 1;
+        a.n = s->nloc; a.S = s->S; a.L = s->L;
+        mx = std::max(mx, a.n);
+    }
+    std::vector<PumpStepArgs>& held = pe->step_held[which];
+    const size_t bytes = (size_t)J * sizeof(PumpStepArgs);
+    if (held.size() != h.size() || memcmp(held.data(), h.data(), bytes)) {
+        char* slot = nullptr;
+        int idx = 0;
+        if (ens_ring_slot(e, &slot, &idx)) return -1;
+        memcpy(slot, h.data(), bytes);
+        if (ens_upload(e, pe->dStep[which], slot, bytes, idx)) return -1;
+        held = h;
+    }
+    *max_n = mx;
+    return 0;
+}
+
+// step() of every member at the members' t (:377-394).  lead: the leading half drift is still to be done (it
+// was not folded into the launch before); fold: append the next step's leading half drift (the caller knows
+// that nothing reads R, V or F before it and that it is a t > 0 step)
+int pump_step(mdqt_pump_ensemble* pe, bool lead, bool fold) {
+    mdqt_ensemble* e = pe->base;
+    const int J = (int)e->jobs.size();
+    const mdqt_ctx* a = e->jobs[0];
+    const double dt = a->dtQ * a->ratio;                         // :389 dt=quantumTimestep*ratio
+    const double DT = 0.5 * dt, DT2 = DT * DT;
+    const int moving = a->t > 0 ? 1 : 0;
+    if (!moving && !lead) return set_error("mdqt_pump_ensemble: the t == 0 step has forces() before its leading drift");
+    int max_n = 0;
+    if (!moving && ens_forces(e)) return -1;                     // :331 forces() before the first drift
+    if (lead) {
+        if (step_blocks(pe, 0, &max_n)) return -1;               // settles what the t == 0 forces() left pending
+        HIPCHK(launch_pump_drift_ens(pe->dStep[0], J, max_n, DT, DT2, moving, e->stream));
+        pe->launches++;
+        for (mdqt_ctx* s : e->jobs) s->f_pending = false;
+    }
+    if (ens_forces(e)) return -1;                                // step_V: forces() :361
+    if (step_blocks(pe, 1, &max_n)) return -1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (e->timing && take_events(pe->evkick, pe->evkick_used, &e0, &e1)) return -1;
+    HIPCHK(launch_pump_kick_ens(pe->dStep[1], J, max_n, DT, DT2, moving, dt, fold ? 1 : 0, e->stream, e0, e1));
+    pe->launches++;
+    for (mdqt_ctx* s : e->jobs) s->f_pending = false;
+    return 0;
+}
+
+// n x qstep() of every member (QT only: run_substeps(s, n, 0, 1, 1)), chunks of at most MAXSUB
+int pump_qsteps(mdqt_pump_ensemble* pe, int n) {
+    mdqt_ensemble* e = pe->base;
+    const int J = (int)e->jobs.size();
+    const int do_qt = e->jobs[0]->p.qt_enabled ? 1 : 0;
+    while (n > 0) {
+        const int m = n < MAXSUB ? n : MAXSUB;
+        char* slot = nullptr;
+        int idx = 0;
+        if (ens_ring_slot(e, &slot, &idx)) return -1;
+        SubstepArgs* h = reinterpret_cast<SubstepArgs*>(slot);
+        double t = 0.;
+        int maxn = 0;
+        for (int k = 0; k < J; ++k) {
+            mdqt_ctx* s = e->jobs[k];
+            t = substep_args(s, h[k], m, 0, do_qt, 1);
+            s->f_pending = false;
+            maxn = std::max(maxn, h[k].n);
+        }
+        if (ens_upload(e, e->dSub, slot, (size_t)J * sizeof(SubstepArgs), idx)) return -1;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (e->timing && take_events(e->evpool[1], e->evused[1], &e0, &e1)) return -1;
+        int inst = 0;
+        HIPCHK(launch_substeps_pump_ens(e->dSub, h[0], J, maxn, e->jobs[0]->dFTab, e->stream, e0, e1, &inst));
+        pe->launches++;
+        for (int k = 0; k < J; ++k) {
+            mdqt_ctx* s = e->jobs[k];
+            s->last_qt_kernel = inst;
+            s->last_qt_nseg = h[k].nseg;
+            s->t = t;
+            s->qidx += (uint64_t)m;
+        }
+        n -= m;
+    }
+    return 0;
+}
+
+// a member's tag array and tagged-distribution buffers, of a size this ensemble knows (the context allocates
+// them once, for the N of that moment)
+int member_buffers(mdqt_pump_ensemble* pe, int k) {
+    mdqt_ensemble* e = pe->base;
+    mdqt_ctx* s = e->jobs[k];
+    const int nch = std::max(1, (s->N + 255) / 256);
+    if (pe->kde_cap[k] < nch || pe->tag_cap[k] < s->capS) HIPCHK(hipStreamSynchronize(e->stream));
+    if (pe->kde_cap[k] < nch) {
+        if (s->dTkde) HIPCHK(hipFree(s->dTkde));
+        s->dTkde = nullptr;
+        HIPCHK(hipMalloc(&s->dTkde, ((size_t)nch + 1) * 3 * TKDE_BINS * sizeof(double)));
+        pe->kde_cap[k] = nch;
+    }
+    if (pe->tag_cap[k] < s->capS) {
+        if (s->dSpinUp) HIPCHK(hipFree(s->dSpinUp));
+        s->dSpinUp = nullptr;
+        HIPCHK(hipMalloc(&s->dSpinUp, (size_t)s->capS * sizeof(int)));
+        HIPCHK(hipMemsetAsync(s->dSpinUp, 0, (size_t)s->capS * sizeof(int), e->stream));
+        if ((int)s->spinUp.size() >= s->N && tagged(s))
+            HIPCHK(hipMemcpyAsync(s->dSpinUp, s->spinUp.data(), (size_t)s->N * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));                 // spinUp may change before the copy would run
+        pe->tag_cap[k] = s->capS;
+    }
+    return 0;
+}
+
+// measureSpinUps() :600-665 of every member but its file: one launch writes every member's device tags, the
+// host lists follow with one synchronisation
+int pump_tag(mdqt_pump_ensemble* pe) {
+    mdqt_ensemble* e = pe->base;
+    const int J = (int)e->jobs.size();
+    char* slot = nullptr;
+    int idx = 0;
+    if (ens_ring_slot(e, &slot, &idx)) return -1;
+    PumpTagArgs* h = reinterpret_cast<PumpTagArgs*>(slot);
+    int maxn = 0;
+    for (int k = 0; k < J; ++k) {
+        if (member_buffers(pe, k)) return -1;
+        mdqt_ctx* s = e->jobs[k];
+        PumpTagArgs& a = h[k];
+        memset(&a, 0, sizeof a);
+        a.psi = s->dPsi; a.n = s->nloc; a.S = s->S;
+        a.gid0 = (uint64_t)s->lo; a.q = s->qidx; a.tags = s->dSpinUp; a.qc = s->qc;
+        maxn = std::max(maxn, a.n);
+    }
+    if (ens_upload(e, pe->dTag, slot, (size_t)J * sizeof(PumpTagArgs), idx)) return -1;
+    HIPCHK(launch_tag_spin_up_ens(pe->dTag, J, maxn, e->stream));
+    pe->launches++;
+    for (mdqt_ctx* s : e->jobs) {
+        s->spinUp.assign((size_t)(s->N > 0 ? s->N : 1), 0);
+        HIPCHK(hipMemcpyAsync(s->spinUp.data(), s->dSpinUp, (size_t)s->nloc * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (mdqt_ctx* s : e->jobs) {
+        int cnt = 0;
+        for (int i = 0; i < s->nloc; ++i) cnt += s->spinUp[i];
+        s->nSpinUp = cnt;
+    }
+    return 0;
+}
+
+// output() :799-935 (and, vaf >= 0, Zfunc(vaf) + printVAF) of every member: the velocity read-backs and the
+// batched tagged distribution queued on the ensemble's stream, one synchronisation, then each member's host
+// sums and files by output_pump's own code (pump_output_host, pump_vaf_host; Epotential() each member's call)
+int pump_output(mdqt_pump_ensemble* pe, int vaf) {
+    mdqt_ensemble* e = pe->base;
+    const int J = (int)e->jobs.size();
+    char* slot = nullptr;
+    int idx = 0;
+    if (ens_ring_slot(e, &slot, &idx)) return -1;
+    PumpKdeArgs* h = reinterpret_cast<PumpKdeArgs*>(slot);
+    int maxN = 0;
+    std::vector<std::vector<double>> Vs((size_t)J), Ps((size_t)J);
+    for (int k = 0; k < J; ++k) {
+        if (member_buffers(pe, k)) return -1;
+        mdqt_ctx* s = e->jobs[k];
+        PumpKdeArgs& a = h[k];
+        memset(&a, 0, sizeof a);
+        a.V = s->dV; a.tags = s->dSpinUp; a.N = s->N; a.S = s->S; a.bin0 = s->pumpBin0;
+        a.part = s->dTkde + (size_t)3 * TKDE_BINS; a.out = s->dTkde;
+        maxN = std::max(maxN, a.N);
+        Vs[k].assign((size_t)3 * s->S, 0.);
+        Ps[k].assign((size_t)3 * TKDE_BINS, 0.);
+        HIPCHK(hipMemcpyAsync(Vs[k].data(), s->dV, Vs[k].size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    }
+    if (ens_upload(e, pe->dKde, slot, (size_t)J * sizeof(PumpKdeArgs), idx)) return -1;
+    HIPCHK(launch_tagged_kde_ens(pe->dKde, J, maxN, e->stream));
+    pe->launches += 2;
+    for (int k = 0; k < J; ++k)
+        HIPCHK(hipMemcpyAsync(Ps[k].data(), e->jobs[k]->dTkde, Ps[k].size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int k = 0; k < J; ++k) {
+        mdqt_ctx* s = e->jobs[k];
+        const int N = s->N, S = s->S;
+        std::vector<double> V((size_t)3 * N);                    // [3][N], as mdqt_get_state gives it
+        for (int c = 0; c < 3; ++c) std::copy_n(Vs[k].begin() + (size_t)c * S, N, V.begin() + (size_t)c * N);
+        if (pump_output_host(s, V, Ps[k], nullptr, e->writer.get())) return -1;
+        if (vaf >= 0 && pump_vaf_host(s, V, vaf)) return -1;
+    }
+    return 0;
+}
+
+int pump_md_steps(mdqt_pump_ensemble* pe, int n) {
+    const bool moving = pe->base->jobs[0]->t > 0;
+    for (int k = 0; k < n; ++k) {
+        // t stays: at t > 0 every step but the call's last takes the next one's leading drift along
+        if (pump_step(pe, !moving || k == 0, moving && k + 1 < n)) return -1;
+        for (mdqt_ctx* s : pe->base->jobs) s->c0++;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" void mdqt_pump_ensemble_destroy(mdqt_pump_ensemble* pe) {
+    if (!pe) return;
+    if (pe->base) {
+        (void)hipSetDevice(pe->base->dev);
+        if (pe->base->stream) (void)hipStreamSynchronize(pe->base->stream);
+    }
+    for (auto& d : pe->dStep) if (d) (void)hipFree(d);
+    if (pe->dTag) (void)hipFree(pe->dTag);
+    if (pe->dKde) (void)hipFree(pe->dKde);
+    for (hipEvent_t ev : pe->evkick) (void)hipEventDestroy(ev);
+    mdqt_ensemble_destroy(pe->base);
+    delete pe;
+}
+
+extern "C" int mdqt_pump_ensemble_create(const mdqt_params* p, int njobs, mdqt_pump_ensemble** out) {
+    if (!p || !out) return set_error("mdqt_pump_ensemble_create: NULL argument");
+    *out = nullptr;
+    std::unique_ptr<mdqt_pump_ensemble, void (*)(mdqt_pump_ensemble*)> pe(new (std::nothrow) mdqt_pump_ensemble(),
+                                                                         mdqt_pump_ensemble_destroy);
+    if (!pe) return set_error("mdqt_pump_ensemble_create: out of memory");
+    if (ensemble_create(p, njobs, &pe->base, "mdqt_pump_ensemble_create", true)) return -1;
+    HIPCHK(hipSetDevice(pe->base->dev));
+    pe->kde_cap.assign((size_t)njobs, 0);
+    pe->tag_cap.assign((size_t)njobs, 0);
+    if (hipMalloc(&pe->dStep[0], (size_t)njobs * sizeof(PumpStepArgs)) != hipSuccess ||
+        hipMalloc(&pe->dStep[1], (size_t)njobs * sizeof(PumpStepArgs)) != hipSuccess ||
+        hipMalloc(&pe->dTag, (size_t)njobs * sizeof(PumpTagArgs)) != hipSuccess ||
+        hipMalloc(&pe->dKde, (size_t)njobs * sizeof(PumpKdeArgs)) != hipSuccess)
+        return set_error("mdqt_pump_ensemble_create: allocating the argument blocks of %d jobs failed", njobs);
+    *out = pe.release();
+    return 0;
+}
+
+extern "C" int mdqt_pump_ensemble_size(const mdqt_pump_ensemble* pe) { return pe && pe->base ? (int)pe->base->jobs.size() : -1; }
+
+extern "C" mdqt_ctx* mdqt_pump_ensemble_job(mdqt_pump_ensemble* pe, int k) {
+    if (!pe || !pe->base || k < 0 || k >= (int)pe->base->jobs.size()) {
+        set_error("mdqt_pump_ensemble_job: job index %d outside the ensemble", k);
+        return nullptr;
+    }
+    return pe->base->jobs[(size_t)k];
+}
+
+extern "C" int mdqt_pump_ensemble_set_option(mdqt_pump_ensemble* pe, const char* name, int value) {
+    if (!pe || !name) return set_error("mdqt_pump_ensemble_set_option: NULL argument");
+    for (mdqt_ctx* s : pe->base->jobs)
+        if (mdqt_set_option(s, name, value)) return -1;
+    return 0;
+}
+
+extern "C" int mdqt_pump_ensemble_init(mdqt_pump_ensemble* pe) {       // init() of every job
+    if (!pe) return set_error("NULL ensemble");
+    for (mdqt_ctx* s : pe->base->jobs) {
+        if (mdqt_init(s)) return -1;
+        s->spinUp.clear();
+        s->nSpinUp = 0;
+    }
+    return 0;
+}
+
+extern "C" int mdqt_pump_ensemble_md_steps(mdqt_pump_ensemble* pe, int n) {   // n x (step(); c0++) of every job
+    if (pump_check(pe, "mdqt_pump_ensemble_md_steps")) return -1;
+    if (n < 0) return set_error("negative step count");
+    HIPCHK(hipSetDevice(pe->base->dev));
+    return pump_md_steps(pe, n);
+}
+
+extern "C" int mdqt_pump_ensemble_qsteps(mdqt_pump_ensemble* pe, int n) {     // n x qstep() of every job
+    if (pump_check(pe, "mdqt_pump_ensemble_qsteps")) return -1;
+    if (n < 0) return set_error("negative step count");
+    HIPCHK(hipSetDevice(pe->base->dev));
+    return pump_qsteps(pe, n);
+}
+
+extern "C" int mdqt_pump_ensemble_tag_spin_up(mdqt_pump_ensemble* pe) {       // measureSpinUps() of every job
+    if (pump_check(pe, "mdqt_pump_ensemble_tag_spin_up")) return -1;
+    HIPCHK(hipSetDevice(pe->base->dev));
+    return pump_tag(pe);
+}
+
+extern "C" int mdqt_pump_ensemble_output(mdqt_pump_ensemble* pe) {            // output() of every job
+    if (pump_check(pe, "mdqt_pump_ensemble_output")) return -1;
+    HIPCHK(hipSetDevice(pe->base->dev));
+    if (pump_output(pe, -1)) return -1;
+    return flush_files(pe->base->jobs[0]);
+}
+
+extern "C" int mdqt_pump_ensemble_synchronize(mdqt_pump_ensemble* pe) {
+    if (!pe) return set_error("NULL ensemble");
+    HIPCHK(hipSetDevice(pe->base->dev));
+    HIPCHK(hipStreamSynchronize(pe->base->stream));
+    for (size_t k = 0; k < pe->base->jobs.size(); ++k)
+        if (pe->base->jobs[k]->hFlags[0] && !pe->base->jobs[k]->guard) {
+            pe->base->jobs[k]->guard = true;
+            return range_flag_error((int)k);
+        }
+    return 0;
+}
+
+extern "C" unsigned long long mdqt_pump_ensemble_launches(const mdqt_pump_ensemble* pe) {
+    return pe && pe->base ? pe->launches + pe->base->force_launches : 0;
+}
+
+// main() :981-1076 for every member at once, as mdqt_run_pump has it (mdqt_pump.cpp): the members are in
+// lockstep, so member 0's t and c0 drive the loop
+extern "C" int mdqt_pump_ensemble_run(mdqt_pump_ensemble* pe) {
+    if (!pe) return set_error("NULL ensemble");
+    mdqt_ensemble* e = pe->base;
+    for (mdqt_ctx* s : e->jobs) {
+        if (pump_setup_directories(s)) return -1;
+        s->spinUp.clear();
+        s->nSpinUp = 0;
+        s->pumpBin0 = -2000;
+    }
+    int recorded = 0;                                            // recordedSpinUps :81
+    if (e->jobs[0]->p.newRun == 1) {                             // :1036-1046
+        for (mdqt_ctx* s : e->jobs)
+            if (mdqt_init(s)) return -1;
+    } else {
+        for (mdqt_ctx* s : e->jobs)
+            if (pump_read_conditions(s, s->p.c0)) return -1;
+        recorded = 1;
+    }
+    std::fill(pe->tag_cap.begin(), pe->tag_cap.end(), 0);        // (readConditions allocates the tags anew)
+    if (pump_check(pe, "mdqt_pump_ensemble_run")) return -1;
+    HIPCHK(hipSetDevice(e->dev));
+    mdqt_ctx* a = e->jobs[0];
+    const double tpump = a->p.tpumpreal * 813490 * sqrt(a->p.density);      // :79
+    const double tendV0 = a->p.tstartV0 + tpump;                             // :80
+    const double tstartV0 = a->p.tstartV0;
+    const double tend = a->p.tmax + 0.0009;
+    const double dtQ = a->dtQ;
+    const int sf = a->p.sampleFreq, ratio = a->ratio;
+    int tsc = ratio;                                             // :1033
+    int pending = 0;                                             // queued qsteps (one fused launch)
+    double tv = a->t;                                            // the loop's t (the members' lags by `pending` qsteps)
+    bool lead_done = false;                                      // the next step's leading drift went with the last launch
+    auto flush = [&]() -> int {
+        if (pending > 0) {
+            if (pump_qsteps(pe, pending)) return -1;             // qstep() x pending :396-598
+            pending = 0;
+            if (a->t != tv) return set_error("mdqt_pump_ensemble_run: time bookkeeping mismatch");
+        }
+        return 0;
+    };
+    // After the MD step at hand (c0 already counted): does the loop reach the next MD step, at a t > 0, before
+    // anything reads R, V or F — the measurement, an output, the end of the run?  The loop's own conditions,
+    // run ahead on copies (both branches of the loop's tail advance t by the same t += dtQ).
+    auto folds = [&](double x, int c0n) -> bool {
+        for (int ts = 0;;) {
+            x += dtQ;
+            ts++;
+            if (!(x <= tend)) return false;
+            if (recorded == 0 && x >= tendV0) return false;
+            if ((c0n + 1) % sf == 0 && ts == 1 && recorded == 1) return false;
+            if (ts == ratio) return x > 0;
+        }
+    };
+    while (tv <= tend) {                                         // :1050
+        if (recorded == 0 && tv >= tendV0) {                     // :1052-1058
+            if (flush()) return -1;
+            if (pump_tag(pe)) return -1;
+            for (mdqt_ctx* s : e->jobs)
+                if (pump_spin_ups_file(s)) return -1;
+            recorded = 1;
+            if (pump_output(pe, 0)) return -1;
+        }
+        if ((a->c0 + 1) % sf == 0 && tsc == 1 && recorded == 1) {   // :1062-1069
+            if (flush()) return -1;
+            if (pump_output(pe, 1)) return -1;
+        }
+        if (tsc == ratio) {                                      // :1070-1074
+            if (flush()) return -1;
+            const bool fold = folds(tv, a->c0 + 1);
+            if (pump_step(pe, !lead_done, fold)) return -1;
+            lead_done = fold;
+            for (mdqt_ctx* s : e->jobs) s->c0++;
+            tsc = 0;
+        }
+        if (tv < tendV0 && tv > tstartV0) {                      // :1075-1077 qstep()
+            pending++;
+            tv += dtQ;                                           // qstep's t += dtQuant :597
+            if (pending == MAXSUB && flush()) return -1;
+        } else {                                                 // :1078-1080
+            if (flush()) return -1;
+            for (mdqt_ctx* s : e->jobs) s->t += s->dtQ;
+            tv = a->t;
+        }
+        tsc++;
+    }
+    if (flush()) return -1;
+    if (lead_done) return set_error("mdqt_pump_ensemble_run: a folded drift without its step");
+    if (flush_files(a)) return -1;                               // the shared pool: every member's files
+    for (mdqt_ctx* s : e->jobs)
+        if (pump_write_conditions(s, s->c0)) return -1;          // :1084
+    return 0;
+}
+
+extern "C" int mdqt_pump_ensemble_enable_timing(mdqt_pump_ensemble* pe, int on) {
+    if (!pe) return set_error("NULL ensemble");
+    pe->evkick_used = 0;
+    return mdqt_ensemble_enable_timing(pe->base, on);
+}
+
+// the batched kernels' own durations (their dispatch timestamps) since the last call: out[9] = force ms (sum),
+// force launches, QT ms, QT launches, kick launch ms, kick launches, then the medians of the three (ms); resets
+extern "C" int mdqt_pump_ensemble_kernel_times(mdqt_pump_ensemble* pe, double* out, int n) {
+    if (!pe || !out) return set_error("mdqt_pump_ensemble_kernel_times: NULL argument");
+    if (n < 9) return set_error("mdqt_pump_ensemble_kernel_times: need 9 doubles");
+    double b[6];
+    if (mdqt_ensemble_kernel_times(pe->base, b, 6)) return -1;
+    std::vector<double> ms;
+    double tot = 0.;
+    for (int i = 0; i + 1 < pe->evkick_used; i += 2) {
+        float x = 0.f;
+        HIPCHK(hipEventElapsedTime(&x, pe->evkick[i], pe->evkick[i + 1]));
+        ms.push_back(x);
+        tot += x;
+    }
+    std::sort(ms.begin(), ms.end());
+    pe->evkick_used = 0;
+    out[0] = b[0]; out[1] = b[1]; out[2] = b[2]; out[3] = b[3];
+    out[4] = tot; out[5] = (double)ms.size();
+    out[6] = b[4]; out[7] = b[5]; out[8] = ms.empty() ? 0. : ms[ms.size() / 2];
+    return 0;
+}

@@ -16,6 +16,7 @@
 // substep; tests/test_gpu_parity.py bounds it against the oracle).  The thread-per-ion and
 // lane-per-state kernels below perform the same operations in the same order: bit-identical.
 #include "mdqt_qtfast.hpp"
+#include "mdqt_pump_device.hpp"   // the body k_tag_spin_up shares with the pump ensemble's batched kernel
 
 namespace mdqt {
 
@@ -308,27 +309,7 @@ __global__ __launch_bounds__(256) void k_tag_spin_up(const double* __restrict__ 
                                                      uint64_t q, QTConst qc, int* __restrict__ tags) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    double nr[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const double re = psi[(size_t)(2 * k) * S + i], im = psi[(size_t)(2 * k + 1) * S + i];
-        nr[k] = re * re + im * im;                                   // std::norm
-    }
-    double rnd, r2;
-    philox_pair(qc, gid0 + (uint64_t)i, q, 3, rnd, r2);
-    int up;
-    if (qc.model == 3) {                                             // 422 (:592-631)
-        if (rnd < nr[0]) up = 1;
-        else if (rnd < nr[0] + nr[2]) up = r2 < 1. / 3;
-        else if (rnd < nr[0] + nr[2] + nr[3]) up = r2 < 2. / 3;
-        else up = 0;
-    } else {                                                         // 408 (:600-640)
-        if (rnd < nr[0] + nr[2]) up = 1;
-        else if (rnd < nr[0] + nr[2] + nr[3]) up = r2 < 2. / 3;
-        else if (rnd < nr[0] + nr[2] + nr[3] + nr[4]) up = r2 < 1. / 3;
-        else up = 0;
-    }
-    tags[i] = up;
+    tag_spin_up_ion(psi, i, S, gid0, q, qc, tags);                   // mdqt_pump_device.hpp
 }
 
 hipError_t launch_tag_spin_up(const double* psi, int n, int S, uint64_t gid0, uint64_t q, const QTConst& qc,

@@ -217,6 +217,10 @@ class Simulation:
     def md_steps(self, n: int):
         check(lib().mdqt_md_steps(self.h, int(n)), "md_steps")
 
+    def pump_md_steps(self, n: int):
+        """n x (step(); c0++) of the optical-pumping programs at the context's t (mdqt_pump_md_steps)"""
+        check(lib().mdqt_pump_md_steps(self.h, int(n)), "pump_md_steps")
+
     def tag_spin_up(self):
         """measureSpinUps / tagParticles of the optical-pumping models: (tags[N], n_up)"""
         tags = np.zeros(self.N, dtype=np.int32)
