@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "../../include/mdmc.h"
-#include "mdqt_ctx.hpp"    // HIPCHK, mdqt::set_error, mdqt::take_events
+#include "mdqt_ctx.hpp"    // HIPCHK, mdqt::set_error, mdqt_batch.hpp's PinRing and LaunchTimer
 #include "mdqt_mt32.hpp"   // Mt32: the reference's std::mt19937 with the state in plain view
 
 struct mdmc_ctx {
@@ -59,17 +59,6 @@ struct mdmc_ctx {
     unsigned short x48[3] = {0x330E, 0xABCD, 0x1234};   // drand48's default state (no srand48 in QTT)
 };
 
-// A pinned ring of equal slots for argument blocks on their way to the device: the host fills a slot, one
-// hipMemcpyAsync reads it in stream order, and the event recorded behind the copy says when the slot may be
-// written again (the host queues far ahead of the device, so a slot is not free when the call returns).
-struct mdmc_pin_ring {
-    char* base = nullptr;
-    size_t slot = 0;
-    int next = 0;
-    std::vector<hipEvent_t> ev;        // one per slot
-    std::vector<char> busy;            // a copy of the slot has been queued
-};
-
 // J contexts (job + k, seed + k) annealed by one launch (mdmc_ensemble.cpp).  Every member keeps its own
 // stream for everything that is its own; the ensemble's stream carries the batched anneal, the batched MD
 // steps and per-step observables (md_batch 1), and their argument blocks.
@@ -82,8 +71,7 @@ struct mdmc_ensemble {
     uint32_t* hMT = nullptr;           // pinned [J][625]: the chains' mt19937 states coming back
     unsigned long long* hAcc = nullptr;   // pinned [J]
     bool timing = false;
-    std::vector<hipEvent_t> evpool;    // the anneal launches' own timestamps (pairs)
-    int evused = 0;
+    mdqt::LaunchTimer annealTimer;     // the anneal launches' own timestamps
     // wall time of the last run's stages (ms, with timing on): anneal, pre-record MD, QT pump, recorded MD,
     // autocorrelations, the rest
     static constexpr int kStages = 6;
@@ -99,7 +87,7 @@ struct mdmc_ensemble {
     mdqt::MDObsArgs* dObs = nullptr;
     mdqt::VVArgs* dVVc = nullptr;
     size_t hdrBytes = 0;               // of the first three
-    mdmc_pin_ring hdrRing, vvRing;     // a stretch's blocks; a collisional step's VVArgs [J]
+    mdqt::PinRing hdrRing, vvRing;     // a stretch's blocks (4 slots); a collisional step's VVArgs [J] (64 slots)
     bool open = false;                 // inside a stretch: the members' streams are fenced behind `stream`
     int parity = 0;                    // which of the two block sets the next step takes
     int obsCap = 0;                    // rows of the members' dTemp / dMom at the stretch's start
@@ -107,8 +95,7 @@ struct mdmc_ensemble {
     std::vector<unsigned long long> skip;   // [J] mt19937 words of collisionless steps still to discard
     std::vector<hipEvent_t> evMember;  // [J] fences: a member's stream -> `stream`
     hipEvent_t evEns = nullptr;        // `stream` -> the members' streams
-    std::vector<hipEvent_t> evForce, evVV;   // the batched force / velocity-Verlet launches' timestamps (pairs)
-    int usedForce = 0, usedVV = 0;
+    mdqt::LaunchTimer forceTimer, vvTimer;   // the batched force / velocity-Verlet launches' timestamps
 };
 
 namespace mdmc {

@@ -7,7 +7,8 @@
 // own stream, one host thread, so they overlap on the chip: the single context's code on the single
 // context's arguments.  Mode 1 steps all members with one force and one velocity-Verlet launch per step on
 // the ensemble's stream ("batched MD stretches" below), again the single-job kernels' bodies on each member's
-// own argument block.
+// own argument block.  The stretches' argument blocks travel through two pinned rings and the launches are timed
+// by event pairs: mdqt_batch.hpp's PinRing and LaunchTimer, shared with the MDQT ensembles.
 #include <algorithm>
 #include <memory>
 
@@ -17,8 +18,6 @@ using namespace mdqt;
 
 namespace {
 
-constexpr int kEnsembleMaxJobs = 1024;
-
 int sync_members(mdmc_ensemble* e) {
     for (mdmc_ctx* c : e->jobs) HIPCHK(hipStreamSynchronize(c->st));
     return 0;
@@ -26,38 +25,6 @@ int sync_members(mdmc_ensemble* e) {
 
 constexpr int kHdrSlots = 4;     // stretches whose blocks may be on their way at once
 constexpr int kVVSlots = 64;     // collisional steps whose blocks may be on their way at once
-
-int ring_create(mdmc_pin_ring& r, size_t slot, int n) {
-    r.slot = slot;
-    if (hipHostMalloc((void**)&r.base, slot * (size_t)n, hipHostMallocDefault) != hipSuccess)
-        return set_error("mdmc_ensemble_create: pinned allocation of the MD argument blocks failed");
-    r.busy.assign((size_t)n, 0);
-    for (int i = 0; i < n; ++i) {
-        hipEvent_t ev = nullptr;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        r.ev.push_back(ev);
-    }
-    return 0;
-}
-
-// the next slot, once the copy that last read it has run (kHdrSlots stretches / kVVSlots steps ago)
-int ring_take(mdmc_pin_ring& r, char** slot, int* idx) {
-    const int i = r.next;
-    r.next = (i + 1) % (int)r.ev.size();
-    if (r.busy[(size_t)i]) HIPCHK(hipEventSynchronize(r.ev[(size_t)i]));
-    r.busy[(size_t)i] = 0;
-    *slot = r.base + r.slot * (size_t)i;
-    *idx = i;
-    return 0;
-}
-
-// one copy of the slot in stream order, the slot's event behind it
-int ring_send(mdmc_pin_ring& r, int idx, void* dst, size_t bytes, hipStream_t s) {
-    HIPCHK(hipMemcpyAsync(dst, r.base + r.slot * (size_t)idx, bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(r.ev[(size_t)idx], s));
-    r.busy[(size_t)idx] = 1;
-    return 0;
-}
 
 int md_blocks_create(mdmc_ensemble* e) {
     const size_t J = e->jobs.size();
@@ -69,7 +36,9 @@ int md_blocks_create(mdmc_ensemble* e) {
     e->dVV = reinterpret_cast<VVArgs*>(e->dBlocks + n3);
     e->dObs = reinterpret_cast<MDObsArgs*>(e->dBlocks + n3 + vv);
     e->dVVc = reinterpret_cast<VVArgs*>(e->dBlocks + e->hdrBytes);
-    if (ring_create(e->hdrRing, e->hdrBytes, kHdrSlots) || ring_create(e->vvRing, J * sizeof(VVArgs), kVVSlots)) return -1;
+    if (e->hdrRing.create(e->hdrBytes, kHdrSlots, hipEventDisableTiming) ||
+        e->vvRing.create(J * sizeof(VVArgs), kVVSlots, hipEventDisableTiming))
+        return -1;
     e->coll.assign(J, 0);
     e->skip.assign(J, 0ull);
     for (size_t k = 0; k < J; ++k) {
@@ -116,7 +85,7 @@ int mdmc::ensemble_md_begin(mdmc_ensemble* e) {
     }
     char* h = nullptr;
     int slot = 0;
-    if (ring_take(e->hdrRing, &h, &slot)) return -1;
+    if (e->hdrRing.take(&h, &slot)) return -1;
     N3Args* n3 = reinterpret_cast<N3Args*>(h);
     VVArgs* vv = reinterpret_cast<VVArgs*>(h + 2 * J * sizeof(N3Args));
     MDObsArgs* ob = reinterpret_cast<MDObsArgs*>(h + 2 * J * (sizeof(N3Args) + sizeof(VVArgs)));
@@ -141,7 +110,7 @@ int mdmc::ensemble_md_begin(mdmc_ensemble* e) {
         e->coll[k] = c->p.timeStep * c->collisionFreq > 0;
         e->skip[k] = 0;
     }
-    if (ring_send(e->hdrRing, slot, e->dBlocks, e->hdrBytes, e->stream)) return -1;
+    if (e->hdrRing.send(slot, e->dBlocks, e->hdrBytes, e->stream)) return -1;
     e->parity = 0;
     e->open = true;
     return 0;
@@ -154,8 +123,7 @@ int mdmc::ensemble_md_step(mdmc_ensemble* e) {
     const int par = e->parity;
     for (mdmc_ctx* c : e->jobs) std::swap(c->dR, c->dRn);
     hipEvent_t f0 = nullptr, f1 = nullptr, v0 = nullptr, v1 = nullptr;
-    if (e->timing && (take_events(e->evForce, e->usedForce, &f0, &f1) || take_events(e->evVV, e->usedVV, &v0, &v1)))
-        return -1;
+    if (e->timing && (e->forceTimer.take(&f0, &f1) || e->vvTimer.take(&v0, &v1))) return -1;
     // force_kernel 1: variant 2 (fast values, the reference's exact pair set), 0: exact            :508
     HIPCHK(launch_forces_n3_mdmc_ens(e->dN3 + par * J, (int)J, c0->npairs, c0->p.force_kernel == 1 ? 2 : 0, e->stream, f0, f1));
     ++e->mdLaunches;
@@ -166,7 +134,7 @@ int mdmc::ensemble_md_step(mdmc_ensemble* e) {
     if (any) {
         char* h = nullptr;
         int slot = 0;
-        if (ring_take(e->vvRing, &h, &slot)) return -1;
+        if (e->vvRing.take(&h, &slot)) return -1;
         VVArgs* vv = reinterpret_cast<VVArgs*>(h);
         for (size_t k = 0; k < J; ++k) {
             mdmc_ctx* c = e->jobs[k];
@@ -178,7 +146,7 @@ int mdmc::ensemble_md_step(mdmc_ensemble* e) {
             mdmc::vv_args(c, hits, nh, vv[k]);
             max_hits = std::max(max_hits, nh);
         }
-        if (ring_send(e->vvRing, slot, e->dVVc, J * sizeof(VVArgs), e->stream)) return -1;
+        if (e->vvRing.send(slot, e->dVVc, J * sizeof(VVArgs), e->stream)) return -1;
         blocks = e->dVVc;
     } else {
         for (size_t k = 0; k < J; ++k) e->skip[k] += 2ull * e->jobs[k]->N;
@@ -263,19 +231,15 @@ extern "C" void mdmc_ensemble_destroy(mdmc_ensemble* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (size_t k = e->jobs.size(); k-- > 0;) mdmc_destroy(e->jobs[k]);
     if (e->dBlocks) (void)hipFree(e->dBlocks);
-    for (mdmc_pin_ring* r : {&e->hdrRing, &e->vvRing}) {
-        if (r->base) (void)hipHostFree(r->base);
-        for (hipEvent_t ev : r->ev) (void)hipEventDestroy(ev);
-    }
+    e->hdrRing.destroy();
+    e->vvRing.destroy();
     for (hipEvent_t ev : e->evMember) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->evForce) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->evVV) (void)hipEventDestroy(ev);
+    for (LaunchTimer* t : {&e->annealTimer, &e->forceTimer, &e->vvTimer}) t->destroy();
     if (e->evEns) (void)hipEventDestroy(e->evEns);
     if (e->dArgs) (void)hipFree(e->dArgs);
     if (e->hArgs) (void)hipHostFree(e->hArgs);
     if (e->hMT) (void)hipHostFree(e->hMT);
     if (e->hAcc) (void)hipHostFree(e->hAcc);
-    for (hipEvent_t ev : e->evpool) (void)hipEventDestroy(ev);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -364,7 +328,7 @@ int mdmc::ensemble_anneal(mdmc_ensemble* e, int nsteps, long long* accepted) {
         const MCArgs* h = e->hArgs + (n == mdmc::kAnnealChunk ? 0 : J);
         HIPCHK(hipMemcpyAsync(e->dArgs, h, J * sizeof(MCArgs), hipMemcpyHostToDevice, e->stream));
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (e->timing && take_events(e->evpool, e->evused, &e0, &e1)) return -1;
+        if (e->timing && e->annealTimer.take(&e0, &e1)) return -1;
         HIPCHK(launch_monte_carlo_ens(e->dArgs, h[0], (int)J, e->stream, e0, e1));
         done += n;
     }
@@ -424,7 +388,7 @@ extern "C" int mdmc_ensemble_run(mdmc_ensemble* e, int verbose) {
 extern "C" int mdmc_ensemble_enable_timing(mdmc_ensemble* e, int on) {
     if (!e) return set_error("NULL ensemble");
     e->timing = on > 0;
-    e->evused = e->usedForce = e->usedVV = 0;
+    for (LaunchTimer* t : {&e->annealTimer, &e->forceTimer, &e->vvTimer}) t->reset();
     return 0;
 }
 
@@ -446,29 +410,6 @@ extern "C" int mdmc_ensemble_md_launches(mdmc_ensemble* e, unsigned long long* o
     return 0;
 }
 
-namespace {
-
-// sum (ms), launches, median, minimum, maximum (ms) of the launches timed by pairs of events; resets the list
-int launch_stats(std::vector<hipEvent_t>& pool, int& used, double* v) {
-    std::vector<double> ms;
-    double tot = 0.;
-    for (int i = 0; i + 1 < used; i += 2) {
-        float x = 0.f;
-        HIPCHK(hipEventElapsedTime(&x, pool[(size_t)i], pool[(size_t)i + 1]));
-        ms.push_back(x);
-        tot += x;
-    }
-    std::sort(ms.begin(), ms.end());
-    v[0] = tot; v[1] = (double)ms.size();
-    v[2] = ms.empty() ? 0. : ms[ms.size() / 2];
-    v[3] = ms.empty() ? 0. : ms.front();
-    v[4] = ms.empty() ? 0. : ms.back();
-    used = 0;
-    return 0;
-}
-
-}  // namespace
-
 // the batched launches' own durations (their dispatch timestamps) since the last call: out[0..5) = the anneal's
 // sum (ms), launches, median, minimum, maximum (ms); out[5..11) = wall time (ms) of the last run's stages: anneal,
 // pre-record MD, QT pump, recorded MD, autocorrelations, the rest; out[11..16) and out[16..21) = the five figures
@@ -480,8 +421,8 @@ extern "C" int mdmc_ensemble_kernel_times(mdmc_ensemble* e, double* out, int n) 
     HIPCHK(hipStreamSynchronize(e->stream));
     constexpr int kOut = 5 + mdmc_ensemble::kStages + 10;
     double v[kOut] = {};
-    if (launch_stats(e->evpool, e->evused, v) || launch_stats(e->evForce, e->usedForce, v + 5 + mdmc_ensemble::kStages) ||
-        launch_stats(e->evVV, e->usedVV, v + 10 + mdmc_ensemble::kStages))
+    if (e->annealTimer.stats(v) || e->forceTimer.stats(v + 5 + mdmc_ensemble::kStages) ||
+        e->vvTimer.stats(v + 10 + mdmc_ensemble::kStages))
         return -1;
     std::copy(e->stage_ms, e->stage_ms + mdmc_ensemble::kStages, v + 5);
     for (int i = 0; i < n && i < kOut; ++i) out[i] = v[i];

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/mdqt.h"
+#include "mdqt_batch.hpp"
 #include "mdqt_internal.hpp"
 #include "mdqt_writer.hpp"
 
@@ -213,8 +214,8 @@ struct mdqt_ctx {
     unsigned tperiod = 1, tcount[2] = {0, 0};   // bracket launches k = toffset mod tperiod of each kind
     unsigned toffset = 0;                        // tperiod / 2 unless mdqt_enable_timing_at
                                                 // (mid-period: not the first launch after a sync)
-    std::vector<hipEvent_t> evpool[4];          // 2: the Newton-3 block kernel's own timestamps (a timed force call)
-    int evused[4] = {0, 0, 0, 0};               // 3: the block kernel of the potential calls (Epotential on the blocks)
+    mdqt::LaunchTimer timers[4];                // 2: the Newton-3 block kernel's own timestamps (a timed force call)
+                                                // 3: the block kernel of the potential calls (Epotential on the blocks)
     // force-call breakdown (timing kind bit 3): per timed block-scheme force call the
     // events between its stages on the context stream — the preceding position all-gather (ag), then
     // m[0] start | sort + boxes | m[1] | plan | m[2] | block kernel | m[3] | slot reduction | m[4] |
@@ -235,16 +236,10 @@ struct mdqt_ensemble {
     mdqt::SubstepArgs* dSub = nullptr;                   // [sub_blocks] the batched QT launches' blocks: [launch][J]
     int sub_blocks = 0;                            // max(J, 1024): mdqt_ensemble_md_steps builds launches ahead
     std::vector<mdqt::N3Args> force_held;                // what dForce holds
-    static constexpr int kRing = 8;
-    char* ring = nullptr;                          // pinned, kRing slots of slot_bytes
-    size_t slot_bytes = 0;
-    hipEvent_t ring_ev[kRing] = {};
-    bool ring_used[kRing] = {};
-    unsigned ring_pos = 0;
+    mdqt::PinRing ring;                            // 8 slots: a launch's blocks of either kind, or md_steps' blocks ahead
     int qt_waves = 0;                              // option "qt_waves": register budget of the production QT instance
     bool timing = false;
-    std::vector<hipEvent_t> evpool[2];             // 0 = force launches, 1 = QT launches (start, stop, ...)
-    int evused[2] = {0, 0};
+    mdqt::LaunchTimer timers[2];                   // 0 = force launches, 1 = QT launches
     unsigned long long force_launches = 0;         // force launches issued by ens_forces (batched + the row members' own)
 };
 
@@ -258,8 +253,7 @@ struct mdqt_pump_ensemble {
     mdqt::PumpKdeArgs* dKde = nullptr;                   // [J]
     std::vector<int> kde_cap, tag_cap;                   // chunks / ints the ensemble allocated of each member's dTkde / dSpinUp
     unsigned long long launches = 0;                     // the pump kernels' launches (the force launches: base)
-    std::vector<hipEvent_t> evkick;                      // the kick launches' timestamps (start, stop, ...)
-    int evkick_used = 0;
+    mdqt::LaunchTimer kick_timer;                        // the kick launches' timestamps
 };
 
 namespace mdqt {
@@ -341,14 +335,17 @@ int pump_read_conditions(mdqt_ctx* s, int c0);
 
 // mdqt_ensemble.cpp: the ensemble's machinery the pump ensemble reuses
 int ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, const char* what, bool pump);
-int ens_ring_slot(mdqt_ensemble* e, char** slot, int* idx);
-int ens_upload(mdqt_ensemble* e, void* dst, const void* src_slot, size_t bytes, int idx);
+inline bool tagged(const mdqt_ctx* s) { return !s->spinUp.empty(); }   // measureSpinUps() has run (pump programs)
+int ens_check(const mdqt_ensemble* e, const char* what, bool pump = false);
 int ens_forces(mdqt_ensemble* e);
+// the fused step();qstep() (do_step 1) or qstep() (0) launches of every member: `launch` issues one
+using EnsQtLaunch = std::function<hipError_t(const SubstepArgs& first, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst)>;
+int ens_qt_chunks(mdqt_ensemble* e, int n, int do_step, const EnsQtLaunch& launch);
+int ens_range_flags(mdqt_ensemble* e, bool drain = true);
 
 // mdqt_options.cpp (timing events)
 int mark(mdqt_ctx* s, int k);
-int take_events(std::vector<hipEvent_t>& pool, int& used, hipEvent_t* e0, hipEvent_t* e1);
-inline int take_events(mdqt_ctx* s, int k, hipEvent_t* e0, hipEvent_t* e1) { return take_events(s->evpool[k], s->evused[k], e0, e1); }
+inline int take_events(mdqt_ctx* s, int k, hipEvent_t* e0, hipEvent_t* e1) { return s->timers[k].take(e0, e1); }
 hipEvent_t bd_event(mdqt_ctx* s);
 bool force_timed_next(const mdqt_ctx* s);
 

@@ -726,8 +726,7 @@ extern "C" void mdqt_destroy(mdqt_ctx* s) {
     if (s->dX48) (void)hipFree(s->dX48);
     if (s->hFlags) (void)hipHostFree((void*)s->hFlags);
     comm_destroy(s);
-    for (auto& pool : s->evpool)
-        for (hipEvent_t ev : pool) (void)hipEventDestroy(ev);
+    for (LaunchTimer& t : s->timers) t.destroy();
     for (auto& c : s->bdcalls) {
         for (hipEvent_t ev : c.m) if (ev) (void)hipEventDestroy(ev);
         if (c.ag0) (void)hipEventDestroy(c.ag0);

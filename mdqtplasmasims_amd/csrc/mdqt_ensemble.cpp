@@ -9,9 +9,9 @@
 //
 // Argument hand-off.  The force blocks (N3Args) do not change from step to step: they are uploaded
 // when they differ from what the device holds (after init, a resize, an option, the range guard).  The
-// QT blocks (SubstepArgs: t[], q0, nseg change every launch) are built in a slot of a pinned ring and
-// copied in stream order before the launches that read them; a slot is reused after the event behind
-// its copy has completed.  mdqt_ensemble_substeps and mdqt_ensemble_run copy one launch's blocks just
+// QT blocks (SubstepArgs: t[], q0, nseg change every launch) are built in a slot of the pinned ring
+// (mdqt_batch.hpp: PinRing, 8 slots) and copied in stream order before the launches that read them; a slot
+// is reused after the event behind its copy has completed.  mdqt_ensemble_substeps and mdqt_ensemble_run copy one launch's blocks just
 // before it; mdqt_ensemble_md_steps builds the blocks of up to 64 MD steps ahead and copies them at once
 // (ens_md_steps has the reason and the numbers).
 
@@ -22,31 +22,15 @@
 using namespace mdqt;
 
 namespace {
-constexpr int kEnsembleMaxJobs = 1024;
+constexpr int kRingSlots = 8;   // launches (or md_steps' batches of launches) whose blocks may be on their way at once
 }  // namespace
 
-// a pinned slot nobody reads any more
-int mdqt::ens_ring_slot(mdqt_ensemble* e, char** slot, int* idx) {
-    const int i = (int)(e->ring_pos++ % mdqt_ensemble::kRing);
-    if (e->ring_used[i]) HIPCHK(hipEventSynchronize(e->ring_ev[i]));
-    *slot = e->ring + (size_t)i * e->slot_bytes;
-    *idx = i;
-    return 0;
-}
-
-int mdqt::ens_upload(mdqt_ensemble* e, void* dst, const void* src_slot, size_t bytes, int idx) {
-    HIPCHK(hipMemcpyAsync(dst, src_slot, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipEventRecord(e->ring_ev[idx], e->stream));
-    e->ring_used[idx] = true;
-    return 0;
-}
-
-namespace {
-
-// Every batched call: the members still are what the batched kernels cover, and still in lockstep.
+// Every batched call: the members still are what the batched kernels cover, and still in lockstep — t
+// (bitwise), the qstep index, c0 and, for the pump programs, the tagged / untagged flag.  Nothing is
+// launched before this has passed.
 // The pending-force state is NOT compared: it is per job by design (a one-tile job never has pending
 // slots; mdqt_get_state on a member settles that member's) and each QT block takes its own nseg.
-int ens_check(const mdqt_ensemble* e, const char* what) {
+int mdqt::ens_check(const mdqt_ensemble* e, const char* what, bool pump) {
     if (!e) return set_error("%s: NULL ensemble", what);
     const mdqt_ctx* a = e->jobs[0];
     for (size_t k = 0; k < e->jobs.size(); ++k) {
@@ -56,17 +40,22 @@ int ens_check(const mdqt_ensemble* e, const char* what) {
             return set_error("%s: job index %zu has the option overlap / fused_step set (one system per launch)", what, k);
         if (s->qt_math != 2) return set_error("%s: job index %zu has qt_math %d (the batched QT kernels are qt_math 2)", what, k, s->qt_math);
         if (s->substep_mode == 1) return set_error("%s: job index %zu has substep_kernel 1 (the batched QT kernels are the lane kernels)", what, k);
-        if (s->N < 1) return set_error("%s: job index %zu has no ions (mdqt_ensemble_init or mdqt_set_state first)", what, k);
+        if (s->N < 1) return set_error("%s: job index %zu has no ions (the ensemble's init or mdqt_set_state first)", what, k);
         if (s->use_n3b || s->N > 65536)
             return set_error("%s: job index %zu has N = %d: beyond the Newton-3 tile scheme (N <= 65,536)", what, k, s->N);
         if (s->force_arrive || s->sub_stream || !s->local.empty()) return set_error("%s: job index %zu is part of another scheme", what, k);
-        if (memcmp(&s->t, &a->t, sizeof(double)) || s->qidx != a->qidx || s->c0 != a->c0)
-            return set_error("%s: job index %zu is out of step with job index 0 (t %.17g / %.17g, qstep %llu / %llu, c0 %d / %d): "
+        if (memcmp(&s->t, &a->t, sizeof(double)) || s->qidx != a->qidx || s->c0 != a->c0 || (pump && tagged(s) != tagged(a))) {
+            char tags[32] = "";
+            if (pump) snprintf(tags, sizeof tags, ", tagged %d / %d", (int)tagged(s), (int)tagged(a));
+            return set_error("%s: job index %zu is out of step with job index 0 (t %.17g / %.17g, qstep %llu / %llu, c0 %d / %d%s): "
                              "a member stepped on its own ends the ensemble's stepping",
-                             what, k, s->t, a->t, (unsigned long long)s->qidx, (unsigned long long)a->qidx, s->c0, a->c0);
+                             what, k, s->t, a->t, (unsigned long long)s->qidx, (unsigned long long)a->qidx, s->c0, a->c0, tags);
+        }
     }
     return 0;
 }
+
+namespace {
 
 // The force blocks of the members on the Newton-3 tiles (packed, in job order), uploaded when they differ
 // from what the device holds
@@ -90,22 +79,13 @@ int ens_force_blocks(mdqt_ensemble* e, EnsForce& f) {
         f.maxp = std::max(f.maxp, a.npairs);
         f.h.push_back(a);
     }
-    const size_t bytes = f.h.size() * sizeof(N3Args);
-    if (!f.h.empty() && (f.h.size() != e->force_held.size() || memcmp(f.h.data(), e->force_held.data(), bytes))) {
-        char* slot = nullptr;
-        int idx = 0;
-        if (ens_ring_slot(e, &slot, &idx)) return -1;
-        memcpy(slot, f.h.data(), bytes);
-        if (ens_upload(e, e->dForce, slot, bytes, idx)) return -1;
-        e->force_held = f.h;
-    }
-    return 0;
+    return e->ring.send_if_changed(f.h, e->force_held, e->dForce, e->stream);
 }
 
 int ens_force_launch(mdqt_ensemble* e, const EnsForce& f) {
     if (f.h.empty()) return 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e->timing && take_events(e->evpool[0], e->evused[0], &e0, &e1)) return -1;
+    if (e->timing && e->timers[0].take(&e0, &e1)) return -1;
     HIPCHK(launch_forces_n3_ens(e->dForce, (int)f.h.size(), f.maxp, f.variant, f.guard, e->stream, e0, e1));
     e->force_launches++;
     return 0;
@@ -127,31 +107,29 @@ int mdqt::ens_forces(mdqt_ensemble* e) {
     return 0;
 }
 
-namespace {
-
-// run_substeps(s, n, 1, 1, 1) of every member: chunks of at most MAXSUB, one launch per chunk
-int ens_substeps(mdqt_ensemble* e, int n) {
+// run_substeps(s, n, do_step, 1, 1) of every member: chunks of at most MAXSUB, one launch per chunk
+int mdqt::ens_qt_chunks(mdqt_ensemble* e, int n, int do_step, const EnsQtLaunch& launch) {
     const int J = (int)e->jobs.size();
     const int do_qt = e->jobs[0]->p.qt_enabled ? 1 : 0;
     while (n > 0) {
         const int m = n < MAXSUB ? n : MAXSUB;
         char* slot = nullptr;
         int idx = 0;
-        if (ens_ring_slot(e, &slot, &idx)) return -1;
+        if (e->ring.take(&slot, &idx)) return -1;
         SubstepArgs* h = reinterpret_cast<SubstepArgs*>(slot);
         double t = 0.;
         int maxn = 0;
         for (int k = 0; k < J; ++k) {
             mdqt_ctx* s = e->jobs[k];
-            t = substep_args(s, h[k], m, 1, do_qt, 1);
+            t = substep_args(s, h[k], m, do_step, do_qt, 1);
             s->f_pending = false;
             maxn = std::max(maxn, h[k].n);
         }
-        if (ens_upload(e, e->dSub, slot, (size_t)J * sizeof(SubstepArgs), idx)) return -1;
+        if (e->ring.send(idx, e->dSub, (size_t)J * sizeof(SubstepArgs), e->stream)) return -1;
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (e->timing && take_events(e->evpool[1], e->evused[1], &e0, &e1)) return -1;
+        if (e->timing && e->timers[1].take(&e0, &e1)) return -1;
         int inst = 0;
-        HIPCHK(launch_substeps_r_ens(e->dSub, h[0], J, maxn, e->jobs[0]->dFTab, e->qt_waves, e->stream, e0, e1, &inst));
+        HIPCHK(launch(h[0], maxn, e0, e1, &inst));
         for (int k = 0; k < J; ++k) {
             mdqt_ctx* s = e->jobs[k];
             s->last_qt_kernel = inst;
@@ -166,7 +144,7 @@ int ens_substeps(mdqt_ensemble* e, int n) {
 
 // check_range_flag of every member with one synchronisation (drain), or, inside the MD-step loops, the
 // members' words as they stand (host loads: what completed launches raised)
-int ens_range_flags(mdqt_ensemble* e, bool drain = true) {
+int mdqt::ens_range_flags(mdqt_ensemble* e, bool drain) {
     const int J = (int)e->jobs.size();
     if (drain) HIPCHK(hipStreamSynchronize(e->stream));
     int first = -1;
@@ -176,6 +154,15 @@ int ens_range_flags(mdqt_ensemble* e, bool drain = true) {
             if (first < 0) first = k;
         }
     return first >= 0 ? range_flag_error(first) : 0;
+}
+
+namespace {
+
+// n x (step(); qstep()) of every member
+int ens_substeps(mdqt_ensemble* e, int n) {
+    return ens_qt_chunks(e, n, 1, [e](const SubstepArgs& first, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst) {
+        return launch_substeps_r_ens(e->dSub, first, (int)e->jobs.size(), maxn, e->jobs[0]->dFTab, e->qt_waves, e->stream, e0, e1, inst);
+    });
 }
 
 // n MD steps without the argument hand-off inside them.  A copy between two launches costs more than
@@ -209,7 +196,7 @@ int ens_md_steps(mdqt_ensemble* e, int n) {
         if (ens_force_blocks(e, f)) return -1;
         char* slot = nullptr;
         int idx = 0;
-        if (ens_ring_slot(e, &slot, &idx)) return -1;
+        if (e->ring.take(&slot, &idx)) return -1;
         SubstepArgs* h = reinterpret_cast<SubstepArgs*>(slot);
         int nl = 0, maxn = 0;
         for (int st = 0; st < b; ++st) {
@@ -230,13 +217,13 @@ int ens_md_steps(mdqt_ensemble* e, int n) {
                 rem -= m;
             }
         }
-        if (ens_upload(e, e->dSub, slot, (size_t)nl * J * sizeof(SubstepArgs), idx)) return -1;
+        if (e->ring.send(idx, e->dSub, (size_t)nl * J * sizeof(SubstepArgs), e->stream)) return -1;
         int inst = 0;
         for (int st = 0, l = 0; st < b; ++st) {
             if (ens_force_launch(e, f)) return -1;
             for (int c = 0; c < per_step; ++c, ++l) {
                 hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (e->timing && take_events(e->evpool[1], e->evused[1], &e0, &e1)) return -1;
+                if (e->timing && e->timers[1].take(&e0, &e1)) return -1;
                 HIPCHK(launch_substeps_r_ens(e->dSub + (size_t)l * J, h[(size_t)l * J], J, maxn, e->jobs[0]->dFTab,
                                              e->qt_waves, e->stream, e0, e1, &inst));
             }
@@ -273,10 +260,8 @@ extern "C" void mdqt_ensemble_destroy(mdqt_ensemble* e) {
     }
     if (e->dForce) (void)hipFree(e->dForce);
     if (e->dSub) (void)hipFree(e->dSub);
-    if (e->ring) (void)hipHostFree(e->ring);
-    for (hipEvent_t ev : e->ring_ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& pool : e->evpool)
-        for (hipEvent_t ev : pool) (void)hipEventDestroy(ev);
+    e->ring.destroy();
+    for (LaunchTimer& t : e->timers) t.destroy();
     delete e;
 }
 
@@ -314,12 +299,11 @@ int mdqt::ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, 
     }
     HIPCHK(hipSetDevice(e->dev));
     e->sub_blocks = std::max(njobs, 1024);
-    e->slot_bytes = std::max((size_t)e->sub_blocks * sizeof(SubstepArgs), (size_t)njobs * sizeof(N3Args));
+    const size_t slot_bytes = std::max((size_t)e->sub_blocks * sizeof(SubstepArgs), (size_t)njobs * sizeof(N3Args));
     if (hipMalloc(&e->dForce, (size_t)njobs * sizeof(N3Args)) != hipSuccess ||
-        hipMalloc(&e->dSub, (size_t)e->sub_blocks * sizeof(SubstepArgs)) != hipSuccess ||
-        hipHostMalloc((void**)&e->ring, e->slot_bytes * mdqt_ensemble::kRing, hipHostMallocDefault) != hipSuccess)
+        hipMalloc(&e->dSub, (size_t)e->sub_blocks * sizeof(SubstepArgs)) != hipSuccess)
         return set_error("%s: allocating the argument blocks of %d jobs failed", what, njobs);
-    for (hipEvent_t& ev : e->ring_ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence));
+    if (e->ring.create(slot_bytes, kRingSlots, hipEventDisableTiming | hipEventDisableSystemFence)) return -1;
     *out = e.release();
     return 0;
 }
@@ -425,7 +409,7 @@ extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
 extern "C" int mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on) {
     if (!e) return set_error("NULL ensemble");
     e->timing = on > 0;
-    e->evused[0] = e->evused[1] = 0;
+    for (LaunchTimer& t : e->timers) t.reset();
     return 0;
 }
 
@@ -437,19 +421,11 @@ extern "C" int mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n) 
     HIPCHK(hipSetDevice(e->dev));
     HIPCHK(hipStreamSynchronize(e->stream));
     for (int k = 0; k < 2; ++k) {
-        std::vector<double> ms;
-        double tot = 0.;
-        for (int i = 0; i + 1 < e->evused[k]; i += 2) {
-            float x = 0.f;
-            HIPCHK(hipEventElapsedTime(&x, e->evpool[k][i], e->evpool[k][i + 1]));
-            ms.push_back(x);
-            tot += x;
-        }
-        std::sort(ms.begin(), ms.end());
-        out[2 * k] = tot;
-        out[2 * k + 1] = (double)ms.size();
-        out[4 + k] = ms.empty() ? 0. : ms[ms.size() / 2];
-        e->evused[k] = 0;
+        double v[5];
+        if (e->timers[k].stats(v)) return -1;
+        out[2 * k] = v[0];
+        out[2 * k + 1] = v[1];
+        out[4 + k] = v[2];
     }
     return 0;
 }

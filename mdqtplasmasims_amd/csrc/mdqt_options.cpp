@@ -286,26 +286,9 @@ extern "C" int mdqt_positions_device(mdqt_ctx* s, void** dptr, int* S) {
 
 // record the next timing event of kind k (start/stop alternate)
 int mdqt::mark(mdqt_ctx* s, int k) {
-    auto& pool = s->evpool[k];
-    if (s->evused[k] == (int)pool.size()) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
-        pool.push_back(e);
-    }
-    HIPCHK(hipEventRecord(pool[s->evused[k]++], s->stream));
-    return 0;
-}
-
-// a start/stop pair from a pool of timing events (a context's of kind k, an ensemble's), for a launch that
-// records them itself
-int mdqt::take_events(std::vector<hipEvent_t>& pool, int& used, hipEvent_t* e0, hipEvent_t* e1) {
-    while ((int)pool.size() < used + 2) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
-        pool.push_back(e);
-    }
-    *e0 = pool[used++];
-    *e1 = pool[used++];
+    hipEvent_t e = nullptr;
+    if (s->timers[k].next(&e)) return -1;
+    HIPCHK(hipEventRecord(e, s->stream));
     return 0;
 }
 
@@ -331,7 +314,7 @@ extern "C" int mdqt_enable_timing_at(mdqt_ctx* s, int on, int kinds, int offset)
     s->toffset = on > 0 ? (unsigned)offset : 0u;
     s->tkinds = (unsigned)kinds;
     s->tcount[0] = s->tcount[1] = 0;
-    s->evused[0] = s->evused[1] = s->evused[2] = s->evused[3] = 0;
+    for (LaunchTimer& t : s->timers) t.reset();
     for (auto& c : s->bdcalls) {                    // (the breakdown restarts with the timing)
         for (hipEvent_t e : c.m) if (e) s->bdfree.push_back(e);
         if (c.ag0) s->bdfree.push_back(c.ag0);
@@ -351,16 +334,11 @@ extern "C" int mdqt_kernel_times(mdqt_ctx* s, double* out, int n) {
     HIPCHK(hipSetDevice(s->dev));
     HIPCHK(hipStreamSynchronize(s->stream));
     for (int k = 0; k < 4; ++k) {
-        if (2 * k + 1 >= n) { s->evused[k] = 0; continue; }
-        double tot = 0.;
-        for (int i = 0; i + 1 < s->evused[k]; i += 2) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, s->evpool[k][i], s->evpool[k][i + 1]));
-            tot += ms;
-        }
-        out[2 * k] = tot;
-        out[2 * k + 1] = (double)(s->evused[k] / 2);
-        s->evused[k] = 0;
+        if (2 * k + 1 >= n) { s->timers[k].reset(); continue; }
+        double v[5];
+        if (s->timers[k].stats(v)) return -1;
+        out[2 * k] = v[0];
+        out[2 * k + 1] = v[1];
     }
     return 0;
 }

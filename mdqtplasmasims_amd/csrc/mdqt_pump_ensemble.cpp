@@ -1,9 +1,9 @@
 // mdqt_pump_ensemble — J independent jobs of an optical-pumping program (randomFrozenStartTag408Linear.cpp,
 // 408Quad, 422Linear; qt_model 1-3) stepped in batched launches (include/mdqt.h, "ensembles of the
 // optical-pumping programs").  It owns an mdqt_ensemble for the members (ordinary contexts on one stream), the
-// pinned argument ring, the batched force launch (ens_forces: k_pairs_n3_ens over the members on the Newton-3
-// tiles, a row member's own small launch) and the writer pool, and adds the pump programs' kernels over members
-// (mdqt_pump_ensemble_kernels.hip).  Each member's arguments come from the helpers its own path uses
+// pinned argument ring, the lockstep check (ens_check), the QT chunk loop (ens_qt_chunks), the batched force launch
+// (ens_forces: k_pairs_n3_ens over the members on the Newton-3 tiles, a row member's own small launch), the range
+// flags and the writer pool, and adds the pump programs' kernels over members (mdqt_pump_ensemble_kernels.hip).  Each member's arguments come from the helpers its own path uses
 // (n3_force_args / n3_forces_pending inside ens_forces, substep_args(s, a, m, 0, 1, 1), mdqt_tag_spin_up's lo,
 // qstep index and qc) and the kernels run the single-job kernels' bodies: every member's state and files are
 // those of the job on its own, bit for bit.
@@ -30,33 +30,8 @@ static_assert(sizeof(PumpTagArgs) <= sizeof(SubstepArgs) && sizeof(PumpKdeArgs) 
 
 namespace {
 
-bool tagged(const mdqt_ctx* s) { return !s->spinUp.empty(); }
-
-// Every batched call: the members still are what the batched kernels cover, and in lockstep — t (bitwise), the
-// qstep index, c0 and the tagged / untagged flag.  Nothing is launched before this has passed.
-int pump_check(const mdqt_pump_ensemble* pe, const char* what) {
-    if (!pe || !pe->base) return set_error("%s: NULL ensemble", what);
-    const mdqt_ensemble* e = pe->base;
-    const mdqt_ctx* a = e->jobs[0];
-    for (size_t k = 0; k < e->jobs.size(); ++k) {
-        const mdqt_ctx* s = e->jobs[k];
-        if (s->stream != e->stream) return set_error("%s: job index %zu was moved to another stream", what, k);
-        if (s->overlap_opt || s->fused_opt)
-            return set_error("%s: job index %zu has the option overlap / fused_step set (one system per launch)", what, k);
-        if (s->qt_math != 2) return set_error("%s: job index %zu has qt_math %d (the pump models are qt_math 2)", what, k, s->qt_math);
-        if (s->substep_mode == 1) return set_error("%s: job index %zu has substep_kernel 1 (the batched QT kernel is the lane kernel)", what, k);
-        if (s->N < 1) return set_error("%s: job index %zu has no ions (mdqt_pump_ensemble_init or mdqt_set_state first)", what, k);
-        if (s->use_n3b || s->N > 65536)
-            return set_error("%s: job index %zu has N = %d: beyond the Newton-3 tile scheme (N <= 65,536)", what, k, s->N);
-        if (s->force_arrive || s->sub_stream || !s->local.empty()) return set_error("%s: job index %zu is part of another scheme", what, k);
-        if (memcmp(&s->t, &a->t, sizeof(double)) || s->qidx != a->qidx || s->c0 != a->c0 || tagged(s) != tagged(a))
-            return set_error("%s: job index %zu is out of step with job index 0 (t %.17g / %.17g, qstep %llu / %llu, c0 %d / %d, "
-                             "tagged %d / %d): a member stepped on its own ends the ensemble's stepping",
-                             what, k, s->t, a->t, (unsigned long long)s->qidx, (unsigned long long)a->qidx, s->c0, a->c0,
-                             (int)tagged(s), (int)tagged(a));
-    }
-    return 0;
-}
+// the base ensemble's check (mdqt_ensemble.cpp: ens_check) with the tagged / untagged flag compared as well
+int pump_check(const mdqt_pump_ensemble* pe, const char* what) { return ens_check(pe ? pe->base : nullptr, what, true); }
 
 // the members' leapfrog blocks from their pending-force state, uploaded to dStep[which] when they differ
 int step_blocks(mdqt_pump_ensemble* pe, int which, int* max_n) {
@@ -73,18 +48,8 @@ int step_blocks(mdqt_pump_ensemble* pe, int which, int* max_n) {
         a.n = s->nloc; a.S = s->S; a.L = s->L;
         mx = std::max(mx, a.n);
     }
-    std::vector<PumpStepArgs>& held = pe->step_held[which];
-    const size_t bytes = (size_t)J * sizeof(PumpStepArgs);
-    if (held.size() != h.size() || memcmp(held.data(), h.data(), bytes)) {
-        char* slot = nullptr;
-        int idx = 0;
-        if (ens_ring_slot(e, &slot, &idx)) return -1;
-        memcpy(slot, h.data(), bytes);
-        if (ens_upload(e, pe->dStep[which], slot, bytes, idx)) return -1;
-        held = h;
-    }
     *max_n = mx;
-    return 0;
+    return e->ring.send_if_changed(h, pe->step_held[which], pe->dStep[which], e->stream);
 }
 
 // step() of every member at the members' t (:377-394).  lead: the leading half drift is still to be done (it
@@ -109,7 +74,7 @@ int pump_step(mdqt_pump_ensemble* pe, bool lead, bool fold) {
     if (ens_forces(e)) return -1;                                // step_V: forces() :361
     if (step_blocks(pe, 1, &max_n)) return -1;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e->timing && take_events(pe->evkick, pe->evkick_used, &e0, &e1)) return -1;
+    if (e->timing && pe->kick_timer.take(&e0, &e1)) return -1;
     HIPCHK(launch_pump_kick_ens(pe->dStep[1], J, max_n, DT, DT2, moving, dt, fold ? 1 : 0, e->stream, e0, e1));
     pe->launches++;
     for (mdqt_ctx* s : e->jobs) s->f_pending = false;
@@ -118,39 +83,12 @@ int pump_step(mdqt_pump_ensemble* pe, bool lead, bool fold) {
 
 // n x qstep() of every member (QT only: run_substeps(s, n, 0, 1, 1)), chunks of at most MAXSUB
 int pump_qsteps(mdqt_pump_ensemble* pe, int n) {
-    mdqt_ensemble* e = pe->base;
-    const int J = (int)e->jobs.size();
-    const int do_qt = e->jobs[0]->p.qt_enabled ? 1 : 0;
-    while (n > 0) {
-        const int m = n < MAXSUB ? n : MAXSUB;
-        char* slot = nullptr;
-        int idx = 0;
-        if (ens_ring_slot(e, &slot, &idx)) return -1;
-        SubstepArgs* h = reinterpret_cast<SubstepArgs*>(slot);
-        double t = 0.;
-        int maxn = 0;
-        for (int k = 0; k < J; ++k) {
-            mdqt_ctx* s = e->jobs[k];
-            t = substep_args(s, h[k], m, 0, do_qt, 1);
-            s->f_pending = false;
-            maxn = std::max(maxn, h[k].n);
-        }
-        if (ens_upload(e, e->dSub, slot, (size_t)J * sizeof(SubstepArgs), idx)) return -1;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (e->timing && take_events(e->evpool[1], e->evused[1], &e0, &e1)) return -1;
-        int inst = 0;
-        HIPCHK(launch_substeps_pump_ens(e->dSub, h[0], J, maxn, e->jobs[0]->dFTab, e->stream, e0, e1, &inst));
-        pe->launches++;
-        for (int k = 0; k < J; ++k) {
-            mdqt_ctx* s = e->jobs[k];
-            s->last_qt_kernel = inst;
-            s->last_qt_nseg = h[k].nseg;
-            s->t = t;
-            s->qidx += (uint64_t)m;
-        }
-        n -= m;
-    }
-    return 0;
+    return ens_qt_chunks(pe->base, n, 0, [pe](const SubstepArgs& first, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst) {
+        mdqt_ensemble* e = pe->base;
+        const hipError_t r = launch_substeps_pump_ens(e->dSub, first, (int)e->jobs.size(), maxn, e->jobs[0]->dFTab, e->stream, e0, e1, inst);
+        if (r == hipSuccess) pe->launches++;
+        return r;
+    });
 }
 
 // a member's tag array and tagged-distribution buffers, of a size this ensemble knows (the context allocates
@@ -186,7 +124,7 @@ int pump_tag(mdqt_pump_ensemble* pe) {
     const int J = (int)e->jobs.size();
     char* slot = nullptr;
     int idx = 0;
-    if (ens_ring_slot(e, &slot, &idx)) return -1;
+    if (e->ring.take(&slot, &idx)) return -1;
     PumpTagArgs* h = reinterpret_cast<PumpTagArgs*>(slot);
     int maxn = 0;
     for (int k = 0; k < J; ++k) {
@@ -198,7 +136,7 @@ int pump_tag(mdqt_pump_ensemble* pe) {
         a.gid0 = (uint64_t)s->lo; a.q = s->qidx; a.tags = s->dSpinUp; a.qc = s->qc;
         maxn = std::max(maxn, a.n);
     }
-    if (ens_upload(e, pe->dTag, slot, (size_t)J * sizeof(PumpTagArgs), idx)) return -1;
+    if (e->ring.send(idx, pe->dTag, (size_t)J * sizeof(PumpTagArgs), e->stream)) return -1;
     HIPCHK(launch_tag_spin_up_ens(pe->dTag, J, maxn, e->stream));
     pe->launches++;
     for (mdqt_ctx* s : e->jobs) {
@@ -222,7 +160,7 @@ int pump_output(mdqt_pump_ensemble* pe, int vaf) {
     const int J = (int)e->jobs.size();
     char* slot = nullptr;
     int idx = 0;
-    if (ens_ring_slot(e, &slot, &idx)) return -1;
+    if (e->ring.take(&slot, &idx)) return -1;
     PumpKdeArgs* h = reinterpret_cast<PumpKdeArgs*>(slot);
     int maxN = 0;
     std::vector<std::vector<double>> Vs((size_t)J), Ps((size_t)J);
@@ -238,7 +176,7 @@ int pump_output(mdqt_pump_ensemble* pe, int vaf) {
         Ps[k].assign((size_t)3 * TKDE_BINS, 0.);
         HIPCHK(hipMemcpyAsync(Vs[k].data(), s->dV, Vs[k].size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     }
-    if (ens_upload(e, pe->dKde, slot, (size_t)J * sizeof(PumpKdeArgs), idx)) return -1;
+    if (e->ring.send(idx, pe->dKde, (size_t)J * sizeof(PumpKdeArgs), e->stream)) return -1;
     HIPCHK(launch_tagged_kde_ens(pe->dKde, J, maxN, e->stream));
     pe->launches += 2;
     for (int k = 0; k < J; ++k)
@@ -276,7 +214,7 @@ extern "C" void mdqt_pump_ensemble_destroy(mdqt_pump_ensemble* pe) {
     for (auto& d : pe->dStep) if (d) (void)hipFree(d);
     if (pe->dTag) (void)hipFree(pe->dTag);
     if (pe->dKde) (void)hipFree(pe->dKde);
-    for (hipEvent_t ev : pe->evkick) (void)hipEventDestroy(ev);
+    pe->kick_timer.destroy();
     mdqt_ensemble_destroy(pe->base);
     delete pe;
 }
@@ -300,21 +238,14 @@ extern "C" int mdqt_pump_ensemble_create(const mdqt_params* p, int njobs, mdqt_p
     return 0;
 }
 
-extern "C" int mdqt_pump_ensemble_size(const mdqt_pump_ensemble* pe) { return pe && pe->base ? (int)pe->base->jobs.size() : -1; }
+// the members are the base ensemble's (its "qt_waves" picks an instance of the SpeedUp QT kernel: the pump
+// kernels do not read it)
+extern "C" int mdqt_pump_ensemble_size(const mdqt_pump_ensemble* pe) { return mdqt_ensemble_size(pe ? pe->base : nullptr); }
 
-extern "C" mdqt_ctx* mdqt_pump_ensemble_job(mdqt_pump_ensemble* pe, int k) {
-    if (!pe || !pe->base || k < 0 || k >= (int)pe->base->jobs.size()) {
-        set_error("mdqt_pump_ensemble_job: job index %d outside the ensemble", k);
-        return nullptr;
-    }
-    return pe->base->jobs[(size_t)k];
-}
+extern "C" mdqt_ctx* mdqt_pump_ensemble_job(mdqt_pump_ensemble* pe, int k) { return mdqt_ensemble_job(pe ? pe->base : nullptr, k); }
 
 extern "C" int mdqt_pump_ensemble_set_option(mdqt_pump_ensemble* pe, const char* name, int value) {
-    if (!pe || !name) return set_error("mdqt_pump_ensemble_set_option: NULL argument");
-    for (mdqt_ctx* s : pe->base->jobs)
-        if (mdqt_set_option(s, name, value)) return -1;
-    return 0;
+    return mdqt_ensemble_set_option(pe ? pe->base : nullptr, name, value);
 }
 
 extern "C" int mdqt_pump_ensemble_init(mdqt_pump_ensemble* pe) {       // init() of every job
@@ -356,14 +287,7 @@ extern "C" int mdqt_pump_ensemble_output(mdqt_pump_ensemble* pe) {            //
 
 extern "C" int mdqt_pump_ensemble_synchronize(mdqt_pump_ensemble* pe) {
     if (!pe) return set_error("NULL ensemble");
-    HIPCHK(hipSetDevice(pe->base->dev));
-    HIPCHK(hipStreamSynchronize(pe->base->stream));
-    for (size_t k = 0; k < pe->base->jobs.size(); ++k)
-        if (pe->base->jobs[k]->hFlags[0] && !pe->base->jobs[k]->guard) {
-            pe->base->jobs[k]->guard = true;
-            return range_flag_error((int)k);
-        }
-    return 0;
+    return mdqt_ensemble_synchronize(pe->base);     // every member that raised the range flag is marked
 }
 
 extern "C" unsigned long long mdqt_pump_ensemble_launches(const mdqt_pump_ensemble* pe) {
@@ -467,7 +391,7 @@ extern "C" int mdqt_pump_ensemble_run(mdqt_pump_ensemble* pe) {
 
 extern "C" int mdqt_pump_ensemble_enable_timing(mdqt_pump_ensemble* pe, int on) {
     if (!pe) return set_error("NULL ensemble");
-    pe->evkick_used = 0;
+    pe->kick_timer.reset();
     return mdqt_ensemble_enable_timing(pe->base, on);
 }
 
@@ -478,18 +402,10 @@ extern "C" int mdqt_pump_ensemble_kernel_times(mdqt_pump_ensemble* pe, double* o
     if (n < 9) return set_error("mdqt_pump_ensemble_kernel_times: need 9 doubles");
     double b[6];
     if (mdqt_ensemble_kernel_times(pe->base, b, 6)) return -1;
-    std::vector<double> ms;
-    double tot = 0.;
-    for (int i = 0; i + 1 < pe->evkick_used; i += 2) {
-        float x = 0.f;
-        HIPCHK(hipEventElapsedTime(&x, pe->evkick[i], pe->evkick[i + 1]));
-        ms.push_back(x);
-        tot += x;
-    }
-    std::sort(ms.begin(), ms.end());
-    pe->evkick_used = 0;
+    double kick[5];
+    if (pe->kick_timer.stats(kick)) return -1;
     out[0] = b[0]; out[1] = b[1]; out[2] = b[2]; out[3] = b[3];
-    out[4] = tot; out[5] = (double)ms.size();
-    out[6] = b[4]; out[7] = b[5]; out[8] = ms.empty() ? 0. : ms[ms.size() / 2];
+    out[4] = kick[0]; out[5] = kick[1];
+    out[6] = b[4]; out[7] = b[5]; out[8] = kick[2];
     return 0;
 }

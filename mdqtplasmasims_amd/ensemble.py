@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+from ._ensemble_base import _EnsembleBase
 from ._lib import MdqtParams, check, lib
 from .engine import Simulation, default_params
 
@@ -43,8 +44,10 @@ class _Member(Simulation):
         self.h = None
 
 
-class Ensemble:
+class Ensemble(_EnsembleBase):
     """``njobs`` independent jobs (job + k, seed + k) resident on one MI355X, stepped together."""
+
+    _DESTROY = "mdqt_ensemble_destroy"
 
     def __init__(self, njobs: int, **params):
         self.params = default_params(**params)
@@ -53,29 +56,6 @@ class Ensemble:
         self.h = h
         self.jobs = [_Member(self, lib().mdqt_ensemble_job(h, k), job_params(self.params, k))
                      for k in range(lib().mdqt_ensemble_size(h))]
-
-    # ---- lifecycle ----
-    def close(self):
-        if getattr(self, "h", None):
-            for j in self.jobs:
-                j.close()
-            lib().mdqt_ensemble_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return len(self.jobs)
 
     @property
     def N(self):
@@ -116,8 +96,7 @@ class Ensemble:
         launches since the last call (synchronises and resets)"""
         out = (C.c_double * 6)()
         check(lib().mdqt_ensemble_kernel_times(self.h, out, 6), "ensemble_kernel_times")
-        keys = ("force_ms", "n_force", "substep_ms", "n_substep", "force_median_ms", "substep_median_ms")
-        return {k: (int(out[i]) if k.startswith("n_") else out[i]) for i, k in enumerate(keys)}
+        return self._times(out, ("force_ms", "n_force", "substep_ms", "n_substep", "force_median_ms", "substep_median_ms"))
 
 
 __all__ = ["Ensemble", "job_params"]

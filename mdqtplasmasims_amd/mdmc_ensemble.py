@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+from ._ensemble_base import _EnsembleBase
 from ._lib import MdmcParams, check, lib
 from .mdmc import MonteCarloMD, default_params
 
@@ -46,8 +47,10 @@ class _Member(MonteCarloMD):
         self._h = None
 
 
-class MonteCarloEnsemble:
+class MonteCarloEnsemble(_EnsembleBase):
     """``njobs`` independent jobs (job + k, seed + k) resident on one MI355X."""
+
+    _DESTROY = "mdmc_ensemble_destroy"
 
     STAGES = ("anneal", "pre_record_md", "qt_pump", "recorded_md", "autocorrelations", "rest")
 
@@ -79,29 +82,6 @@ class MonteCarloEnsemble:
         check(lib().mdmc_ensemble_md_launches(self.h, C.byref(n)), "mdmc_ensemble_md_launches")
         return int(n.value)
 
-    # ---- lifecycle ----
-    def close(self):
-        if getattr(self, "h", None):
-            for j in self.jobs:
-                j.close()
-            lib().mdmc_ensemble_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return len(self.jobs)
-
     # ---- the reference's function seam, for every job at once ----
     def init(self):
         check(lib().mdmc_ensemble_init(self.h), "mdmc_ensemble_init")
@@ -130,11 +110,9 @@ class MonteCarloEnsemble:
         and velocity-Verlet launches (md_batch 1), and stage_ms: the wall time of the last run()'s stages"""
         out = (C.c_double * 21)()
         check(lib().mdmc_ensemble_kernel_times(self.h, out, 21), "mdmc_ensemble_kernel_times")
-        d = {"anneal_ms": out[0], "n_anneal": int(out[1]), "anneal_median_ms": out[2], "anneal_min_ms": out[3],
-             "anneal_max_ms": out[4]}
-        for i, k in ((11, "md_force"), (16, "md_vv")):
-            d.update({k + "_ms": out[i], "n_" + k: int(out[i + 1]), k + "_median_ms": out[i + 2],
-                      k + "_min_ms": out[i + 3], k + "_max_ms": out[i + 4]})
+        d = {}
+        for i, k in ((0, "anneal"), (11, "md_force"), (16, "md_vv")):
+            d.update(self._times(out, (k + "_ms", "n_" + k, k + "_median_ms", k + "_min_ms", k + "_max_ms"), i))
         d["stage_ms"] = {k: out[5 + i] for i, k in enumerate(self.STAGES)}
         return d
 

@@ -22,13 +22,16 @@ from __future__ import annotations
 
 import ctypes as C
 
+from ._ensemble_base import _EnsembleBase
 from ._lib import check, lib
 from .engine import default_params_pump
 from .ensemble import _Member, job_params
 
 
-class PumpEnsemble:
+class PumpEnsemble(_EnsembleBase):
     """``njobs`` independent jobs (job + k, seed + k) of pump program 1 / 2 / 3, stepped together."""
+
+    _DESTROY = "mdqt_pump_ensemble_destroy"
 
     def __init__(self, njobs: int, pump_program: int = 1, **params):
         self.params = default_params_pump(pump_program, **params)
@@ -38,29 +41,6 @@ class PumpEnsemble:
         self.h = h
         self.jobs = [_Member(self, lib().mdqt_pump_ensemble_job(h, k), job_params(self.params, k))
                      for k in range(lib().mdqt_pump_ensemble_size(h))]
-
-    # ---- lifecycle ----
-    def close(self):
-        if getattr(self, "h", None):
-            for j in self.jobs:
-                j.close()
-            lib().mdqt_pump_ensemble_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return len(self.jobs)
 
     @property
     def N(self):
@@ -113,9 +93,8 @@ class PumpEnsemble:
         median ms"""
         out = (C.c_double * 9)()
         check(lib().mdqt_pump_ensemble_kernel_times(self.h, out, 9), "pump_ensemble_kernel_times")
-        keys = ("force_ms", "n_force", "qt_ms", "n_qt", "kick_ms", "n_kick", "force_median_ms", "qt_median_ms",
-                "kick_median_ms")
-        return {k: (int(out[i]) if k.startswith("n_") else out[i]) for i, k in enumerate(keys)}
+        return self._times(out, ("force_ms", "n_force", "qt_ms", "n_qt", "kick_ms", "n_kick", "force_median_ms",
+                                 "qt_median_ms", "kick_median_ms"))
 
 
 __all__ = ["PumpEnsemble"]

@@ -172,6 +172,69 @@ def test_md_only(M):
         assert_same(g, single(M, params, k, opts, lambda s: s.md_steps(3)), f"job index {k}")
 
 
+# ---- 6a. more argument uploads in a row than the pinned ring has slots (8) ----
+def test_more_launches_than_ring_slots(M):
+    """every substeps() call takes a slot for its QT blocks: 12 of them go once and a half round the ring"""
+    opts = {"force_scheme": 2}
+
+    def calls(x):
+        for _ in range(12):
+            x.forces()
+            x.substeps(1)
+        x.md_steps(3)
+
+    got, _ = ensemble(M, SMALL, 3, opts, calls)
+    for k, g in enumerate(got):
+        assert g["qstep"] == 12 + 75
+        assert_same(g, single(M, SMALL, k, opts, calls), f"job index {k}")
+
+
+def test_md_steps_built_ahead_round_the_ring(M):
+    """md_steps' built-ahead path: 1024 device blocks / 64 jobs / 1 QT launch per MD step = 16 MD steps per upload,
+    so 130 = 8 x 16 + 2 MD steps are 9 uploads, one more than the ring has slots (the force blocks, unchanged from
+    step to step, took one more slot before the first)"""
+    opts = {"force_scheme": 2}
+    njobs, seen = 64, {}
+
+    def calls(e):
+        ratio = e.jobs[0].const("plasmaToQuantumTimestepRatio")
+        per_step = -(-int(ratio) // 32)                     # QT launches per MD step (MAXSUB 32)
+        ahead = min(64, 1024 // (njobs * per_step))
+        assert ahead >= 2 and 64 % ahead == 0               # the built-ahead path, whole batches up to step 64 k
+        seen["steps"] = 8 * ahead + 2                       # 9 uploads
+        e.md_steps(seen["steps"])
+
+    got, _ = ensemble(M, SMALL, njobs, opts, calls)
+    assert seen["steps"] == 130
+    for k in (0, 31, 63):
+        assert got[k]["c0"] == 129
+        assert_same(got[k], single(M, SMALL, k, opts, lambda s: s.md_steps(seen["steps"])), f"job index {k}")
+
+
+# ---- 6b. the timing contract: exact launch counts, then a reset ----
+def test_kernel_times_count_the_batched_launches(M):
+    with M.Ensemble(njobs=3, **SMALL) as e:
+        e.set_option("force_scheme", 2)                     # every member on the tiles: one force launch per MD step
+        e.init()
+        e.enable_timing()
+        e.md_steps(4)
+        t = e.kernel_times()
+        assert t["n_force"] == 4 and t["n_substep"] == 4    # ratio 25 <= MAXSUB: one QT launch per MD step
+        for k in ("force", "substep"):
+            assert 0 < t[k + "_median_ms"] <= t[k + "_ms"]
+        again = e.kernel_times()
+        assert all(v == 0 for v in again.values()), again
+    with M.Simulation(**SMALL) as s:
+        s.set_option("force_scheme", 2)
+        s.init()
+        s.enable_timing()
+        s.md_steps(4)
+        t = s.kernel_times()
+        assert t["n_force"] > 0 and t["n_substep"] > 0 and t["force_ms"] > 0 and t["substep_ms"] > 0
+        again = s.kernel_times()                            # a single context's: the same reset
+        assert all(v == 0 for v in again.values()), again
+
+
 # ---- 7. lockstep ----
 def test_lockstep_names_the_job(M):
     with M.Ensemble(njobs=3, **SMALL) as e:

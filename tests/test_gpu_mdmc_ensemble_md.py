@@ -208,6 +208,23 @@ def test_member_stepped_alone_restated_and_set_apart(M):
         G.close()
 
 
+# ---- 2a. more uploads in flight than the pinned rings have slots: 64 collisional steps, 4 stretches ----
+def test_more_steps_and_stretches_than_ring_slots(M):
+    N = 27
+    G = Groups(M, 3, **params(N, collisionFreq=COLL))
+    try:
+        for g in G.groups:
+            start(g, N)
+        G.md_steps(70)                                   # one stretch of 70 collisional steps: 70 VVArgs uploads
+        same_all(G.groups, "70 collisional steps in one stretch")
+        for _ in range(6):                               # six stretches: six header uploads
+            G.md_steps(1)
+        same_all(G.groups, "six stretches of one step")
+        same_rng(G.groups, "rng")
+    finally:
+        G.close()
+
+
 # ---- 3. the launch count: 2 per collisionless step, whatever J ----
 @pytest.mark.parametrize("J", [1, 5])
 def test_two_launches_per_collisionless_step(M, J):

@@ -152,6 +152,44 @@ def test_qsteps_and_tagging(M, model):
     assert jumps > 0, "no quantum jump on the single contexts: the jump path did not run"
 
 
+# ---- 4a. more QT launches in a row than the pinned ring has slots (8), and the tagging's slot after them ----
+def test_more_qt_launches_than_ring_slots(M):
+    njobs = 3
+    params = dict(MID, **QT[1])
+    with M.PumpEnsemble(njobs, pump_program=1, **params) as e:
+        e.init()
+        for _ in range(12):
+            e.qsteps(1)
+        got = [snapshot(j) for j in e.jobs]
+        tags = e.tag_spin_up()
+    for k in range(njobs):
+        with M.Simulation(pump_program=1, **member_params(params, k)) as s:
+            s.init()
+            for _ in range(12):
+                s.qstep()
+            assert_same(got[k], snapshot(s), f"job index {k} after twelve launches of one qstep")
+            wtags, wn = s.tag_spin_up()
+        assert tags[k][1] == wn and np.array_equal(tags[k][0], wtags), f"job index {k}: tags"
+
+
+# ---- 4b. the timing contract: exact launch counts, then a reset ----
+def test_kernel_times_count_the_batched_launches(M):
+    with M.PumpEnsemble(3, pump_program=1, **MID) as e:
+        e.init()
+        assert min(e.N) >= 128                              # every member on the Newton-3 tiles
+        for j in e.jobs:
+            j.t = T1
+        e.enable_timing()
+        e.md_steps(4)                                       # (force, kick-drift) x 4
+        e.qsteps(40)                                        # 32 + 8: two QT launches
+        t = e.kernel_times()
+        assert (t["n_force"], t["n_kick"], t["n_qt"]) == (4, 4, 2)
+        for k in ("force", "kick", "qt"):
+            assert 0 < t[k + "_median_ms"] <= t[k + "_ms"]
+        again = e.kernel_times()
+        assert all(v == 0 for v in again.values()), again
+
+
 # ---- 5. run() and 6. the resume, against run_pump() of every job into another directory ----
 def tree(d):
     out = []
