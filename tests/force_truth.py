@@ -65,6 +65,58 @@ and U_i to the same with Gu_i, U_i, Eu_i, Hu_i.  Every term is derived, none is 
 
 phi = max_i |dF_i|_inf / (u P_i) over ions with H_i = 0 measures an instance on the scale of its own
 row sum; the tests compare it with the same figure of the reference's operations (the oracle).
+
+The Newton-3 blocks (force_scheme 3: k_pairs_n3b, k_pairs_n3b_pw, k_n3b_reduce, k_tail_fix) are held to
+
+    gate_i = [the gate above with D = depth_blocks(N)]  +  Form_i  +  Tail_i,
+
+and U_i to the same with FormU_i, TailU_i.  The three block terms come from the truth's separations and
+the constants the engine publishes (the radii of the call, mdqt_internal.hpp's kFormErrA/B); none from a
+device result.
+
+* Summation (depth_blocks).  T = ceil(N/64) tiles, NB = ceil(T/8) blocks, nd = NB/2 + 1 block distances
+  in R runs of runlen (n3b_set_range: R = min(nd, ceil(65536/NB)), runlen = ceil(nd/R), R =
+  ceil(nd/runlen); N <= 5000: runlen = 1, R = nd).  A pair term reaches F_i along one of two chains:
+    i side:  the tile pair's fresh sum (<= 64 steps: four 16-step groups, 40 on the diagonal tile), into
+             the block distance's sum (<= 8 J tiles), into the run's sum in LDS (runlen), the i-slot;
+    j side:  the wave's LDS accumulator (64 ds_add_f64 per tile pair; the paired-wave kernel adds its
+             two tile pairs of a J step into one: 128), the two LDS copies (1), the fixed pairwise tree
+             over the 8 or 4 waves (3 or 2), the j-slot;
+  then k_n3b_reduce adds the nd j-slots and the R i-slots in one chain.  A term takes part in at most
+    D = max(64 + 8 + runlen, 128 + 1 + 3) + nd + R + 8
+  additions (the 8 as the rows' and tiles': the kernel's own zero starts and the negation-free combine), and
+  any tree in which no term meets more than D additions is within D u sum |t_k| to first order.  The f32
+  ultra-far form's 16-term f32 partial sums are part of its stated error (kUfar32B's 15u), not of D.
+  k_tail_fix's replaced rows: a 64-term partial per J tile, compensated across tiles, 4 waves: below D.
+  One chain over every term, N + 8, bounds any order (pad ions and masked lanes add exact zeros), so
+  depth_blocks returns min(D, N + 8): the count above exceeds it only at N = 129 (142 against 137).
+* Per term.  The exact instances (VARIANT 0, guarded or not) run pair_ft<0> / pair_u<0>, the fast ones
+  (guarded or not) pair_ft_cut / pair_ft<1> (k_tail_fix) / pair_u<1>: counted above, within KF, KU, KT.
+  n3_terms adds one product with the rotation weight (1.0 or 0.0) and, on a ragged tile, mi mj (1.0 or
+  0.0): exact.  Uniform image (SHIFT) and one-axis image (AXP): the lane's xi - n L is one fma (one
+  rounding, <= 1.25 L u), then sx - xj one more: two roundings per axis, what the per-pair image's
+  (xi - xj) - n L has (equal bit for bit where n = 0), inside GEOM = 3.5.  No recount needed.
+* Form_i.  A sub-tile group evaluated in the pair form of plan level e (1 mid, 2 far, 3 very far, 4
+  ultra far, 5 ultra far in f32; n3b_level) has every sub-box gap, hence every pair, at r >= R_e; the
+  kernel may take a lower level than the gap allows (ragged tiles and the diagonal: exact; a per-pair
+  image: levels 4, 5 as 3 or 4; an f32 group whose J box is too wide: 4), never a higher one, and the
+  stated relative errors err_e(r) = kFormErrA[e] r/lDeb + kFormErrB[e] grow with e at every r (asserted in
+  tests/test_force_truth.py).  So
+      Form_i = sum_j g(r_ij) err_level(r_ij)(r_ij),   level(r) = the highest enabled e with R_e <= r
+  (a tier is enabled when its radius is below L/2), FormU_i the same with u (pair_u_cut's error is
+  within the force form's: one factor ri instead of three).  The level is taken at r (1 + 2^-50): the
+  truth's double r against the engine's double radius.  err_e is pinned to mdqt_force_plan.cpp's far_err
+  through mdqt_tier_radius_model on the CPU.
+  With a-priori radii (force_form_mode 0, or no measured tail) the f32 tier decides the cutoff on its f32
+  r^2: fl32 relative coordinates and three f32 operations put r^2 within 11 x 2^-24 of itself
+  (mdqt_internal.hpp, kUfar32A/B's derivation: r within 5.5 x 2^-24, and fl32(rc2) another half), so a pair
+  within F32CUT 2^-24 L/2 of L/2, F32CUT = 6, inside the reference's pair set or not, may be decided either
+  way: a whole term g (u) each, added to Form_i — the analogue of H_i.  (far_radius_l's comment still
+  says 3 x 2^-24, the round-3 form's count; its term (N - 1) g(L/2 (1 - 2^-20)) covers a shell 16 x 2^-24
+  wide.)  The measured modes keep the f32 form off every group that can reach L/2 (u32lim2): no such term.
+* Tail_i = sum g over the pairs of S_i with r >= R_skip (force_skip_radius): a skipped tile pair or sub-tile
+  group has its boxes, hence its pairs, at least R_skip apart.  0 where R_skip = L/2.  Rows that k_tail_fix
+  replaced hold every pair to L/2 in pair_ft<1> and are inside the gate without it.
 """
 import math
 
@@ -145,6 +197,23 @@ def row_sums(R, L, lDeb, idx=None, chunk=128):
     return out
 
 
+def row_sums_threads(R, L, lDeb, nthreads=8):
+    """row_sums of every ion, the rows split over threads (numpy's long double loops release the GIL): the
+    same sums row for row, each row's in the same order"""
+    from concurrent.futures import ThreadPoolExecutor
+    N = np.asarray(R).shape[1]
+    parts = [p for p in np.array_split(np.arange(N), nthreads) if len(p)]
+    with ThreadPoolExecutor(len(parts)) as ex:
+        rows = list(ex.map(lambda p: row_sums(R, L, lDeb, p), parts))
+    out = Rows()
+    out.idx = np.arange(N)
+    out.T = np.concatenate([r.T for r in rows], axis=1)
+    for k in ("P", "G", "E", "H", "U", "Gu", "Eu", "Hu"):
+        setattr(out, k, np.concatenate([getattr(r, k) for r in rows]))
+    out.nshell = sum(r.nshell for r in rows)
+    return out
+
+
 def geom_roundings(R, L):
     """roundings of L u per axis of a separation: GEOM inside [-L/8, 9L/8]; outside, the half-ulps of
     the largest separation (its subtraction) and of the largest image shift n L (the division form's
@@ -197,11 +266,152 @@ def depth_tiles(slots):
 
 
 # ---------------------------------------------------------------------------------------------
+# the Newton-3 blocks (force_scheme 3)
+# ---------------------------------------------------------------------------------------------
+
+BLOCK_TILES = 8            # kN3BBlock: tiles per block (512 ions)
+BLOCK_WORKGROUPS = 65536   # n3b_set_range's workgroups per rank
+
+
+def block_layout(N):
+    """(T, NB, nd, R, runlen) of the block scheme at world 1 (mdqt_engine.cpp n3b_set_range)"""
+    T = -(-N // 64)
+    NB = -(-T // BLOCK_TILES)
+    nd = NB // 2 + 1
+    R = min(nd, -(-BLOCK_WORKGROUPS // NB))
+    runlen = -(-nd // R)
+    return T, NB, nd, -(-nd // runlen), runlen
+
+
+def depth_blocks(N):
+    _, _, nd, R, runlen = block_layout(N)
+    return min(max(64 + BLOCK_TILES + runlen, 128 + 1 + 3) + nd + R + 8, N + 8)
+
+
+# mdqt_internal.hpp: kRsq1RelErr, kTab4RelErr, kFarRelErr, kRsqRawErr, kExp5RelErr, kExp2fRelErr, kUfar32A/B
+_RSQ1, _TAB4, _FAR, _RSQRAW, _EXP5, _EXP2F = 2.2e-14, 4e-15, 3e-9, 2.0 ** -23, 1.1e-7, 2.0 ** -22
+# kFormErrA/B by plan level (n3b_level): 0 exact, 1 mid, 2 far, 3 very far, 4 ultra far, 5 ultra far in f32
+FORM_A = (0.0, _RSQ1 + 2.0 ** -52, 0.0, _RSQRAW, _RSQRAW + 2.0 ** -24, 22 * 2.0 ** -24)
+FORM_B = (0.0, 3 * (_RSQ1 + 2.0 ** -52) + _TAB4, _FAR, 3 * _RSQRAW + _EXP5, 3 * _RSQRAW + _EXP2F, 52 * 2.0 ** -24)
+# plan level -> the level numbering of mdqt_force_plan.cpp's far_err and mdqt_tier_radius_model
+MODEL_LEVEL = {1: 5, 2: 1, 3: 2, 4: 3, 5: 4}
+TIERS = {1: "mid", 2: "far", 3: "vfar", 4: "ufar", 5: "ufar32"}     # force_<name>_radius
+F32CUT = 6.0               # the f32 tier's cutoff shell: |r - L/2| <= F32CUT 2^-24 L/2
+
+
+def form_err(e, r, lDeb):
+    """err_e(r): the stated relative error of a pair term at distance r in the form of plan level e"""
+    return FORM_A[e] * (r / lDeb) + FORM_B[e]
+
+
+class BlockTerms:
+    """Form_i, FormU_i, Tail_i, TailU_i of ions idx (double: bounds, not truths)"""
+    __slots__ = ("idx", "form", "formu", "tail", "tailu", "nform", "ntail", "ncut")
+
+
+def block_terms(R, L, lDeb, radii, skip, f32cut, idx=None, chunk=256, nthreads=8):
+    """the blocks' gate terms over the reference's pair set: radii = {plan level: R_e} (missing or >= L/2:
+    off), skip = R_skip, f32cut: the f32 tier decides its own cutoff (a-priori radii).  nform[e], ntail, ncut
+    count the ordered pairs at level e, beyond R_skip and on the f32 cutoff shell.  The rows in chunks over
+    threads (numpy's loops release the GIL); each row's sum is the same whatever the split"""
+    from concurrent.futures import ThreadPoolExecutor
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    N = R.shape[1]
+    idx = np.arange(N) if idx is None else np.asarray(idx, dtype=np.int64)
+    m = len(idx)
+    half = L / 2
+    on = sorted(e for e, r in radii.items() if r < half)
+    cut = f32cut and 5 in on
+
+    def rows(a):
+        ii = idx[a:a + chunk]
+        n, keep = pair_set(R, L, ii)
+        d = (R[:, ii, None] - R[:, None, :]) - L * n
+        r = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        other = r > 0
+        r = np.where(other, r, 1.0)
+        e_ = np.exp(-r / lDeb)
+        u = e_ / r
+        g = (1 / (r * r) + 1 / (r * lDeb)) * e_
+        up = r * (1 + 2.0 ** -50)
+        err = np.zeros_like(r)
+        lev = np.zeros(r.shape, dtype=np.int8)
+        for e in on:                                    # ascending: the highest level with R_e <= r stays
+            at = keep & (up >= radii[e])
+            err = np.where(at, form_err(e, r, lDeb), err)
+            lev[at] = e
+        form, formu = (g * err).sum(axis=1), (u * err).sum(axis=1)
+        ncut = 0
+        if cut:
+            shell = other & (np.abs(r - half) <= F32CUT * 2.0 ** -24 * half)
+            form += np.where(shell, g, 0.0).sum(axis=1)
+            formu += np.where(shell, u, 0.0).sum(axis=1)
+            ncut = int(shell.sum())
+        far = keep & (up >= skip) if skip < half else np.zeros_like(keep)
+        return (a, form, formu, np.where(far, g, 0.0).sum(axis=1), np.where(far, u, 0.0).sum(axis=1),
+                {e: int((lev == e).sum()) for e in on}, int(far.sum()), ncut)
+
+    out = BlockTerms()
+    out.idx = idx
+    for k in ("form", "formu", "tail", "tailu"):
+        setattr(out, k, np.zeros(m))
+    out.nform, out.ntail, out.ncut = {e: 0 for e in on}, 0, 0
+    with ThreadPoolExecutor(nthreads) as ex:
+        for a, form, formu, tail, tailu, nform, ntail, ncut in ex.map(rows, range(0, m, chunk)):
+            s = slice(a, a + len(form))
+            out.form[s], out.formu[s], out.tail[s], out.tailu[s] = form, formu, tail, tailu
+            for e in on:
+                out.nform[e] += nform[e]
+            out.ntail += ntail
+            out.ncut += ncut
+    return out
+
+
+def rounding_part(t, L, D, geom=GEOM, potential=False):
+    """the geometry and rounding terms of the gate: no shell, form or tail allowance"""
+    return potential_gate(t, L, D, False, geom) if potential else force_gate(t, L, D, False, geom)
+
+
+def block_force_gate(t, b, L, D, fast, geom=GEOM):
+    return force_gate(t, L, D, fast, geom) + b.form.astype(LD) + b.tail.astype(LD)
+
+
+def block_potential_gate(t, b, L, D, fast, geom=GEOM):
+    return potential_gate(t, L, D, fast, geom) + b.formu.astype(LD) + b.tailu.astype(LD)
+
+
+# ---------------------------------------------------------------------------------------------
 # the states
 # ---------------------------------------------------------------------------------------------
 
 def random_state(N, L, seed=2024):
     return np.random.default_rng([seed, N]).uniform(0.0, L, (3, N))
+
+
+def clustered_state(N, L, frac, rc, seed=2024):
+    """a fraction frac of the N ions uniform in a ball of radius rc at the box centre, the rest uniform in
+    the box, in random index order: far from the uniform density the skip radius's model assumes"""
+    rng = np.random.default_rng([seed, N, 7])
+    nc = int(frac * N)
+    v = rng.normal(size=(3, nc))
+    v /= np.linalg.norm(v, axis=0)
+    ball = L / 2 + v * (rc * rng.uniform(0, 1, nc) ** (1 / 3))
+    R = np.concatenate([rng.uniform(0.0, L, (3, N - nc)), ball], axis=1)[:, rng.permutation(N)]
+    return np.ascontiguousarray(R)
+
+
+def clumped_state(N, L, per=64, radius=1.0, seed=2024):
+    """ions in compact clumps of `per` (the last one smaller), uniform in balls of `radius` whose centres are
+    uniform in the box: in spatial order a 64-ion tile is then ~2 wide instead of the uniform density's ~6.4,
+    and whole tile pairs lie beyond the cutoff at a few thousand ions already"""
+    rng = np.random.default_rng([seed, N, 11])
+    nc = -(-N // per)
+    c = rng.uniform(radius, L - radius, (3, nc))
+    v = rng.normal(size=(3, N))
+    v /= np.linalg.norm(v, axis=0)
+    R = np.repeat(c, per, axis=1)[:, :N] + v * (radius * rng.uniform(0, 1, N) ** (1 / 3))
+    assert R.min() >= 0 and R.max() <= L
+    return np.ascontiguousarray(R)
 
 
 NDESIGNED = 14

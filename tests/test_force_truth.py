@@ -150,3 +150,137 @@ def test_input_conditions(box):
         if name.startswith("out of range"):
             assert ft.geom_roundings(R, L) > ft.GEOM
             assert (np.abs(R) > 2 * L).sum() >= 6 and ((R < -L / 8) | (R > 9 * L / 8)).any(axis=0).sum() >= 12
+
+
+# ---------------------------------------------------------------------------------------------
+# the Newton-3 blocks' gate terms (tests/test_gpu_block_accuracy.py)
+# ---------------------------------------------------------------------------------------------
+
+BLOCK_SIZES = (129, 512, 513, 1100, 2500, 5000)
+
+
+def test_block_depth_within_one_chain():
+    """depth_blocks: the layout n3b_set_range gives at the block tests' sizes, and never more than the one
+    chain over every term, N + 8"""
+    want = {129: (3, 1, 1, 1, 1), 512: (8, 1, 1, 1, 1), 513: (9, 2, 2, 2, 1), 1100: (18, 3, 2, 2, 1),
+            2500: (40, 5, 3, 3, 1), 5000: (79, 10, 6, 6, 1)}
+    for N in BLOCK_SIZES:
+        assert ft.block_layout(N) == want[N], N
+        T, NB, nd, R, runlen = want[N]
+        D = ft.depth_blocks(N)
+        assert D <= N + 8
+        assert D == min(132 + nd + R + 8, N + 8)
+        print(f"N = {N}: T {T}, NB {NB}, nd {nd}, R {R}: D = {D} (N + 8 = {N + 8})")
+    assert ft.depth_blocks(129) == 137 and ft.depth_blocks(5000) == 152
+    for N in range(1, 5001, 7):
+        assert ft.depth_blocks(N) <= N + 8
+
+
+def test_form_err_pinned_to_the_engine():
+    """err_e(r) = kFormErrA[e] r/lDeb + kFormErrB[e] as force_truth states it against mdqt_force_plan.cpp's
+    far_err: the a-priori radius model returns bound = (N - 1) g(radius) err(radius) (for the f32 level
+    without its constant cutoff term: apriori 2)"""
+    from mdqtplasmasims_amd.engine import tier_radius_model
+    N, L, lDeb = 5000, (5000 * 4 * np.pi / 3) ** 0.333333333, 1 / 3.0
+    for e in (1, 2, 3, 4, 5):
+        for k in (13, 9):
+            r, bound = tier_radius_model(N, L, lDeb, k, ft.MODEL_LEVEL[e], apriori=2 if e == 5 else 1)
+            assert 0 < r < L / 2, (e, k)
+            g = (1 / r + 1 / lDeb) * np.exp(-r / lDeb) / r
+            err = bound / ((N - 1) * g)
+            print(f"level {e} ({ft.TIERS[e]}), 1e-{k}: radius {r:.4f}, err {err:.6e}, force_truth {ft.form_err(e, r, lDeb):.6e}")
+            assert abs(err - ft.form_err(e, r, lDeb)) <= 1e-12 * err
+
+
+def test_form_err_grows_with_the_level():
+    """Form_i charges a pair the error of the highest level its distance allows; the kernel may take a lower
+    one: the stated errors must grow with the level at every distance"""
+    x = np.concatenate([[0.0], np.logspace(-6, 4, 400)])          # r / lDeb
+    for e in (1, 2, 3, 4):
+        assert (ft.form_err(e + 1, x, 1.0) > ft.form_err(e, x, 1.0)).all(), e
+
+
+def test_block_terms_match_a_plain_loop(box):
+    """Form_i, FormU_i, Tail_i, TailU_i and the f32 cutoff shell on 40 ions, against a double loop over the
+    reference's pair set (SpeedUp:213-222), radii that put pairs in every level"""
+    import math
+    L, lDeb = box
+    R = ft.designed_state(40, L)
+    half = L / 2
+    R[:, 21] = R[:, 20]                                # a pair on the f32 tier's cutoff shell, outside L/2
+    R[0, 20], R[0, 21] = 0.25 * L, 0.25 * L + half * (1 + 2.0 ** -23)
+    radii = {1: 0.2 * half, 2: 0.4 * half, 3: 0.6 * half, 4: 0.7 * half, 5: 0.8 * half}
+    skip = 0.9 * half
+    for on, f32cut in (((1, 2, 3, 4, 5), True), ((1, 2, 3, 4, 5), False), ((2, 4), True), ((), False)):
+        rad = {e: (radii[e] if e in on else half) for e in radii}
+        b = ft.block_terms(R, L, lDeb, rad, skip, f32cut, chunk=16)
+        form, formu, tail, tailu = (np.zeros(40) for _ in range(4))
+        nform, ntail, ncut = {e: 0 for e in on}, 0, 0
+        for i in range(40):
+            for j in range(40):
+                if i == j:
+                    continue
+                d = [R[k, i] - R[k, j] for k in range(3)]
+                d = [x - L * float(ft.c_round(np.float64(x / L))) for x in d]
+                r = math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+                g = (1 / (r * r) + 1 / (r * lDeb)) * math.exp(-r / lDeb)
+                u = math.exp(-r / lDeb) / r
+                if f32cut and 5 in on and abs(r - half) <= ft.F32CUT * 2.0 ** -24 * half:
+                    form[i] += g
+                    formu[i] += u
+                    ncut += 1
+                if not 0 < r < half:
+                    continue
+                lev = max([e for e in on if rad[e] <= r * (1 + 2.0 ** -50)], default=0)
+                if lev:
+                    nform[lev] += 1
+                    form[i] += g * ft.form_err(lev, r, lDeb)
+                    formu[i] += u * ft.form_err(lev, r, lDeb)
+                if r * (1 + 2.0 ** -50) >= skip:
+                    tail[i] += g
+                    tailu[i] += u
+                    ntail += 1
+        assert b.nform == nform and b.ntail == ntail and b.ncut == ncut
+        assert ncut == (2 + 6 if f32cut and 5 in on else 0)        # the new pair and the designed state's three
+        assert ntail > 0 and all(v > 0 for v in nform.values())
+        for got, ref in ((b.form, form), (b.formu, formu), (b.tail, tail), (b.tailu, tailu)):
+            assert np.allclose(got, ref, rtol=1e-12, atol=0)
+    # no tier, no tail: nothing
+    b = ft.block_terms(R, L, lDeb, {}, half, True)
+    assert not b.form.any() and not b.tail.any() and not b.formu.any() and not b.tailu.any()
+
+
+def test_block_gate_sees_one_cutoff_pair(orc):
+    """what test_gpu_block_accuracy.py's weak-screening cases rest on: in the box of 129 ions at Ge 0.1 one
+    pair term at the cutoff, dropped from the designed state's exact row sums, stands 1e9 gates above the
+    blocks' gate; the fast variant's shell allowance covers the pair one ulp inside L/2 and no other"""
+    o = orc.OracleSim(N0=129, Ge=0.1)
+    L, lDeb = o.const("L"), o.const("lDeb")
+    o.close()
+    R = ft.designed_state(129, L)
+    t = ft.row_sums(R, L, lDeb)
+    none = ft.block_terms(R, L, lDeb, {}, L / 2, False)
+    D = ft.depth_blocks(129)
+    r = R[0, 5] - R[0, 4]                               # one ulp inside L/2, along x: in the pair set
+    assert r < L / 2 and ft.pair_set(R, L, np.array([4]))[1][0, 5]
+    g = (1 / (r * r) + 1 / (r * lDeb)) * np.exp(-r / lDeb)
+    F = t.T.astype(np.float64)
+    assert (ft.force_err(F, t) <= ft.block_force_gate(t, none, L, D, False)).all()
+    F[0, 4] += g                                        # ion 4 loses its partner at +x: its force moves by +g
+    ratio = ft.force_err(F, t) / ft.block_force_gate(t, none, L, D, False)
+    print(f"g(L/2) = {g:.3e}: |dF_4| / gate_4 = {float(ratio[4]):.3e} (the exact variant's gate)")
+    assert ratio[4] > 1e9 and (np.delete(ratio, 4) <= 1).all()
+    # the fast variant's gate allows exactly that pair (H_4 = g: mic_r may decide it either way), and no other:
+    # ion 20's farthest partner inside the cutoff, off the shell
+    assert ft.force_err(F, t)[4] <= ft.block_force_gate(t, none, L, D, True)[4]
+    n, keep = ft.pair_set(R, L, np.array([20]))
+    d = (R[:, 20, None] - R) - L * n[:, 0, :]
+    rr = np.where(keep[0], np.sqrt((d * d).sum(axis=0)), 0.0)
+    j = int(np.argmax(rr))
+    assert t.H[20] == 0 and 0.9 * L / 2 < rr[j] < L / 2
+    gj = (1 / (rr[j] ** 2) + 1 / (rr[j] * lDeb)) * np.exp(-rr[j] / lDeb)
+    F = t.T.astype(np.float64)
+    F[:, 20] -= gj * d[:, j] / rr[j]
+    ratio = ft.force_err(F, t) / ft.block_force_gate(t, none, L, D, True)
+    print(f"ion 20 without its partner at r = {rr[j]:.3f}: |dF_20| / gate_20 = {float(ratio[20]):.3e} (the fast variant's gate)")
+    assert ratio[20] > 1e8 and (np.delete(ratio, 20) <= 1).all()
