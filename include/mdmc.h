@@ -137,8 +137,10 @@ int mdmc_set_psi(mdmc_ctx* c, const double* psi);
  *                         collision scatter on a step where a member has a hit), and one launch per kind for
  *                         the per-step observables of the recorded stages, on the ensemble's stream: the
  *                         single-job kernels' bodies on each member's own argument block in device memory.
- *                         mdmc_ensemble_md_steps and, in mdmc_ensemble_run, every MD stage but the QT programs'
- *                         pump and recorded stage go this way; g(r) and the autocorrelations stay per member.
+ *                         mdmc_ensemble_md_steps and, in mdmc_ensemble_run, every MD stage go this way; g(r) and
+ *                         the autocorrelations stay per member.  For the QT tagging programs (qt_model 1..3) the
+ *                         QT substeps, the tagging and the tagged ions' moments and X distribution are batched
+ *                         too (the mdmc_ensemble_*qt* calls below; the pump and recorded stage of the run).
  * Members need no lockstep: any mdmc_* call on a member between ensemble calls is legal and the member simply
  * carries its state (its buffer parity, its stale pre-advanced positions, its own collision frequency and
  * laser force included). */
@@ -163,9 +165,29 @@ int       mdmc_ensemble_enable_timing(mdmc_ensemble* e, int on); /* timestamps o
 /* out[0..5): the anneal launches since the last call: sum (ms), count, median, min, max (ms);
  * out[5..11): wall ms of the last run's stages (timing on): anneal, pre-record MD, QT pump, recorded MD,
  * autocorrelations, the rest; out[11..16), out[16..21): the same five figures of the batched force and of the
- * batched velocity-Verlet launches (md_batch 1, timing on; the launches' own timestamps).
- * Fills min(n, 21) entries, n >= 3 */
+ * batched velocity-Verlet launches (md_batch 1, timing on; the launches' own timestamps); out[21..26),
+ * out[26..31): those of the batched QT launches and of the X distribution's chunk kernel.
+ * Fills min(n, 31) entries, n >= 3 */
 int       mdmc_ensemble_kernel_times(mdmc_ensemble* e, double* out, int n);
+
+/* ---- ensembles of the QT tagging variants (qt_model 1..3; an error with the context-has-no-QT message
+ * otherwise) ----
+ * Under md_batch 0 each call is the members' own call, member by member.  Under md_batch 1 each is one launch
+ * for all members (or the few stated) on the ensemble's stream, fenced behind the members' streams and
+ * synchronised once; every member computes what its own call computes, bit for bit. */
+/* mdmc_qsteps of every member: ceil(n / 32) launches whatever njobs is.  Every member keeps its own qstep index,
+ * so members need not be in lockstep */
+int       mdmc_ensemble_qsteps(mdmc_ensemble* e, int n);
+/* mdmc_tag_qt of every member, one launch: tags [njobs][N] or NULL, n_up [njobs] or NULL */
+int       mdmc_ensemble_tag_qt(mdmc_ensemble* e, int* tags, int* n_up);
+/* mdmc_tagged_moments_qt of every member: out4 [njobs][4]; distX [njobs][4001] or NULL.  X ONLY: the row the
+ * programs write (vel_distX_timestep%06d.dat, QTT:1128-1136) and the only one a recorded step needs, so the
+ * batched kernel evaluates a third of the three-row kernel's terms; distX[k] holds the bits of row 0 of member
+ * k's mdmc_tagged_moments_qt.  One launch for the moments, two more with distX */
+int       mdmc_ensemble_tagged_moments_qt(mdmc_ensemble* e, double* out4, double* distX);
+/* kernel launches the batched QT, tagging, moment and distribution paths have issued since creation (md_batch 0
+ * leaves it unchanged); mdmc_ensemble_md_launches does not count them */
+int       mdmc_ensemble_qt_launches(mdmc_ensemble* e, unsigned long long* out);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,10 @@ MDMC_SIGNATURES = [
     ("mdmc_ensemble_run", C.c_int, [C.c_void_p, C.c_int]),
     ("mdmc_ensemble_enable_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("mdmc_ensemble_kernel_times", C.c_int, [C.c_void_p, _dp, C.c_int]),
+    ("mdmc_ensemble_qsteps", C.c_int, [C.c_void_p, C.c_int]),
+    ("mdmc_ensemble_tag_qt", C.c_int, [C.c_void_p, _ip, _ip]),
+    ("mdmc_ensemble_tagged_moments_qt", C.c_int, [C.c_void_p, _dp, _dp]),
+    ("mdmc_ensemble_qt_launches", C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
 ]
 
 # (name, restype, argtypes) of every symbol include/mdqt.h declares

@@ -80,13 +80,14 @@ struct mdmc_ensemble {
     int mdBatch = 0;                   // mdmc_ensemble_set_md_batch: 0 member by member, 1 batched
     unsigned long long mdLaunches = 0; // kernel launches the batched path has issued
     // device blocks of a stretch, one allocation: N3Args [2][J], VVArgs [2][J] (the two buffer parities of
-    // the collisionless step), MDObsArgs [J], then VVArgs [J] of a step with collision draws
+    // the collisionless step), MDObsArgs [J], MDKdeXArgs [J], then VVArgs [J] of a step with collision draws
     char* dBlocks = nullptr;
     mdqt::N3Args* dN3 = nullptr;
     mdqt::VVArgs* dVV = nullptr;
     mdqt::MDObsArgs* dObs = nullptr;
+    mdqt::MDKdeXArgs* dKdeX = nullptr;
     mdqt::VVArgs* dVVc = nullptr;
-    size_t hdrBytes = 0;               // of the first three
+    size_t hdrBytes = 0;               // of the first four
     mdqt::PinRing hdrRing, vvRing;     // a stretch's blocks (4 slots); a collisional step's VVArgs [J] (64 slots)
     bool open = false;                 // inside a stretch: the members' streams are fenced behind `stream`
     int parity = 0;                    // which of the two block sets the next step takes
@@ -96,6 +97,16 @@ struct mdmc_ensemble {
     std::vector<hipEvent_t> evMember;  // [J] fences: a member's stream -> `stream`
     hipEvent_t evEns = nullptr;        // `stream` -> the members' streams
     mdqt::LaunchTimer forceTimer, vvTimer;   // the batched force / velocity-Verlet launches' timestamps
+    // ---- batched QT (mdmc_ensemble.cpp, "batched QT"; members with qt_model 1..3 only) ----
+    static constexpr int kDistSlots = 4;   // recorded steps whose X distributions may be on their way at once
+    unsigned long long qtLaunches = 0; // kernel launches the batched QT, tagging and distribution paths have issued
+    char* dQt = nullptr;               // [J] SubstepArgs of a QT chunk, or PumpTagArgs of the tagging: the next launch's
+    mdqt::PinRing qtRing;              // their way over, in stream order
+    double* dDist = nullptr;           // [kDistSlots][J][TKDE_BINS]: the reduce's rows
+    double* hDist = nullptr;           // pinned, the same shape: one copy per slot brings all members' rows
+    double* hMom = nullptr;            // pinned [J][kTagMomentSums]: mdmc_ensemble_tagged_moments_qt's sums
+    hipEvent_t evDist[kDistSlots] = {};   // behind the copy into a slot of hDist
+    mdqt::LaunchTimer qtTimer, distTimer;   // the batched QT launches'; the distribution's chunk kernel's
 };
 
 namespace mdmc {
@@ -114,6 +125,11 @@ void vv_args(const mdmc_ctx* c, const double* hits, int nhits, mdqt::VVArgs& v);
 int collision_draws(mdmc_ctx* c, hipStream_t drain, double** hits, int* nhits);
 int pair_corr_queue(mdmc_ctx* c);                   // g(r) of the member queued on its stream, evDrain behind the copy
 int qsteps_async(mdmc_ctx* c, int n);
+// a launch of m <= MAXSUB QT substeps of the member from its qstep index: qsteps_async's block, shared with the
+// batched launch (the caller advances qidx)
+void substep_args(const mdmc_ctx* c, int m, mdqt::SubstepArgs& a);
+// the sums of k_tag_moments' tag set 0 -> recordTaggedParticleMoments' four moments (QTT:1106-1109)
+void moments_qt_from_sums(const double* m, double* out4);
 // main() of the program for J contexts in lockstep: J = 1 without an ensemble is mdmc_run
 int run_members(mdmc_ctx* const* cs, int J, mdmc_ensemble* ens, int verbose);
 
@@ -130,5 +146,14 @@ int ensemble_md_temperatures(mdmc_ensemble* e, int k);
 int ensemble_md_tag_moments(mdmc_ensemble* e, int k);
 int ensemble_md_store_velocities(mdmc_ensemble* e, int t);
 int ensemble_md_pair_corr_queue(mdmc_ensemble* e);   // every member's g(r) on its own stream, fenced both ways
+// batched QT (md_batch 1), queued on the ensemble's stream inside a stretch: n qsteps of every member in
+// ceil(n / MAXSUB) launches; the spin-up tagging in one; k_tag_moments of tag set 0 into row k of every member's
+// dMom; the X distribution into slot `slot` of the distribution ring and its copy to the pinned ring
+int ensemble_qt_steps(mdmc_ensemble* e, int n);
+int ensemble_qt_tag(mdmc_ensemble* e);
+int ensemble_qt_tag_moments(mdmc_ensemble* e, int k);
+int ensemble_qt_dist_x(mdmc_ensemble* e, int slot);
+// waits for slot's copy: [J][TKDE_BINS], valid until the slot is queued again (NULL: error)
+const double* ensemble_qt_dist_rows(mdmc_ensemble* e, int slot);
 
 }  // namespace mdmc

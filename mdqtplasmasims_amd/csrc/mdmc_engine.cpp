@@ -13,11 +13,14 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <random>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "mdmc_ctx.hpp"   // struct mdmc_ctx; HIPCHK, mdqt::set_error, Mt32
+#include "mdqt_writer.hpp"   // FileWriter, LgText: the QT tagging programs' distribution files
 
 using namespace mdqt;
 
@@ -633,17 +636,21 @@ static int need_qt(const mdmc_ctx* c, const char* what) {
 
 // qstep() x n (QTT:555-756): the pumping model's fused QT substeps on this system's velocities
 // (no drift: the MD steps move the ions), in launches of up to MAXSUB substeps
+void mdmc::substep_args(const mdmc_ctx* c, int m, SubstepArgs& a) {
+    memset(&a, 0, sizeof a);
+    a.R = c->dR; a.V = c->dV; a.F = c->dA; a.Fpart = nullptr; a.nseg = 1;
+    a.psi = c->dPsi; a.tPart = c->dTp; a.oor = c->dFlags;
+    a.n = c->N; a.S = c->S; a.gid0 = 0; a.q0 = c->qidx;
+    a.nsub = m; a.do_step = 0; a.do_qt = 1; a.U = nullptr;
+    a.L = c->L;
+    a.qc = c->qc;
+}
+
 int mdmc::qsteps_async(mdmc_ctx* c, int n) {
     while (n > 0) {
         const int m = n < MAXSUB ? n : MAXSUB;
         SubstepArgs a;
-        memset(&a, 0, sizeof a);
-        a.R = c->dR; a.V = c->dV; a.F = c->dA; a.Fpart = nullptr; a.nseg = 1;
-        a.psi = c->dPsi; a.tPart = c->dTp; a.oor = c->dFlags;
-        a.n = c->N; a.S = c->S; a.gid0 = 0; a.q0 = c->qidx;
-        a.nsub = m; a.do_step = 0; a.do_qt = 1; a.U = nullptr;
-        a.L = c->L;
-        a.qc = c->qc;
+        substep_args(c, m, a);
         HIPCHK(launch_substeps_r(a, c->dFTab, 0, c->st));
         c->qidx += (uint64_t)m;
         n -= m;
@@ -683,10 +690,11 @@ static int tagged_moments_qt_queue(mdmc_ctx* c, double* sums_dev, bool dist) {
     if (dist) HIPCHK(launch_tagged_kde(c->dV, c->dTags, c->N, c->S, c->dKdePart, c->dKde, c->st));
     return 0;
 }
-static void moments_qt_from_sums(const double* m, double* out4) {   // :1106-1109
+void mdmc::moments_qt_from_sums(const double* m, double* out4) {   // :1106-1109
     const unsigned num = (unsigned)m[4];
     out4[0] = m[0] / num; out4[1] = m[1] / num; out4[2] = m[2] / num; out4[3] = m[3] / num;
 }
+using mdmc::moments_qt_from_sums;
 
 extern "C" int mdmc_tagged_moments_qt(mdmc_ctx* c, double out4[4], double* dist) {
     if (need_qt(c, "mdmc_tagged_moments_qt")) return -1;
@@ -756,8 +764,8 @@ extern "C" const char* mdmc_save_directory(const mdmc_ctx* c) { return c ? c->sa
 // their own streams first and then drains member by member (wait for the copies, format,
 // write), so a step with a host round trip costs one wait, not J in a row, and the host
 // formats one member's rows while the device runs the others' MD step.  An ensemble with
-// md_batch 1 queues the MD steps and per-step observables of stage_md, stage_md_temp_axes and
-// stage_record_mcmd as batched launches on the ensemble's stream instead (batched()).
+// md_batch 1 queues the MD steps, QT steps and per-step observables of every MD stage as batched
+// launches on the ensemble's stream instead (batched()).
 // ------------------------------------------------------------------------------------------
 namespace {
 
@@ -770,6 +778,7 @@ struct Run {
     mdmc_ensemble* ens;           // NULL: one context, annealed by its own launch
     int verbose;
     Clock::time_point t0;
+    std::unique_ptr<FileWriter> writer;   // stage_record_qtt's pool: one per run, joined before the stage ends
 };
 
 struct Files {                    // one open file per member, closed on every way out
@@ -865,7 +874,7 @@ int stage_anneal(Run& r) {
 
 // n MDStep()s of every member; `count` prints the step counter every 100 (:1081-1089, :1126-1135)
 // An ensemble with md_batch 1 steps its members in batched launches on the ensemble's stream (mdmc_ensemble.cpp,
-// "batched MD stretches"): every MD stage below but the QT programs' pump and recorded stage is one stretch.
+// "batched MD stretches", "batched QT"): every MD stage below is one stretch.
 bool batched(const Run& r) { return r.ens && r.ens->mdBatch == 1; }
 
 int stage_md(Run& r, int n, bool count) {
@@ -1015,6 +1024,15 @@ int stage_anisotropy(Run& r) {
 int stage_pump(Run& r) {
     for (int j = 0; j < r.J; ++j) r.c[j]->collisionFreq = 0;
     if (r.verbose) printf("pumpMDTimeSteps=%d\nquantumStepsPerMD=%d\n", r.c[0]->pumpSteps, r.c[0]->qtRatio);
+    if (batched(r)) {
+        // one stretch: per pump step ceil(ratio / MAXSUB) QT launches and one MD step for all members, then
+        // one tagging launch; nobody reads the counts, so nothing comes back
+        mdmc_ensemble* e = r.ens;
+        if (mdmc::ensemble_md_begin(e)) return -1;
+        for (int k = 0; k < r.c[0]->pumpSteps; k++)
+            if (mdmc::ensemble_qt_steps(e, r.c[0]->qtRatio) || mdmc::ensemble_md_step(e)) return -1;
+        return mdmc::ensemble_qt_tag(e) || mdmc::ensemble_md_end(e) ? -1 : 0;
+    }
     for (int k = 0; k < r.c[0]->pumpSteps; k++)
         for (int j = 0; j < r.J; ++j) {
             mdmc_ctx* c = r.c[j];
@@ -1026,10 +1044,99 @@ int stage_pump(Run& r) {
     return 0;
 }
 
+// vel_distX_timestep%06d.dat of one member and step (QTT:1128-1136) from a snapshot of its 4,001 values, on
+// the run's writer pool: LgText's rows are fprintf("%lg\t%lg\n")'s bytes
+void submit_dist_file(Run& r, const mdmc_ctx* c, int k, const double* dist) {
+    char name[64];
+    snprintf(name, sizeof name, "vel_distX_timestep%06d.dat", k);
+    auto snap = std::make_shared<const std::vector<double>>(dist, dist + TKDE_BINS);
+    r.writer->submit(c->saveDir + name, "w", [snap](LgText& t) {
+        for (int i = 0; i < TKDE_BINS; i++) {
+            t.num((double)(i - 2000) * 0.0025); t.ch('\t'); t.num((*snap)[i]); t.ch('\n');
+        }
+    });
+}
+
+// the pool of a run: at most 16 threads whatever J is, and a cap on the files in flight, so the snapshots
+// held stay (cap + 1) x 32 KB however far the stage runs ahead of the disk
+void start_writer(Run& r) {
+    const int hw = (int)std::thread::hardware_concurrency();
+    const int threads = std::min(16, std::max(1, hw - 1));
+    r.writer.reset(new FileWriter(threads, (size_t)4 * threads));
+}
+
+int join_writer(Run& r) {
+    std::string err;
+    if (r.writer && r.writer->flush(&err)) return set_error("%s", err.c_str());
+    return 0;
+}
+
+// the stage's taggedMoments.dat and temperature.dat of one member from its buffered rows (md_batch 1): the
+// lines stage_record_qtt writes step by step otherwise, through the same two functions
+int write_recorded_qtt(mdmc_ctx* c, FILE* fm, FILE* ft) {
+    const int T = c->T;
+    std::vector<double> s((size_t)T * 4), m((size_t)T * kTagMomentSums);
+    HIPCHK(hipMemcpyAsync(s.data(), c->dTemp, s.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(m.data(), c->dMom, m.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    for (int k = 0; k < T; ++k) {
+        double mom[4], tt[4];
+        moments_qt_from_sums(&m[(size_t)kTagMomentSums * k], mom);
+        fprintf(fm, "%lg\t%lg\t%lg\t%lg\t%lg\n", k * c->p.timeStep, mom[0], mom[1], mom[2], mom[3]);   // :1114
+        temps_from_sums(c, &s[(size_t)4 * k], tt);
+        fprintf(ft, "%lg\n", tt[0]);
+    }
+    return 0;
+}
+
+// the recorded stage in batched launches (md_batch 1), one stretch.  Per step seven launches whatever J is:
+// the tag moments into row k of every member's dMom, the X distribution (two) into a slot of the ensemble's
+// ring and one copy of all members' rows to the pinned ring, the temperatures into row k of dTemp, the force
+// and velocity-Verlet launches, the velocity store.  The host formats nothing itself: it hands the rows of the
+// step kLag back to the pool, so it queues that far ahead of the device.  g(r) every 100 steps stays each
+// member's own.  The moments and temperatures come back once, at the end.
+int stage_record_qtt_batched(Run& r, Files& fm, Files& ft) {
+    mdmc_ensemble* e = r.ens;
+    const int T = r.c[0]->T;
+    constexpr int kLag = mdmc_ensemble::kDistSlots - 1;
+    for (int j = 0; j < r.J; ++j)
+        if (ensure_step_buffers(r.c[j], T)) return -1;
+    auto drain = [&](int k) {
+        const double* rows = mdmc::ensemble_qt_dist_rows(e, k % mdmc_ensemble::kDistSlots);
+        if (!rows) return -1;
+        for (int j = 0; j < r.J; ++j) submit_dist_file(r, r.c[j], k, rows + (size_t)j * TKDE_BINS);
+        return 0;
+    };
+    if (mdmc::ensemble_md_begin(e)) return -1;
+    for (int k = 0; k < T; k++) {
+        const bool gr = k % 100 == 0;
+        if (mdmc::ensemble_qt_tag_moments(e, k) || mdmc::ensemble_qt_dist_x(e, k % mdmc_ensemble::kDistSlots) ||
+            (gr && mdmc::ensemble_md_pair_corr_queue(e)) || mdmc::ensemble_md_temperatures(e, k) ||
+            mdmc::ensemble_md_step(e) || mdmc::ensemble_md_store_velocities(e, k))
+            return -1;
+        if (gr && r.verbose) printf("%d\n", k);
+        if (gr)
+            for (int j = 0; j < r.J; ++j) {
+                HIPCHK(hipEventSynchronize(r.c[j]->evDrain));
+                if (write_pair_corr_file(r.c[j], k)) return -1;
+            }
+        if (k >= kLag && drain(k - kLag)) return -1;
+    }
+    for (int k = std::max(0, T - kLag); k < T; ++k)
+        if (drain(k)) return -1;
+    if (mdmc::ensemble_md_end(e)) return -1;
+    for (int j = 0; j < r.J; ++j)
+        if (write_recorded_qtt(r.c[j], fm.f[j], ft.f[j])) return -1;
+    return 0;
+}
+
 // QTT step 6 :1235-1245: per step the tagged moments and distribution, g(r) every 100, the temperature
-// (all read back into the member's landing area, evDrain behind them), then the MD step
+// (all read back into the member's landing area, evDrain behind them), then the MD step.  The distribution
+// files are formatted and written by the run's pool in every mode; taggedMoments.dat and temperature.dat are
+// one appended line a step, in order, and stay here.
 int stage_record_qtt(Run& r) {
     const int T = r.c[0]->T;
+    start_writer(r);
     Files fm, ft;
     for (int j = 0; j < r.J; ++j) {
         fm.f.push_back(open_in(r.c[j], "taggedMoments.dat", "a"));
@@ -1037,6 +1144,7 @@ int stage_record_qtt(Run& r) {
         if (!fm.f.back() || !ft.f.back())
             return set_error("cannot open taggedMoments.dat / temperature.dat in %s", r.c[j]->saveDir.c_str());
     }
+    if (batched(r)) return stage_record_qtt_batched(r, fm, ft) || join_writer(r) ? -1 : 0;
     for (int k = 0; k < T; k++) {
         const bool gr = k % 100 == 0;
         for (int j = 0; j < r.J; ++j) {
@@ -1059,19 +1167,13 @@ int stage_record_qtt(Run& r) {
             double mom[4], tt[4];
             moments_qt_from_sums(c->hStage, mom);
             fprintf(fm.f[j], "%lg\t%lg\t%lg\t%lg\t%lg\n", k * c->p.timeStep, mom[0], mom[1], mom[2], mom[3]);   // :1114
-            char name[64];
-            snprintf(name, sizeof name, "vel_distX_timestep%06d.dat", k);                                     // :1128-1136
-            FILE* fd = open_in(c, name, "w");
-            if (!fd) return set_error("cannot open %s%s", c->saveDir.c_str(), name);
-            const double* dist = c->hStage + 24;
-            for (int i = 0; i < TKDE_BINS; i++) fprintf(fd, "%lg\t%lg\n", (double)(i - 2000) * 0.0025, dist[i]);
-            fclose(fd);
+            submit_dist_file(r, c, k, c->hStage + 24);            // the X row, snapshotted: the next step lands here
             if (gr && write_pair_corr_file(c, k)) return -1;
             temps_from_sums(c, c->hStage + 20, tt);
             fprintf(ft.f[j], "%lg\n", tt[0]);
         }
     }
-    return 0;
+    return join_writer(r);
 }
 
 }  // namespace

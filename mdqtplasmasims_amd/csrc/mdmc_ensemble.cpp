@@ -7,8 +7,10 @@
 // own stream, one host thread, so they overlap on the chip: the single context's code on the single
 // context's arguments.  Mode 1 steps all members with one force and one velocity-Verlet launch per step on
 // the ensemble's stream ("batched MD stretches" below), again the single-job kernels' bodies on each member's
-// own argument block.  The stretches' argument blocks travel through two pinned rings and the launches are timed
-// by event pairs: mdqt_batch.hpp's PinRing and LaunchTimer, shared with the MDQT ensembles.
+// own argument block.  For the QT tagging programs mode 1 batches the QT substeps, the tagging and the tagged
+// ions' moments and X distribution the same way ("batched QT" below).  The argument blocks travel through pinned
+// rings and the launches are timed by event pairs: mdqt_batch.hpp's PinRing and LaunchTimer, shared with the MDQT
+// ensembles.
 #include <algorithm>
 #include <memory>
 
@@ -29,12 +31,14 @@ constexpr int kVVSlots = 64;     // collisional steps whose blocks may be on the
 int md_blocks_create(mdmc_ensemble* e) {
     const size_t J = e->jobs.size();
     const size_t n3 = 2 * J * sizeof(N3Args), vv = 2 * J * sizeof(VVArgs), ob = J * sizeof(MDObsArgs);
-    e->hdrBytes = n3 + vv + ob;
+    const size_t kx = J * sizeof(MDKdeXArgs);
+    e->hdrBytes = n3 + vv + ob + kx;
     if (hipMalloc((void**)&e->dBlocks, e->hdrBytes + J * sizeof(VVArgs)) != hipSuccess)
         return set_error("mdmc_ensemble_create: allocating the MD argument blocks of %zu jobs failed", J);
     e->dN3 = reinterpret_cast<N3Args*>(e->dBlocks);
     e->dVV = reinterpret_cast<VVArgs*>(e->dBlocks + n3);
     e->dObs = reinterpret_cast<MDObsArgs*>(e->dBlocks + n3 + vv);
+    e->dKdeX = reinterpret_cast<MDKdeXArgs*>(e->dBlocks + n3 + vv + ob);
     e->dVVc = reinterpret_cast<VVArgs*>(e->dBlocks + e->hdrBytes);
     if (e->hdrRing.create(e->hdrBytes, kHdrSlots, hipEventDisableTiming) ||
         e->vvRing.create(J * sizeof(VVArgs), kVVSlots, hipEventDisableTiming))
@@ -52,6 +56,49 @@ int md_blocks_create(mdmc_ensemble* e) {
 
 int need_open(const mdmc_ensemble* e, const char* what) {
     if (!e->open) return set_error("%s outside a batched MD stretch", what);
+    return 0;
+}
+
+// the batched QT's own areas, for an ensemble of QT tagging jobs
+constexpr int kQtSlots = 8;      // QT chunks / taggings whose blocks may be on their way at once
+
+int qt_blocks_create(mdmc_ensemble* e) {
+    const size_t J = e->jobs.size();
+    const size_t dist = (size_t)mdmc_ensemble::kDistSlots * J * TKDE_BINS * sizeof(double);
+    if (hipMalloc((void**)&e->dQt, J * sizeof(SubstepArgs)) != hipSuccess || hipMalloc((void**)&e->dDist, dist) != hipSuccess ||
+        hipHostMalloc((void**)&e->hDist, dist, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void**)&e->hMom, J * kTagMomentSums * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        return set_error("mdmc_ensemble_create: allocating the QT blocks and distribution rings of %zu jobs failed", J);
+    if (e->qtRing.create(J * sizeof(SubstepArgs), kQtSlots, hipEventDisableTiming)) return -1;
+    for (hipEvent_t& ev : e->evDist) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return 0;
+}
+
+// the ensemble's stream behind every member's stream
+int fence_in(mdmc_ensemble* e) {
+    for (size_t k = 0; k < e->jobs.size(); ++k) {
+        HIPCHK(hipEventRecord(e->evMember[k], e->jobs[k]->st));
+        HIPCHK(hipStreamWaitEvent(e->stream, e->evMember[k], 0));
+    }
+    return 0;
+}
+
+// a member's per-step observable blocks: the rows go to its dTemp / dMom (a stretch) or, scratch, its sums
+// land in dOut as its own calls' do
+void obs_args(const mdmc_ctx* c, bool scratch, MDObsArgs& o, MDKdeXArgs& x) {
+    memset(&o, 0, sizeof o);
+    o.V = c->dV; o.tags = c->dTags; o.N = c->N; o.S = c->S; o.T = c->T;
+    o.temp = scratch ? c->dOut : c->dTemp; o.mom = scratch ? c->dOut : c->dMom; o.vs = c->dVS;
+    memset(&x, 0, sizeof x);
+    x.V = c->dV; x.tags = c->dTags; x.N = c->N; x.S = c->S; x.part = c->dKdePart;
+}
+
+static_assert(sizeof(PumpTagArgs) <= sizeof(SubstepArgs), "a QT ring slot holds one block per member of either kind");
+
+int need_qt(const mdmc_ensemble* e, const char* what) {
+    if (!e) return set_error("%s: NULL ensemble", what);
+    if (!e->jobs[0]->qt) return set_error("%s: the context has no QT (qt_model 0)", what);
+    if (e->open) return set_error("%s inside a batched MD stretch", what);
     return 0;
 }
 
@@ -79,16 +126,14 @@ int mdmc::ensemble_md_begin(mdmc_ensemble* e) {
     if (e->open) return set_error("ensemble_md_begin inside a batched MD stretch");
     const size_t J = e->jobs.size();
     HIPCHK(hipSetDevice(e->dev));
-    for (size_t k = 0; k < J; ++k) {
-        HIPCHK(hipEventRecord(e->evMember[k], e->jobs[k]->st));
-        HIPCHK(hipStreamWaitEvent(e->stream, e->evMember[k], 0));
-    }
+    if (fence_in(e)) return -1;
     char* h = nullptr;
     int slot = 0;
     if (e->hdrRing.take(&h, &slot)) return -1;
     N3Args* n3 = reinterpret_cast<N3Args*>(h);
     VVArgs* vv = reinterpret_cast<VVArgs*>(h + 2 * J * sizeof(N3Args));
     MDObsArgs* ob = reinterpret_cast<MDObsArgs*>(h + 2 * J * (sizeof(N3Args) + sizeof(VVArgs)));
+    MDKdeXArgs* kx = reinterpret_cast<MDKdeXArgs*>(ob + J);
     e->obsCap = e->jobs[0]->capTemp;
     for (size_t k = 0; k < J; ++k) {
         mdmc_ctx* c = e->jobs[k];
@@ -102,10 +147,7 @@ int mdmc::ensemble_md_begin(mdmc_ensemble* e) {
             mdmc::n3_args(c, n3[par * J + k]);
             mdmc::vv_args(c, nullptr, 0, vv[par * J + k]);
         }                                         // two swaps: the member's pointers are back
-        MDObsArgs& o = ob[k];
-        memset(&o, 0, sizeof o);
-        o.V = c->dV; o.tags = c->dTags; o.N = c->N; o.S = c->S; o.T = c->T;
-        o.temp = c->dTemp; o.mom = c->dMom; o.vs = c->dVS;
+        obs_args(c, false, ob[k], kx[k]);
         e->obsCap = std::min(e->obsCap, c->capTemp);
         e->coll[k] = c->p.timeStep * c->collisionFreq > 0;
         e->skip[k] = 0;
@@ -215,6 +257,185 @@ int mdmc::ensemble_md_pair_corr_queue(mdmc_ensemble* e) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Batched QT (md_batch 1; an ensemble of the QT tagging programs).  The pump models' QT substeps, the spin-up
+// tagging and the tagged ions' moments and X distribution of all members, each in one launch (two for the
+// distribution) on the ensemble's stream: the single-job kernels' bodies on each member's own block.  A QT
+// chunk's blocks are what mdmc::qsteps_async builds (mdmc::substep_args) — each member's own qstep index and
+// Philox key, so members need not be in lockstep; the by-lane table is member 0's, since all members share the
+// model's parameters — and go through the pinned QT ring in stream order, as the tagging's do.  The moment and
+// distribution blocks are resident with the stretch's.  The distribution's rows land in a slot of the
+// ensemble's [kDistSlots][J][TKDE_BINS] device ring and one copy a slot brings all members' rows to the pinned
+// ring; evDist[slot] behind the copy is all the host ever waits for.
+// These are queued between ensemble_md_begin and ensemble_md_end (run()), or by the entry points below between
+// fence_in and a synchronisation of the ensemble's stream.
+// ------------------------------------------------------------------------------------------------------------
+int mdmc::ensemble_qt_steps(mdmc_ensemble* e, int n) {
+    const size_t J = e->jobs.size();
+    while (n > 0) {
+        const int m = n < MAXSUB ? n : MAXSUB;
+        char* h = nullptr;
+        int slot = 0;
+        if (e->qtRing.take(&h, &slot)) return -1;
+        SubstepArgs* a = reinterpret_cast<SubstepArgs*>(h);
+        int max_n = 0;
+        for (size_t k = 0; k < J; ++k) {
+            mdmc_ctx* c = e->jobs[k];
+            mdmc::substep_args(c, m, a[k]);
+            c->qidx += (uint64_t)m;
+            max_n = std::max(max_n, c->N);
+        }
+        if (e->qtRing.send(slot, e->dQt, J * sizeof(SubstepArgs), e->stream)) return -1;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (e->timing && e->qtTimer.take(&e0, &e1)) return -1;
+        // a[0] picks the instance (the slot is read by the copy only, and not rewritten before take() hands it out again)
+        HIPCHK(launch_substeps_pump_ens(reinterpret_cast<const SubstepArgs*>(e->dQt), a[0], (int)J, max_n, e->jobs[0]->dFTab,
+                                        e->stream, e0, e1));
+        ++e->qtLaunches;
+        n -= m;
+    }
+    return 0;
+}
+
+int mdmc::ensemble_qt_tag(mdmc_ensemble* e) {                      // tagParticles, QTT:1022-1067
+    const size_t J = e->jobs.size();
+    char* h = nullptr;
+    int slot = 0;
+    if (e->qtRing.take(&h, &slot)) return -1;
+    PumpTagArgs* a = reinterpret_cast<PumpTagArgs*>(h);
+    int max_n = 0;
+    for (size_t k = 0; k < J; ++k) {
+        const mdmc_ctx* c = e->jobs[k];
+        memset(&a[k], 0, sizeof a[k]);                               // mdmc_tag_qt's arguments
+        a[k].psi = c->dPsi; a[k].n = c->N; a[k].S = c->S; a[k].gid0 = 0; a[k].q = c->qidx; a[k].tags = c->dTags;
+        a[k].qc = c->qc;
+        max_n = std::max(max_n, c->N);
+    }
+    if (e->qtRing.send(slot, e->dQt, J * sizeof(PumpTagArgs), e->stream)) return -1;
+    HIPCHK(launch_tag_spin_up_ens(reinterpret_cast<const PumpTagArgs*>(e->dQt), (int)J, max_n, e->stream));
+    ++e->qtLaunches;
+    return 0;
+}
+
+int mdmc::ensemble_qt_tag_moments(mdmc_ensemble* e, int k) {
+    if (need_open(e, "ensemble_qt_tag_moments")) return -1;
+    if (k < 0 || k >= e->obsCap) return set_error("ensemble_qt_tag_moments: step %d outside the %d buffered", k, e->obsCap);
+    HIPCHK(launch_tag_moments_ens(e->dObs, (int)e->jobs.size(), k, e->stream));
+    ++e->qtLaunches;
+    return 0;
+}
+
+int mdmc::ensemble_qt_dist_x(mdmc_ensemble* e, int slot) {
+    if (slot < 0 || slot >= mdmc_ensemble::kDistSlots) return set_error("ensemble_qt_dist_x: slot %d outside the ring", slot);
+    const size_t J = e->jobs.size(), row = J * TKDE_BINS;
+    int max_N = 0;
+    for (const mdmc_ctx* c : e->jobs) max_N = std::max(max_N, c->N);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (e->timing && e->distTimer.take(&e0, &e1)) return -1;
+    HIPCHK(launch_tagged_kde_x_ens(e->dKdeX, (int)J, max_N, e->dDist + row * slot, e->stream, e0, e1));
+    e->qtLaunches += 2;
+    HIPCHK(hipMemcpyAsync(e->hDist + row * slot, e->dDist + row * slot, row * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipEventRecord(e->evDist[slot], e->stream));
+    return 0;
+}
+
+const double* mdmc::ensemble_qt_dist_rows(mdmc_ensemble* e, int slot) {
+    if (slot < 0 || slot >= mdmc_ensemble::kDistSlots) {
+        set_error("ensemble_qt_dist_rows: slot %d outside the ring", slot);
+        return nullptr;
+    }
+    const hipError_t r = hipEventSynchronize(e->evDist[slot]);
+    if (r != hipSuccess) {
+        set_error("ensemble_qt_dist_rows: %s", hipGetErrorString(r));
+        return nullptr;
+    }
+    return e->hDist + e->jobs.size() * TKDE_BINS * (size_t)slot;
+}
+
+// mdmc_qsteps of every member
+extern "C" int mdmc_ensemble_qsteps(mdmc_ensemble* e, int n) {
+    if (need_qt(e, "mdmc_ensemble_qsteps")) return -1;
+    HIPCHK(hipSetDevice(e->dev));
+    if (e->mdBatch == 1) {
+        if (fence_in(e) || mdmc::ensemble_qt_steps(e, n)) return -1;
+        HIPCHK(hipStreamSynchronize(e->stream));
+        return 0;
+    }
+    for (mdmc_ctx* c : e->jobs)
+        if (mdmc::qsteps_async(c, n)) return -1;
+    return sync_members(e);
+}
+
+// mdmc_tag_qt of every member: tags [J][N] or NULL, n_up [J] or NULL
+extern "C" int mdmc_ensemble_tag_qt(mdmc_ensemble* e, int* tags, int* n_up) {
+    if (need_qt(e, "mdmc_ensemble_tag_qt")) return -1;
+    HIPCHK(hipSetDevice(e->dev));
+    const size_t J = e->jobs.size();
+    if (e->mdBatch != 1) {
+        for (size_t k = 0; k < J; ++k)
+            if (mdmc_tag_qt(e->jobs[k], tags ? tags + k * (size_t)e->jobs[k]->N : nullptr, n_up ? n_up + k : nullptr)) return -1;
+        return 0;
+    }
+    if (fence_in(e) || mdmc::ensemble_qt_tag(e)) return -1;
+    const size_t N = (size_t)e->jobs[0]->N;
+    std::vector<int> h(tags || !n_up ? 0 : J * N);
+    int* dst = tags ? tags : h.data();
+    if (tags || n_up)
+        for (size_t k = 0; k < J; ++k)
+            HIPCHK(hipMemcpyAsync(dst + k * N, e->jobs[k]->dTags, N * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; n_up && k < J; ++k) {
+        int cnt = 0;
+        for (size_t i = 0; i < N; ++i) cnt += dst[k * N + i];
+        n_up[k] = cnt;
+    }
+    return 0;
+}
+
+// mdmc_tagged_moments_qt of every member: out4 [J][4]; distX [J][TKDE_BINS] or NULL — the X row only, the one
+// the programs write (QTT:1128-1136)
+extern "C" int mdmc_ensemble_tagged_moments_qt(mdmc_ensemble* e, double* out4, double* distX) {
+    if (need_qt(e, "mdmc_ensemble_tagged_moments_qt")) return -1;
+    if (!out4) return set_error("mdmc_ensemble_tagged_moments_qt: NULL argument");
+    HIPCHK(hipSetDevice(e->dev));
+    const size_t J = e->jobs.size();
+    if (e->mdBatch != 1) {
+        std::vector<double> d(distX ? (size_t)3 * TKDE_BINS : 0);
+        for (size_t k = 0; k < J; ++k) {
+            if (mdmc_tagged_moments_qt(e->jobs[k], out4 + 4 * k, distX ? d.data() : nullptr)) return -1;
+            if (distX) std::copy_n(d.begin(), TKDE_BINS, distX + k * TKDE_BINS);
+        }
+        return 0;
+    }
+    if (fence_in(e)) return -1;
+    // the members' blocks with the sums landing in their dOut, as their own call's do; through a slot of the
+    // stretches' ring to where a stretch keeps them (the next stretch uploads its own)
+    char* h = nullptr;
+    int slot = 0;
+    if (e->hdrRing.take(&h, &slot)) return -1;
+    MDObsArgs* ob = reinterpret_cast<MDObsArgs*>(h);
+    MDKdeXArgs* kx = reinterpret_cast<MDKdeXArgs*>(ob + J);
+    for (size_t k = 0; k < J; ++k) obs_args(e->jobs[k], true, ob[k], kx[k]);
+    if (e->hdrRing.send(slot, e->dObs, J * (sizeof(MDObsArgs) + sizeof(MDKdeXArgs)), e->stream)) return -1;
+    HIPCHK(launch_tag_moments_ens(e->dObs, (int)J, 0, e->stream));
+    ++e->qtLaunches;
+    if (distX && mdmc::ensemble_qt_dist_x(e, 0)) return -1;
+    for (size_t k = 0; k < J; ++k)
+        HIPCHK(hipMemcpyAsync(e->hMom + kTagMomentSums * k, e->jobs[k]->dOut, kTagMomentSums * sizeof(double),
+                              hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; k < J; ++k) mdmc::moments_qt_from_sums(e->hMom + kTagMomentSums * k, out4 + 4 * k);
+    if (distX) std::copy_n(e->hDist, J * TKDE_BINS, distX);
+    return 0;
+}
+
+extern "C" int mdmc_ensemble_qt_launches(mdmc_ensemble* e, unsigned long long* out) {
+    if (!e || !out) return set_error("mdmc_ensemble_qt_launches: NULL argument");
+    if (need_qt(e, "mdmc_ensemble_qt_launches")) return -1;
+    *out = e->qtLaunches;
+    return 0;
+}
+
 extern "C" int mdmc_ensemble_job_params(const mdmc_params* base, int k, mdmc_params* out) {
     if (!base || !out) return set_error("mdmc_ensemble_job_params: NULL argument");
     if (k < 0 || k >= kEnsembleMaxJobs) return set_error("mdmc_ensemble_job_params: job index %d outside [0, %d)", k, kEnsembleMaxJobs);
@@ -233,8 +454,15 @@ extern "C" void mdmc_ensemble_destroy(mdmc_ensemble* e) {
     if (e->dBlocks) (void)hipFree(e->dBlocks);
     e->hdrRing.destroy();
     e->vvRing.destroy();
+    e->qtRing.destroy();
+    if (e->dQt) (void)hipFree(e->dQt);
+    if (e->dDist) (void)hipFree(e->dDist);
+    if (e->hDist) (void)hipHostFree(e->hDist);
+    if (e->hMom) (void)hipHostFree(e->hMom);
+    for (hipEvent_t ev : e->evDist)
+        if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evMember) (void)hipEventDestroy(ev);
-    for (LaunchTimer* t : {&e->annealTimer, &e->forceTimer, &e->vvTimer}) t->destroy();
+    for (LaunchTimer* t : {&e->annealTimer, &e->forceTimer, &e->vvTimer, &e->qtTimer, &e->distTimer}) t->destroy();
     if (e->evEns) (void)hipEventDestroy(e->evEns);
     if (e->dArgs) (void)hipFree(e->dArgs);
     if (e->hArgs) (void)hipHostFree(e->hArgs);
@@ -277,6 +505,7 @@ extern "C" int mdmc_ensemble_create(const mdmc_params* p, int njobs, mdmc_ensemb
         hipHostMalloc((void**)&e->hAcc, J * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
         return set_error("mdmc_ensemble_create: allocating the argument blocks of %d jobs failed", njobs);
     if (md_blocks_create(e.get())) return -1;
+    if (e->jobs[0]->qt && qt_blocks_create(e.get())) return -1;
     *out = e.release();
     return 0;
 }
@@ -388,7 +617,7 @@ extern "C" int mdmc_ensemble_run(mdmc_ensemble* e, int verbose) {
 extern "C" int mdmc_ensemble_enable_timing(mdmc_ensemble* e, int on) {
     if (!e) return set_error("NULL ensemble");
     e->timing = on > 0;
-    for (LaunchTimer* t : {&e->annealTimer, &e->forceTimer, &e->vvTimer}) t->reset();
+    for (LaunchTimer* t : {&e->annealTimer, &e->forceTimer, &e->vvTimer, &e->qtTimer, &e->distTimer}) t->reset();
     return 0;
 }
 
@@ -413,16 +642,18 @@ extern "C" int mdmc_ensemble_md_launches(mdmc_ensemble* e, unsigned long long* o
 // the batched launches' own durations (their dispatch timestamps) since the last call: out[0..5) = the anneal's
 // sum (ms), launches, median, minimum, maximum (ms); out[5..11) = wall time (ms) of the last run's stages: anneal,
 // pre-record MD, QT pump, recorded MD, autocorrelations, the rest; out[11..16) and out[16..21) = the five figures
-// of the batched force and velocity-Verlet launches (md_batch 1).  Fills what n holds (n >= 3); resets the lists
+// of the batched force and velocity-Verlet launches (md_batch 1); out[21..26) and out[26..31) = those of the
+// batched QT launches and of the X distribution's chunk kernel.  Fills what n holds (n >= 3); resets the lists
 extern "C" int mdmc_ensemble_kernel_times(mdmc_ensemble* e, double* out, int n) {
     if (!e || !out) return set_error("mdmc_ensemble_kernel_times: NULL argument");
     if (n < 3) return set_error("mdmc_ensemble_kernel_times: need at least 3 doubles");
     HIPCHK(hipSetDevice(e->dev));
     HIPCHK(hipStreamSynchronize(e->stream));
-    constexpr int kOut = 5 + mdmc_ensemble::kStages + 10;
+    constexpr int kOut = 5 + mdmc_ensemble::kStages + 20;
     double v[kOut] = {};
     if (e->annealTimer.stats(v) || e->forceTimer.stats(v + 5 + mdmc_ensemble::kStages) ||
-        e->vvTimer.stats(v + 10 + mdmc_ensemble::kStages))
+        e->vvTimer.stats(v + 10 + mdmc_ensemble::kStages) || e->qtTimer.stats(v + 15 + mdmc_ensemble::kStages) ||
+        e->distTimer.stats(v + 20 + mdmc_ensemble::kStages))
         return -1;
     std::copy(e->stage_ms, e->stage_ms + mdmc_ensemble::kStages, v + 5);
     for (int i = 0; i < n && i < kOut; ++i) out[i] = v[i];

@@ -550,6 +550,17 @@ hipError_t launch_collide_ens(const VVArgs* jobs, int njobs, int max_nhits, hipS
 hipError_t launch_temperatures_ens(const MDObsArgs* jobs, int njobs, int k, hipStream_t s);
 hipError_t launch_tag_moments_ens(const MDObsArgs* jobs, int njobs, int k, hipStream_t s);
 hipError_t launch_store_velocities_ens(const MDObsArgs* jobs, int njobs, int max_N, int t, hipStream_t s);
+// The X row of the tagged distribution of every member of an ensemble of QT tagging jobs
+// (mdmc_ensemble_qt_kernels.hip): launch_tagged_kde's component 0, bit for bit, member k's 4,001 values into
+// rows[k][TKDE_BINS]; two launches; ev0 / ev1 (or null) take the chunk kernel's own timestamps
+struct MDKdeXArgs {
+    const double* V;
+    const int* tags;    // [N] tag set 0
+    int N, S;
+    double* part;       // [chunks][1][TKDE_BINS]: the member's own partial buffer
+};
+hipError_t launch_tagged_kde_x_ens(const MDKdeXArgs* jobs, int njobs, int max_N, double* rows, hipStream_t s,
+                                   hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // error message of the C ABI (mdqt_last_error), shared by the mdmc_* and mdlc_* entry points
 int set_error(const char* fmt, ...);
 // the reference's "(unsigned)(x)" printed with %d (x86-64 runtime behaviour):

@@ -69,9 +69,13 @@ __device__ __forceinline__ void tag_spin_up_ion(const double* __restrict__ psi, 
     tags[i] = up;
 }
 
-// k_tagged_kde's workgroup: 256 bins (bx) x chunk `ch` of TKDE_CHUNK ions, LDS staged, ascending
+// k_tagged_kde's workgroup: 256 bins (bx) x chunk `ch` of TKDE_CHUNK ions, LDS staged, ascending.
+// NC = the components evaluated, the first NC of (x, y, z): 3 in the programs' own kernels, 1 where only the
+// X row is written (mdmc_ensemble_qt_kernels.hip).  A component's terms, their order and its skips do not
+// depend on the others, so component c of any NC holds the same bits; the partials are [chunks][NC][TKDE_BINS].
 constexpr int TKDE_CHUNK = 256;
 
+template <int NC = 3>
 __device__ __forceinline__ void tagged_kde_chunk(const double* __restrict__ V, const int* __restrict__ tags, int N,
                                                  int S, int bin0, double* __restrict__ part, int bx, int ch,
                                                  double (*sv)[TKDE_CHUNK], int* st) {
@@ -79,7 +83,8 @@ __device__ __forceinline__ void tagged_kde_chunk(const double* __restrict__ V, c
     const int i0 = ch * TKDE_CHUNK;
     const int i = i0 + threadIdx.x;
     if (i < N) {
-        sv[0][threadIdx.x] = V[i]; sv[1][threadIdx.x] = V[S + i]; sv[2][threadIdx.x] = V[2 * S + i];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) sv[c][threadIdx.x] = V[c * S + i];
         st[threadIdx.x] = tags[i];
     } else {
         st[threadIdx.x] = 0;
@@ -87,27 +92,30 @@ __device__ __forceinline__ void tagged_kde_chunk(const double* __restrict__ V, c
     __syncthreads();
     const double vel = (double)(j + bin0) * 0.0025;                 // QTT:250 (bin0 = -2000)
     const double V2 = kKdeV2;                                      // 1 / (2 * 0.002^2), QTT:1072
-    double p[3] = {0., 0., 0.};
+    double p[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) p[c] = 0.;
     const int m = min(TKDE_CHUNK, N - i0);
     for (int k = 0; k < m; ++k) {
         if (!st[k]) continue;                                      // uniform over the workgroup
         // a component whose term is exactly +0 on every bin of the wave (|vel - v| >= 0.0773:
         // V2 d^2 >= 746.9, below exp's underflow) adds exact zeros there and is skipped
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
+        for (int c = 0; c < NC; ++c)
             if (__builtin_amdgcn_ballot_w64(!(fabs(vel - sv[c][k]) >= kKdeSkip)))
                 p[c] += exp(-V2 * (vel - sv[c][k]) * (vel - sv[c][k]));   // :1100-1102
     }
     if (j < TKDE_BINS)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) part[((size_t)ch * 3 + c) * TKDE_BINS + j] = p[c];
+        for (int c = 0; c < NC; ++c) part[((size_t)ch * NC + c) * TKDE_BINS + j] = p[c];
 }
 
-// k_tagged_kde_reduce's element k = c * TKDE_BINS + j: the chunk partials in chunk order
+// k_tagged_kde_reduce's element k = c * TKDE_BINS + j (c < NC): the chunk partials in chunk order
+template <int NC = 3>
 __device__ __forceinline__ void tagged_kde_reduce_1(const double* __restrict__ part, int nch, double* __restrict__ out,
                                                     int k) {
     double s = 0.;
-    for (int q = 0; q < nch; ++q) s = s + part[(size_t)q * 3 * TKDE_BINS + k];
+    for (int q = 0; q < nch; ++q) s = s + part[(size_t)q * NC * TKDE_BINS + k];
     out[k] = s / (6.0 * sqrt(2 * M_PI * 0.002 * 0.002));            // :1121-1123
 }
 

@@ -10,7 +10,10 @@
 //     caller hands over, so the device keeps stepping while the text is produced (SURVEY §8(f)1,
 //     "async writers").  flush() is the only join point: the engine calls it before anything
 //     reads the files back (readConditions), at the end of mdqt_run and in mdqt_destroy, and
-//     reports the first I/O error there.
+//     reports the first I/O error there.  A writer made with a cap holds at most that many
+//     submitted-but-unwritten files: submit() blocks at the cap, so the snapshots in flight stay
+//     bounded however far the caller runs ahead (the QT tagging programs' recorded stage: one
+//     4,001-row file per job and step).  Without a cap (the default) submit() never blocks.
 #pragma once
 
 #include <cerrno>
@@ -70,7 +73,8 @@ class FileWriter {
   public:
     using Fill = std::function<void(LgText&)>;
 
-    explicit FileWriter(int threads = 4) {
+    // cap: the most files submitted and not yet written (queued or being written); 0 = no limit
+    explicit FileWriter(int threads = 4, size_t cap = 0) : cap_(cap) {
         if (threads < 1) threads = 1;
         for (int i = 0; i < threads; ++i) pool_.emplace_back([this] { loop(); });
     }
@@ -86,10 +90,12 @@ class FileWriter {
     FileWriter(const FileWriter&) = delete;
     FileWriter& operator=(const FileWriter&) = delete;
 
-    // format and write `path` (mode "w" or "a") on a pool thread; `fill` owns its data
+    // format and write `path` (mode "w" or "a") on a pool thread; `fill` owns its data.  With a cap,
+    // waits until fewer than `cap` files are unwritten
     void submit(std::string path, const char* mode, Fill fill) {
         {
-            std::lock_guard<std::mutex> g(m_);
+            std::unique_lock<std::mutex> g(m_);
+            if (cap_) room_.wait(g, [this] { return pending_ < cap_; });
             q_.push_back(Job{std::move(path), mode, std::move(fill)});
             ++pending_;
         }
@@ -142,15 +148,17 @@ class FileWriter {
                 std::lock_guard<std::mutex> g(m_);
                 if (!e.empty() && err_.empty()) err_ = e;
                 if (--pending_ == 0) done_.notify_all();
+                if (cap_) room_.notify_one();
             }
         }
     }
 
     std::mutex m_;
-    std::condition_variable cv_, done_;
+    std::condition_variable cv_, done_, room_;
     std::deque<Job> q_;
     std::vector<std::thread> pool_;
     size_t pending_ = 0;
+    const size_t cap_;
     bool stop_ = false;
     std::string err_;
 };

@@ -13,10 +13,12 @@
         the k_monte_carlo_lds dispatches of such a trace: the 20 after the first 5, median (min-max)
     python tools/mdmc_ensemble_rate.py e2e --bin A/bin/mdmc --seq-bin B/bin/mdmc --njobs 8 [--qt_model 2] [--runs 3]
         wall clock with process start of `mdmc 1 --njobs=J --seed=777 --quiet=1` (build A) against J sequential
-        `mdmc k --seed=777+k-1 --quiet=1` (build B), and `diff -r` of the two trees; --no-seq: the ensemble only; --plain: build A without --njobs (J = 1)
+        `mdmc k --seed=777+k-1 --quiet=1` (build B), and `diff -r` of the two trees; --no-seq: the ensemble only; --plain: build A without --njobs (J = 1);
+        --keep DIR keeps the last ensemble tree, --same-as DIR compares it with one kept before (another build or --md_batch)
     python tools/mdmc_ensemble_rate.py stages --njobs 8 [--qt_model 2] [--md_batch 1]
         wall time by stage of one ensemble run (host timers around the stage helpers); with --md_batch 1 also the
-        batched force and velocity-Verlet launches' own time
+        batched force and velocity-Verlet launches' own time and, with --qt_model, the batched QT launches' and the
+        X distribution's chunk kernel's
     python tools/mdmc_ensemble_rate.py md [--jobs 1,8,64] [--md_batch 0|1] [--steps 300]
         the MD step of the ensemble (N = 4096, force_kernel 1, collisionless, after 2,000 Metropolis steps): wall us
         per ensemble step of one md_steps(--steps) call after a warm-up call of 50; with --md_batch 1 also, from a
@@ -160,6 +162,12 @@ def cmd_e2e(a):
             res["diff_r_identical"] = r.returncode == 0 and r.stdout == ""
             res["files"] = sum(len(f) for _, _, f in os.walk(work + "/ens"))
             res["done"] = max(res["ens_s"]) < min(res["seq_s"]) and res["diff_r_identical"]
+        if a.same_as:                                    # the tree of another build or mode, kept by its --keep
+            r = subprocess.run(["diff", "-r", work + "/ens", a.same_as], capture_output=True, text=True)
+            res["same_as"] = dict(tree=a.same_as, identical=r.returncode == 0 and r.stdout == "")
+        if a.keep:
+            shutil.rmtree(a.keep, ignore_errors=True)
+            shutil.move(work + "/ens", a.keep)
     finally:
         shutil.rmtree(work, ignore_errors=True)
     print(json.dumps({"e2e": res}))
@@ -183,6 +191,9 @@ def cmd_stages(a):
     if a.md_batch == 1:
         res.update(md_force_ms=t["md_force_ms"], n_md_force=t["n_md_force"], md_force_median_us=t["md_force_median_ms"] * 1e3,
                    md_vv_ms=t["md_vv_ms"], n_md_vv=t["n_md_vv"], md_vv_median_us=t["md_vv_median_ms"] * 1e3)
+        if a.qt_model:                                   # zeros from a build that predates the batched QT stages
+            res.update(qt_ms=t["qt_ms"], n_qt=t["n_qt"], qt_median_us=t["qt_median_ms"] * 1e3,
+                       qt_dist_ms=t["qt_dist_ms"], n_qt_dist=t["n_qt_dist"], qt_dist_median_us=t["qt_dist_median_ms"] * 1e3)
     print(json.dumps({"stages": res}))
 
 
@@ -197,6 +208,7 @@ def main():
     p.add_argument("--qt_model", type=int, default=0); p.add_argument("--runs", type=int, default=3)
     p.add_argument("--no-seq", action="store_true"); p.add_argument("--plain", action="store_true")
     p.add_argument("--limit", type=float, default=300.); p.add_argument("--md_batch", type=int, choices=[0, 1])
+    p.add_argument("--keep"); p.add_argument("--same-as")
     p.set_defaults(f=cmd_e2e)
     p = sub.add_parser("stages"); p.add_argument("--njobs", type=int, default=8)
     p.add_argument("--qt_model", type=int, default=0); p.add_argument("--md_batch", type=int, choices=[0, 1])
