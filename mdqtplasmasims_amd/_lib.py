@@ -164,6 +164,7 @@ SIGNATURES = [
                                   C.c_int]),
     ("mdqt_potentials_raw", C.c_int, [C.c_int, C.c_double, C.c_double, _dp, C.c_size_t, _dp, C.c_int,
                                       C.c_int, C.c_int]),
+    ("mdqt_device_math", C.c_int, [C.c_int, _dp, C.c_int, _dp, _dp, C.c_int]),
     ("mdqt_epotential", C.c_int, [C.c_void_p, _dp]),
     ("mdqt_observables", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     ("mdqt_setup_directories", C.c_int, [C.c_void_p]),

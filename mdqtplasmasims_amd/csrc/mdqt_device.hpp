@@ -132,23 +132,38 @@ __device__ __forceinline__ double hfma(double z, double p, double c) {
     return fma(z, p, c);
 #endif
 }
-// the reduction + kernels without the range check (valid for |x| < 2^20), branch-free
+// the reduction + kernels without the range check (valid for |x| < 2^20), branch-free.  The reduced
+// argument is kept as r + y: the first reduction step is exact for |x| < 2^20; the second is an exact
+// product (p + pe = n P2) and an exact sum (two-sum: r1 + its error = r0 - p, for any size of r0 against
+// p, so also next to a zero, where r0 ~ p), the third lands in the tail.  The kernels take the tail the
+// way fdlibm's do (sin: r - ((z (y/2 - v ps) - y) - v S1); cos: ... + (z pc - r y)).  Without the tail r's
+// own half ulp came on top of the kernels' error — 1.38 ulp of the result measured on the GPU (sin and
+// cos, results >= 2^-10), against the "< 1 ulp" stated above; with it 0.78 ulp, next to the zeros 0.50 ulp
+// and 5.4e-20 absolute (a C transcription on 2e7 arguments; tests/test_gpu_device_math.py holds the GPU to
+// < 1 ulp and 2^-53 absolute, docs/QT_KERNEL.md has its figures).  Used by the qt_math 1 kernels only.
 __device__ __forceinline__ void sincos_fast(double x, double& sn, double& cs) {
     const double n = rint(x * 0.63661977236758134308);           // 2/pi
-    double r = fma(-n, 1.57079632679489655800e+00, x);            // pi/2 = P1 + P2 + P3
-    r = fma(-n, 6.12323399573676603587e-17, r);
-    r = fma(-n, -1.49738490485916983014e-33, r);
+    const double r0 = fma(-n, 1.57079632679489655800e+00, x);     // pi/2 = P1 + P2 + P3
+    const double p = n * 6.12323399573676603587e-17;
+    const double pe = fma(n, 6.12323399573676603587e-17, -p);
+    const double r1 = r0 - p;
+    const double bb = r1 - r0;
+    const double y1 = ((r0 - (r1 - bb)) - (p + bb)) - pe;         // (r0 - n P2) - r1, exactly up to its own rounding
+    const double t = fma(-n, -1.49738490485916983014e-33, y1);
+    const double r = r1 + t;
+    const double y = (r1 - r) + t;
     const double z = r * r;
     const double ps = hfma(z, hfma(z, hfma(z, hfma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08),
                                            2.75573137070700676789e-06), -1.98412698298579493134e-04),
                            8.33333333332248946124e-03);
-    const double sr = fma(r * z, hfma(z, ps, -1.66666666666666324348e-01), r);
+    const double v = r * z;
+    const double sr = r - ((z * (0.5 * y - v * ps) - y) - v * -1.66666666666666324348e-01);
     const double pc = z * hfma(z, hfma(z, hfma(z, hfma(z, hfma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09),
                                                     -2.75573143513906633035e-07), 2.48015872894767294178e-05),
                                    -1.38888888888741095749e-03), 4.16666666666666019037e-02);
     const double hz = 0.5 * z;
     const double wc = 1.0 - hz;
-    const double cr = wc + (((1.0 - wc) - hz) + z * pc);
+    const double cr = wc + (((1.0 - wc) - hz) + (z * pc - r * y));
     const int q = (int)n & 3;
     const double s0 = (q & 1) ? cr : sr, c0 = (q & 1) ? sr : cr;
     sn = (q & 2) ? -s0 : s0;
@@ -167,8 +182,11 @@ __device__ __forceinline__ void sincos_q(double x, double& sn, double& cs) {
 // + r by the same FMA Cody-Waite reduction (three-part constant), |r| <= pi/64, then
 // e^(ix) = e^(2 pi i (m mod 64)/64) e^(ir) with e^(ir) by its Taylor series (sin to r^9, cos to
 // r^8: truncation below 1e-20) and the table entries correctly rounded (60-digit decimal
-// arithmetic).  22 VALU and one LDS read instead of sincos_fast's ~40; <= 2 ulp.  |x| < 2^20 (the
-// callers take the library beyond).  `tab`: kSinCos64 (cos, sin pairs) in LDS or global memory.
+// arithmetic).  22 VALU and one LDS read instead of sincos_fast's ~40.  Error: <= 2^-52 ABSOLUTE
+// (1.51e-16 measured over |x| < 2^20, tests/test_gpu_device_math.py) — not a statement in ulps of the
+// result: that reaches 2.3 ulp at x = 0.049 and is unbounded near the zeros.  The absolute statement is
+// what the kernels need (c2 = c2re + dms sin: the value is scaled by a coupling and added).  |x| < 2^20
+// (the callers take the library beyond).  `tab`: kSinCos64 (cos, sin pairs) in LDS or global memory.
 static __constant__ const double kSinCos64[128] = {
     0x1.0000000000000p+0, 0x0.0p+0, 0x1.fd88da3d12526p-1, 0x1.917a6bc29b42cp-4,
     0x1.f6297cff75cb0p-1, 0x1.8f8b83c69a60bp-3, 0x1.e9f4156c62ddap-1, 0x1.294062ed59f06p-2,

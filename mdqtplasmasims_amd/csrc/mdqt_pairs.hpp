@@ -19,9 +19,14 @@ struct PairC {
 // 2^t of the Newton-3 kernels' exact pair form by a 64-entry table (round 3):
 // t64 = 64 t (the multiplier scaled by 64: exact), m = rint(t64), g = t64 - m (exact, |g| <= 1/2),
 // 2^t = 2^(m >> 6) 2^((m & 63)/64) 2^(g/64) with the table entry correctly rounded (60-digit decimal
-// arithmetic) and 2^(g/64) = e^(g ln2/64) by its degree-5 Taylor series (|g ln2/64| <= 0.0055:
-// truncation 3.5e-17); <= 2 ulp.  Five FMAs instead of eleven for three integer operations and one
-// LDS read.  The cutoff is folded into the exponent shift: 0 (2^-1100 underflows) unless keep — one 32-bit
+// arithmetic) and 2^(g/64) = 1 + g q(g), q the degree-4 fit of (e^(g ln2/64) - 1) / g on [-1/2, 1/2]
+// (Chebyshev interpolation in 80-digit arithmetic, coefficients rounded to double: 2.4e-18 relative, 0.02
+// ulp), the result formed as fma(te, g q, te): the table entry's half ulp and one rounding, 1.01 ulp
+// measured (tests/test_gpu_device_math.py holds it to <= 2 ulp; tests/force_truth.py's budget KF counts
+// 2).  The form before — the degree-5 Taylor series p, then p te — had the series' truncation (0.32 ulp
+// at the ties |g| = 1/2) and p's own rounding on top: 2.13 ulp measured, above the 2 ulp it stated.  The
+// same six operations, instead of eleven FMAs, for three integer operations and one LDS read.
+// The cutoff is folded into the exponent shift: 0 (2^-1100 underflows) unless keep — one 32-bit
 // select instead of a 64-bit one on the result; for finite t only.
 static __constant__ const double kExp2Tab64[64] = {
     0x1.0000000000000p+0, 0x1.02c9a3e778061p+0, 0x1.059b0d3158574p+0, 0x1.0874518759bc8p+0,
@@ -46,13 +51,12 @@ __device__ __forceinline__ double exp2_neg_cut_tab(double t64, bool keep, const 
     const double g = t64 - m;
     const int mi = (int)m;
     const double te = tab[mi & 63];
-    double p = 0x1.5d87fe78a6731p-40;
-    p = fma(p, g, 0x1.3b2ab6fba4e77p-31);
-    p = fma(p, g, 0x1.c6b08d704a0c0p-23);
-    p = fma(p, g, 0x1.ebfbdff82c58fp-15);
-    p = fma(p, g, 0x1.62e42fefa39efp-7);
-    p = fma(p, g, 1.0);
-    return ldexp(p * te, keep ? (mi >> 6) : -1100);
+    double q = 0x1.5d8812769ed72p-40;
+    q = fma(q, g, 0x1.3b2ad0385b409p-31);
+    q = fma(q, g, 0x1.c6b08d70496c1p-23);
+    q = fma(q, g, 0x1.ebfbdff82ac52p-15);
+    q = fma(q, g, 0x1.62e42fefa39efp-7);
+    return ldexp(fma(te, g * q, te), keep ? (mi >> 6) : -1100);
 }
 // the mid tier's 2^t (Newton-3 blocks, pairs >= r_mid apart): the same table times a degree-4 fit of
 // 2^(g/64) on g in [-1/2, 1/2] (Chebyshev interpolation in long double, coefficients rounded to double;

@@ -12,8 +12,10 @@
 //     kernel's DPP tree order), constants folded on the host (kick scale, h dP, 2(1+kRat)gamToE);
 //   * step(): one coordinate per lane (lanes 0..11 and 14..15 x, 12 y, 13 z), exact operations.
 //
-// Results differ from the exact mode (qt_math 0) by rounding only (~1e-15 relative per
-// substep; tests/test_gpu_parity.py bounds it against the oracle).  The thread-per-ion and
+// Results differ from the exact mode (qt_math 0) by rounding only: tests/test_gpu_qt_accuracy.py holds
+// every instance, per ion, to the rounding count of tests/qt_truth.py (K ~ 14 roundings of |psi| per
+// substep, plus the coupling phase's own conditioning) against an extended-precision truth; measured
+// err / bound <= 0.11 (docs/QT_KERNEL.md, "The QT kernels' per-ion gate").  The thread-per-ion and
 // lane-per-state kernels below perform the same operations in the same order: bit-identical.
 #include "mdqt_qtfast.hpp"
 #include "mdqt_pump_device.hpp"   // the body k_tag_spin_up shares with the pump ensemble's batched kernel

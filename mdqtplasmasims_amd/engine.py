@@ -98,6 +98,21 @@ def potentials_raw(R, L: float, lDeb: float, nseg: int = 0, device: int = -1, va
     return U
 
 
+DEVICE_MATH_FN = {"sincos_tab": 0, "sincos_fast": 1, "sincos_q2": 2, "rsq3": 3, "exp_neg": 4, "exp2_tab": 5}
+
+
+def device_math(fn, x, device: int = -1):
+    """The kernels' device math function `fn` (a name of DEVICE_MATH_FN or its code) on the array x,
+    through the inline functions the kernels call (include/mdqt.h mdqt_device_math).  Returns
+    (sin, cos) for the sincos forms, else one array; "exp2_tab" takes x = 64 t."""
+    code = DEVICE_MATH_FN[fn] if isinstance(fn, str) else int(fn)
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    a = np.zeros(x.size)
+    b = np.zeros(x.size) if code < 3 else None
+    check(lib().mdqt_device_math(code, dptr(x), x.size, dptr(a), dptr(b), int(device)), "device_math")
+    return (a, b) if code < 3 else a
+
+
 def comm_unique_id() -> bytes:
     """a fresh RCCL unique id (rank 0 makes it; the launcher broadcasts it)"""
     buf = C.create_string_buffer(128)
@@ -423,4 +438,4 @@ def tier_radius_model(N: int, L: float, lDeb: float, k: int, level: int, hi: flo
     return r.value, b.value
 
 
-__all__ = ["forces_raw", "potentials_raw", "tier_radius_model", "Simulation", "MdqtError", "default_params", "device_count", "slab", "NBINS", "NUM_STATES"]
+__all__ = ["forces_raw", "potentials_raw", "device_math", "DEVICE_MATH_FN", "tier_radius_model", "Simulation", "MdqtError", "default_params", "device_count", "slab", "NBINS", "NUM_STATES"]

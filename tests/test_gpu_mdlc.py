@@ -59,6 +59,8 @@ def checker_run(orc, seed, job, N0, steps):
 
 # ---- 1. one step, no-jump branch ----
 def test_one_step_no_jump(orc):
+    """(a 1e-12 gate against the double checker; tests/test_gpu_qt_accuracy.py holds the same kernel per ion to
+    a derived rounding bound against an extended-precision truth, over 17 and 32 steps)"""
     N0, seed, job = 70, 4242, 3                        # 70 ions: neither a whole wave nor a whole workgroup
     rng = np.random.default_rng(11)
     psi = random_states(rng, N0)

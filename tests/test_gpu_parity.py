@@ -279,6 +279,8 @@ def _evolved_state(orc, N0=300, seed=21, nmd=4):
 
 @pytest.mark.parametrize("qt_math", [0, 1, 2])
 def test_qstep_matches_oracle(eng, orc, qt_math):
+    """one qstep against the double oracle, max |dpsi| < 1e-12 (a global gate; tests/test_gpu_qt_accuracy.py
+    holds the same kernels per ion to a derived rounding bound ~1e-14 against an extended-precision truth)"""
     o = _evolved_state(orc)
     st = o.get_state()
     s = eng.Simulation(N0=300, seed=21, rng_mode=1)
