@@ -1,6 +1,6 @@
 // Internal header of the Monte-Carlo + MD host engine: the context behind include/mdmc.h's opaque mdmc_ctx,
-// an ensemble of them (struct mdmc_ensemble), and the functions of mdmc_engine.cpp that mdmc_ensemble.cpp
-// drives (namespace mdmc).  Not installed: the C ABI sees both structs as opaque.
+// an ensemble of them (struct mdmc_ensemble), and what crosses between mdmc_engine.cpp (the context), mdmc_run.cpp
+// (main() by stage) and mdmc_ensemble.cpp (namespace mdmc).  Not installed: the C ABI sees both structs as opaque.
 #pragma once
 
 #include <random>
@@ -130,7 +130,13 @@ int qsteps_async(mdmc_ctx* c, int n);
 void substep_args(const mdmc_ctx* c, int m, mdqt::SubstepArgs& a);
 // the sums of k_tag_moments' tag set 0 -> recordTaggedParticleMoments' four moments (QTT:1106-1109)
 void moments_qt_from_sums(const double* m, double* out4);
-// main() of the program for J contexts in lockstep: J = 1 without an ensemble is mdmc_run
+FILE* open_in(const mdmc_ctx* c, const char* name, const char* mode);   // fopen in the member's save directory
+void pair_corr_finish(const mdmc_ctx* c, std::vector<double>& g);       // g(r) from the landed histogram (:627-635)
+int autocorr_queue(mdmc_ctx* c, double* out);                           // the four autocorrelations [4][T] and their copy, queued
+void temps_from_sums(const mdmc_ctx* c, const double* s, double* out4);      // k_temperatures' sums -> T, Tx, Ty, Tz
+void moments_from_sums(const mdmc_ctx* c, const double* m, double* out16);   // k_tag_moments' sums -> the four tag sets' moments
+int tagged_moments_qt_queue(mdmc_ctx* c, double* sums_dev, bool dist);       // tag set 0's sums (+ the three-component KDE), queued
+// mdmc_run.cpp: main() of the program for J contexts in lockstep: J = 1 without an ensemble is mdmc_run
 int run_members(mdmc_ctx* const* cs, int J, mdmc_ensemble* ens, int verbose);
 
 // mdmc_ensemble.cpp: nsteps Metropolis steps of every member, chunked launches on the ensemble's stream
@@ -143,17 +149,47 @@ int ensemble_md_begin(mdmc_ensemble* e);
 int ensemble_md_step(mdmc_ensemble* e);
 int ensemble_md_end(mdmc_ensemble* e);
 int ensemble_md_temperatures(mdmc_ensemble* e, int k);
-int ensemble_md_tag_moments(mdmc_ensemble* e, int k);
+int ensemble_tag_moments(mdmc_ensemble* e, int k, bool qt);   // row k of dMom; charges qt_launches() (qt) or md_launches()
 int ensemble_md_store_velocities(mdmc_ensemble* e, int t);
 int ensemble_md_pair_corr_queue(mdmc_ensemble* e);   // every member's g(r) on its own stream, fenced both ways
 // batched QT (md_batch 1), queued on the ensemble's stream inside a stretch: n qsteps of every member in
-// ceil(n / MAXSUB) launches; the spin-up tagging in one; k_tag_moments of tag set 0 into row k of every member's
-// dMom; the X distribution into slot `slot` of the distribution ring and its copy to the pinned ring
+// ceil(n / MAXSUB) launches; the spin-up tagging in one; the X distribution into slot `slot` of the distribution
+// ring and its copy to the pinned ring
 int ensemble_qt_steps(mdmc_ensemble* e, int n);
 int ensemble_qt_tag(mdmc_ensemble* e);
-int ensemble_qt_tag_moments(mdmc_ensemble* e, int k);
 int ensemble_qt_dist_x(mdmc_ensemble* e, int slot);
 // waits for slot's copy: [J][TKDE_BINS], valid until the slot is queued again (NULL: error)
 const double* ensemble_qt_dist_rows(mdmc_ensemble* e, int slot);
+
+// What a stage queues a step on: one member on its own stream (c), or the whole ensemble in batched launches
+// (e, md_batch 1).  Exactly one of the two is set; every method is the member's call or its batched twin.
+struct MdLane {
+    mdmc_ctx* c;
+    mdmc_ensemble* e;
+    int begin() const { return e ? ensemble_md_begin(e) : 0; }
+    int end() const { return e ? ensemble_md_end(e) : 0; }
+    int md_step() const { return e ? ensemble_md_step(e) : md_step_async(c); }
+    int temperatures(int k) const {
+        if (e) return ensemble_md_temperatures(e, k);
+        HIPCHK(mdqt::launch_temperatures(c->dV, c->N, c->S, c->dTemp + (size_t)4 * k, c->st));
+        return 0;
+    }
+    int tag_moments(int k) const {
+        if (e) return ensemble_tag_moments(e, k, false);
+        HIPCHK(mdqt::launch_tag_moments(c->dV, c->dTags, c->N, c->dMom + (size_t)20 * k, c->st));
+        return 0;
+    }
+    int store_velocities(int k) const { return e ? ensemble_md_store_velocities(e, k) : mdmc_record_velocities(c, k); }
+    int pair_corr_queue() const { return e ? ensemble_md_pair_corr_queue(e) : mdmc::pair_corr_queue(c); }
+    int qt_steps(int n) const { return e ? ensemble_qt_steps(e, n) : qsteps_async(c, n); }
+    int qt_tag() const { return e ? ensemble_qt_tag(e) : mdmc_tag_qt(c, nullptr, nullptr); }
+};
+// a run's lanes: one ensemble lane under md_batch 1, else J member lanes in job order (mdmc_run: J = 1, no ensemble)
+inline std::vector<MdLane> md_lanes(mdmc_ctx* const* cs, int J, mdmc_ensemble* ens) {
+    if (ens && ens->mdBatch == 1) return {MdLane{nullptr, ens}};
+    std::vector<MdLane> l;
+    for (int j = 0; j < J; ++j) l.push_back(MdLane{cs[j], nullptr});
+    return l;
+}
 
 }  // namespace mdmc

@@ -8,7 +8,9 @@
 // context's arguments.  Mode 1 steps all members with one force and one velocity-Verlet launch per step on
 // the ensemble's stream ("batched MD stretches" below), again the single-job kernels' bodies on each member's
 // own argument block.  For the QT tagging programs mode 1 batches the QT substeps, the tagging and the tagged
-// ions' moments and X distribution the same way ("batched QT" below).  The argument blocks travel through pinned
+// ions' moments and X distribution the same way ("batched QT" below).  The stages themselves are mdmc_run.cpp's,
+// written once on mdmc_ctx.hpp's MdLane: J member lanes in mode 0, one ensemble lane in mode 1, and the
+// stepping calls here take the same lanes.  The argument blocks travel through pinned
 // rings and the launches are timed by event pairs: mdqt_batch.hpp's PinRing and LaunchTimer, shared with the MDQT
 // ensembles.
 #include <algorithm>
@@ -226,11 +228,13 @@ int mdmc::ensemble_md_temperatures(mdmc_ensemble* e, int k) {
     return 0;
 }
 
-int mdmc::ensemble_md_tag_moments(mdmc_ensemble* e, int k) {
-    if (need_open(e, "ensemble_md_tag_moments")) return -1;
-    if (k < 0 || k >= e->obsCap) return set_error("ensemble_md_tag_moments: step %d outside the %d buffered", k, e->obsCap);
+// the MC + MD program's four tag sets or, qt, the QT tagging programs' one: the same launch, charged to its own counter
+int mdmc::ensemble_tag_moments(mdmc_ensemble* e, int k, bool qt) {
+    const char* what = qt ? "ensemble_qt_tag_moments" : "ensemble_md_tag_moments";
+    if (need_open(e, what)) return -1;
+    if (k < 0 || k >= e->obsCap) return set_error("%s: step %d outside the %d buffered", what, k, e->obsCap);
     HIPCHK(launch_tag_moments_ens(e->dObs, (int)e->jobs.size(), k, e->stream));
-    ++e->mdLaunches;
+    ++(qt ? e->qtLaunches : e->mdLaunches);
     return 0;
 }
 
@@ -267,7 +271,7 @@ int mdmc::ensemble_md_pair_corr_queue(mdmc_ensemble* e) {
 // distribution blocks are resident with the stretch's.  The distribution's rows land in a slot of the
 // ensemble's [kDistSlots][J][TKDE_BINS] device ring and one copy a slot brings all members' rows to the pinned
 // ring; evDist[slot] behind the copy is all the host ever waits for.
-// These are queued between ensemble_md_begin and ensemble_md_end (run()), or by the entry points below between
+// These are queued between ensemble_md_begin and ensemble_md_end (mdmc_run.cpp's stages), or by the entry points below between
 // fence_in and a synchronisation of the ensemble's stream.
 // ------------------------------------------------------------------------------------------------------------
 int mdmc::ensemble_qt_steps(mdmc_ensemble* e, int n) {
@@ -317,14 +321,6 @@ int mdmc::ensemble_qt_tag(mdmc_ensemble* e) {                      // tagParticl
     return 0;
 }
 
-int mdmc::ensemble_qt_tag_moments(mdmc_ensemble* e, int k) {
-    if (need_open(e, "ensemble_qt_tag_moments")) return -1;
-    if (k < 0 || k >= e->obsCap) return set_error("ensemble_qt_tag_moments: step %d outside the %d buffered", k, e->obsCap);
-    HIPCHK(launch_tag_moments_ens(e->dObs, (int)e->jobs.size(), k, e->stream));
-    ++e->qtLaunches;
-    return 0;
-}
-
 int mdmc::ensemble_qt_dist_x(mdmc_ensemble* e, int slot) {
     if (slot < 0 || slot >= mdmc_ensemble::kDistSlots) return set_error("ensemble_qt_dist_x: slot %d outside the ring", slot);
     const size_t J = e->jobs.size(), row = J * TKDE_BINS;
@@ -356,14 +352,14 @@ const double* mdmc::ensemble_qt_dist_rows(mdmc_ensemble* e, int slot) {
 extern "C" int mdmc_ensemble_qsteps(mdmc_ensemble* e, int n) {
     if (need_qt(e, "mdmc_ensemble_qsteps")) return -1;
     HIPCHK(hipSetDevice(e->dev));
-    if (e->mdBatch == 1) {
-        if (fence_in(e) || mdmc::ensemble_qt_steps(e, n)) return -1;
-        HIPCHK(hipStreamSynchronize(e->stream));
-        return 0;
-    }
-    for (mdmc_ctx* c : e->jobs)
-        if (mdmc::qsteps_async(c, n)) return -1;
-    return sync_members(e);
+    const std::vector<mdmc::MdLane> lanes = mdmc::md_lanes(e->jobs.data(), (int)e->jobs.size(), e);
+    // no stretch: an ensemble lane's launches go between the fence and a wait for the ensemble's stream
+    if (lanes[0].e && fence_in(e)) return -1;
+    for (const mdmc::MdLane& l : lanes)
+        if (l.qt_steps(n)) return -1;
+    if (!lanes[0].e) return sync_members(e);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
 }
 
 // mdmc_tag_qt of every member: tags [J][N] or NULL, n_up [J] or NULL
@@ -581,21 +577,20 @@ extern "C" int mdmc_ensemble_monte_carlo(mdmc_ensemble* e, int nsteps, long long
     return mdmc::ensemble_anneal(e, nsteps, accepted);
 }
 
-// MDStep() x n of every member (:504-511): md_batch 0, each step queued member by member on the members' own
-// streams; md_batch 1, one batched stretch on the ensemble's stream
+// MDStep() x n of every member (:504-511) on the run's lanes: md_batch 0, each step queued member by member on
+// the members' own streams; md_batch 1, one batched stretch on the ensemble's stream (none for nsteps <= 0)
 extern "C" int mdmc_ensemble_md_steps(mdmc_ensemble* e, int nsteps) {
     if (!e) return set_error("NULL ensemble");
     HIPCHK(hipSetDevice(e->dev));
-    if (e->mdBatch == 1 && nsteps > 0) {
-        bool ok = !mdmc::ensemble_md_begin(e);
-        for (int k = 0; ok && k < nsteps; ++k) ok = !mdmc::ensemble_md_step(e);
-        ok = ok && !mdmc::ensemble_md_end(e);
+    if (nsteps > 0) {
+        const std::vector<mdmc::MdLane> lanes = mdmc::md_lanes(e->jobs.data(), (int)e->jobs.size(), e);
+        bool ok = true;
+        for (const mdmc::MdLane& l : lanes) ok = ok && !l.begin();
+        for (int k = 0; ok && k < nsteps; ++k)
+            for (const mdmc::MdLane& l : lanes) ok = ok && !l.md_step();
+        for (const mdmc::MdLane& l : lanes) ok = ok && !l.end();
         e->open = false;                       // a failed stretch is abandoned
         if (!ok) return -1;
-    } else {
-        for (int k = 0; k < nsteps; ++k)
-            for (mdmc_ctx* c : e->jobs)
-                if (mdmc::md_step_async(c)) return -1;
     }
     if (sync_members(e)) return -1;
     for (mdmc_ctx* c : e->jobs) c->hitOff = 0;
