@@ -423,9 +423,32 @@ int         mdqt_ensemble_run(mdqt_ensemble* e);               /* main()'s time 
                                                                   job: directories, init() or readConditions,
                                                                   output() per job, writeConditions per job */
 int         mdqt_ensemble_synchronize(mdqt_ensemble* e);       /* + the range flags of all jobs */
+/* output() (SpeedUp:917-1032) and Epotential() (:244-281) of every job in one device pass: the members on the
+ * Newton-3 tiles (what mdqt_observables takes at world 1: potential_n3 1, N >= 128 or force_scheme 2) share
+ * six launches — the pair potentials, their slot sum per ion, <vx> and the energy sums, the velocity
+ * distributions' KDE and its reduction, the per-ion columns — two device-to-host copies and one
+ * synchronisation, where each job's own mdqt_output is seven launches, two copies and a synchronisation.
+ * Every number and file is bit for bit / byte for byte that job's own mdqt_observables / mdqt_epotential /
+ * mdqt_output (the same kernels' bodies on the same arguments; the potential writes slots of its own, so
+ * pending force slots stay pending).  Any other member takes its own call inside.  Ensemble option
+ * "output_batch" (mdqt_ensemble_set_option; 1 = batched; 0 = member by member, the default: the measured
+ * end-to-end gain at 8 and 64 jobs did not come with a clean result at one job, docs/PROGRAMS.md) selects the
+ * path for these calls and for mdqt_ensemble_run's outputs.
+ * mdqt_ensemble_output returns when the files are on disk, as mdqt_output does.
+ * mdqt_ensemble_observables: out7 [J][7] (mdqt_observables' t, EkinX, EkinY, EkinZ, Epot, dE, <vx>), Pvel
+ * [J][3 * 2001] or NULL, pops = the jobs' [N_k][3] S / P / D populations one after the other (3 sum N_k
+ * doubles) or NULL.  mdqt_ensemble_epotential: Epot [J]; the potential, slot-sum and sums launches only. */
+int         mdqt_ensemble_output(mdqt_ensemble* e);
+int         mdqt_ensemble_observables(mdqt_ensemble* e, double* out7, double* Pvel, double* pops);
+int         mdqt_ensemble_epotential(mdqt_ensemble* e, double* Epot);
+/* kernel launches the batched output path has issued since creation (6 per output with every per-ion column,
+ * 5 without the populations, 3 per mdqt_ensemble_epotential; a member's own fallback calls are not counted) */
+unsigned long long mdqt_ensemble_output_launches(const mdqt_ensemble* e);
 /* the two batched kernels' own durations from their dispatch timestamps (on > 0: every launch):
  * out[6] = force ms (sum), force launches, QT ms (sum), QT launches, median force launch ms, median
- * QT launch ms — since the last call; synchronises and resets.  Replaces no reference function */
+ * QT launch ms — since the last call; synchronises and resets.  With n >= 12 also the batched output's
+ * potential and KDE launches: out[6..11] = potential ms (sum), launches, KDE ms (sum), launches, and the two
+ * medians.  Replaces no reference function */
 int         mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on);
 int         mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n);
 
@@ -449,7 +472,9 @@ int         mdqt_pump_ensemble_create(const mdqt_params* p, int njobs, mdqt_pump
 void        mdqt_pump_ensemble_destroy(mdqt_pump_ensemble* e);
 int         mdqt_pump_ensemble_size(const mdqt_pump_ensemble* e);
 mdqt_ctx*   mdqt_pump_ensemble_job(mdqt_pump_ensemble* e, int k);       /* job k's context, owned by the ensemble */
-int         mdqt_pump_ensemble_set_option(mdqt_pump_ensemble* e, const char* name, int value);   /* on every member */
+/* on every member; "output_batch" 1: output()'s Epotential() of all members by the three batched potential
+ * launches of mdqt_ensemble_epotential under output()'s one synchronisation (default 0: each member's call) */
+int         mdqt_pump_ensemble_set_option(mdqt_pump_ensemble* e, const char* name, int value);
 int         mdqt_pump_ensemble_init(mdqt_pump_ensemble* e);             /* init() of every job; untagged          */
 int         mdqt_pump_ensemble_md_steps(mdqt_pump_ensemble* e, int n);  /* n x (step(); c0++) of every job        */
 int         mdqt_pump_ensemble_qsteps(mdqt_pump_ensemble* e, int n);    /* n x qstep() of every job (QT only)     */

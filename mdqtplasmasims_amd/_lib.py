@@ -221,6 +221,10 @@ SIGNATURES = [
     ("mdqt_ensemble_synchronize", C.c_int, [C.c_void_p]),
     ("mdqt_ensemble_enable_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("mdqt_ensemble_kernel_times", C.c_int, [C.c_void_p, _dp, C.c_int]),
+    ("mdqt_ensemble_output", C.c_int, [C.c_void_p]),
+    ("mdqt_ensemble_observables", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    ("mdqt_ensemble_epotential", C.c_int, [C.c_void_p, _dp]),
+    ("mdqt_ensemble_output_launches", C.c_ulonglong, [C.c_void_p]),
     # ensembles of the optical-pumping programs, and the single context's stepwise MD step
     ("mdqt_pump_md_steps", C.c_int, [C.c_void_p, C.c_int]),
     ("mdqt_pump_ensemble_create", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.POINTER(C.c_void_p)]),

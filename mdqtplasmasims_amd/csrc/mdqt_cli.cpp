@@ -14,6 +14,8 @@
 //   --njobs=J runs the jobs <job> .. <job>+J-1 of the reference's Slurm array (exampleSlurmFile.slurm:3)
 //   as one ensemble (mdqt_ensemble_run: one force and one QT launch per MD step for all of them), job k
 //   seeded seed + k; each job's files are those of `mdqt <job>+k --seed=<seed>+k`; prints every N.
+//   --output_batch=0|1 (with --njobs): output() of all jobs in one device pass (1) or job after job (0, the
+//   default); the same files either way.
 //
 //   --pump_program=m --pump_jobs=J does the same for the pumping programs (mdqt_pump_ensemble_run): the jobs
 //   <job> .. <job>+J-1 stepped in batched launches, each job's tree byte for byte that of
@@ -36,6 +38,7 @@ static void usage(void) {
             "       mdqt <job> --pump_program=1|2|3 [--tpumpreal=2e-7] [--tstartV0=15] [... as above]\n"
             "       mdqt <job> --njobs=J [... as above]   jobs <job> .. <job>+J-1 as one ensemble (J >= 1;\n"
             "                  seeds seed .. seed+J-1; not with --pump_program: --pump_jobs)\n"
+            "                  [--output_batch=0|1]   output() of all jobs in one device pass (1) or job after job (0)\n"
             "       mdqt <job> --pump_program=1|2|3 --pump_jobs=J [...]   the pump jobs <job> .. <job>+J-1 as one\n"
             "                  ensemble (1 <= J <= 1024; seeds seed .. seed+J-1; not with --njobs)\n");
 }
@@ -54,6 +57,7 @@ int main(int argc, char** argv) {
     int seed_given = 0;
     long njobs = -1;                                        // --njobs: the jobs of an ensemble (-1: not given)
     long pump_jobs = -1;                                    // --pump_jobs: the jobs of a pump ensemble
+    long output_batch = -1;                                 // --output_batch: the ensemble's option (-1: its default)
     for (int i = 2; i < argc; ++i) {
         const char* a = argv[i];
         if (strncmp(a, "--", 2) != 0 || !strchr(a, '=')) { usage(); return 2; }
@@ -79,6 +83,12 @@ int main(int argc, char** argv) {
             if (end == v || *end || njobs < 1 || njobs > 1024) { usage(); return 2; }
             continue;
         }
+        if (!strcmp(key, "output_batch")) {
+            char* end = NULL;
+            output_batch = strtol(v, &end, 10);
+            if (end == v || *end || output_batch < 0 || output_batch > 1) { usage(); return 2; }
+            continue;
+        }
         if (!strcmp(key, "pump_jobs")) {
             char* end = NULL;
             pump_jobs = strtol(v, &end, 10);
@@ -95,11 +105,17 @@ int main(int argc, char** argv) {
     }
     if (njobs > 0 && pump) { usage(); return 2; }
     if (pump_jobs > 0 && (!pump || njobs > 0)) { usage(); return 2; }
+    if (output_batch >= 0 && njobs < 1) { usage(); return 2; }
     if (!seed_given) p.seed = (uint32_t)(time(NULL) + job);   // SpeedUp:1219
     if (njobs > 0) {
         mdqt_ensemble* e = NULL;
         if (mdqt_ensemble_create(&p, (int)njobs, &e)) {
             fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
+            return 1;
+        }
+        if (output_batch >= 0 && mdqt_ensemble_set_option(e, "output_batch", (int)output_batch)) {
+            fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
+            mdqt_ensemble_destroy(e);
             return 1;
         }
         const int rc = mdqt_ensemble_run(e);

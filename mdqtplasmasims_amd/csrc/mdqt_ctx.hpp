@@ -241,6 +241,20 @@ struct mdqt_ensemble {
     bool timing = false;
     mdqt::LaunchTimer timers[2];                   // 0 = force launches, 1 = QT launches
     unsigned long long force_launches = 0;         // force launches issued by ens_forces (batched + the row members' own)
+    // the batched output() (mdqt_ensemble_output.cpp): the members' blocks, their results on the device (rows
+    // [J][kObsRow] in dScr's layout, the packed columns [sum 4 N_k]) and the pinned slot they come back to
+    int output_batch = 0;                          // option "output_batch": 1 = one pass for all members, 0 = member by member
+                                                   // (the default: docs/PROGRAMS.md "Batched output()" has the measurement)
+    mdqt::N3Args* dPot = nullptr;                  // [J] the potential launch's blocks (batched members, packed)
+    mdqt::EnsObsArgs* dObs = nullptr;              // [J] the observables' blocks (the same members)
+    std::vector<mdqt::N3Args> pot_held;            // what they hold
+    std::vector<mdqt::EnsObsArgs> obs_held;
+    double* dObsRows = nullptr;                    // [J][kObsRow]
+    double* dObsCols = nullptr;                    // [obs_cols_cap]
+    size_t obs_cols_cap = 0;
+    mdqt::PinRing obs_ring;                        // one slot: the rows, then the columns
+    unsigned long long output_launches = 0;        // kernel launches of the batched output path
+    mdqt::LaunchTimer obs_timers[2];               // 0 = the batched potential launches, 1 = the batched KDE launches
 };
 
 // J independent jobs of an optical-pumping program stepped in batched launches (mdqt_pump_ensemble.cpp): an
@@ -312,12 +326,18 @@ int md_step_fused(mdqt_ctx* s);
 // mdqt_observables.cpp
 bool observables_w1_applies(const mdqt_ctx* s);
 int observables_w1(mdqt_ctx* s, double out7[7], double* Pvel, double* pops, double* vx);
+bool potential_on_tiles(const mdqt_ctx* s);
+int potential_n3_block(mdqt_ctx* s, N3Args& a);
+void observables_from_rows(mdqt_ctx* s, const double* h, const double* col, double out7[7], double* Pvel, double* pops,
+                           double* vx);
 
 // mdqt_io.cpp
 FILE* open_in(const mdqt_ctx* s, const char* name, const char* mode);
 int finish_directories(mdqt_ctx* s, const char* name);
 int flush_files(mdqt_ctx* s);
 int output_async(mdqt_ctx* s);
+int output_files(mdqt_ctx* s, const double* o, std::shared_ptr<std::vector<double>> P,
+                 std::shared_ptr<std::vector<double>> pops, std::shared_ptr<std::vector<double>> V);
 int write_conditions_async(mdqt_ctx* s, int c0);
 int read_ions_conditions(mdqt_ctx* s, int c0, std::vector<double>& R, std::vector<double>& V);
 int fusable_substeps(const mdqt_ctx* s, double tend, long c0, int ts);
@@ -328,7 +348,7 @@ int pump_md_step(mdqt_ctx* s);
 int pump_spin_ups_file(mdqt_ctx* s);
 int pump_output_buffers(mdqt_ctx* s);
 int pump_output_host(mdqt_ctx* s, const std::vector<double>& V, std::vector<double>& P,
-                     const std::function<int()>& tagged, FileWriter* pool);
+                     const std::function<int()>& tagged, FileWriter* pool, const double* epot = nullptr);
 int pump_vaf_host(mdqt_ctx* s, const std::vector<double>& V, int c1V);
 int pump_write_conditions(mdqt_ctx* s, int c0);
 int pump_read_conditions(mdqt_ctx* s, int c0);
@@ -342,6 +362,15 @@ int ens_forces(mdqt_ensemble* e);
 using EnsQtLaunch = std::function<hipError_t(const SubstepArgs& first, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst)>;
 int ens_qt_chunks(mdqt_ensemble* e, int n, int do_step, const EnsQtLaunch& launch);
 int ens_range_flags(mdqt_ensemble* e, bool drain = true);
+
+// mdqt_ensemble_output.cpp: output() of every member in one device pass
+int ens_output(mdqt_ensemble* e);
+int ens_epotential(mdqt_ensemble* e, double* Epot);
+// the same queued without a synchronisation (the pump ensemble's output, which has one of its own): after it,
+// batched member member[q]'s Epotential() is ens_epot_of(job, rows + 64 q)
+int ens_epotential_queue(mdqt_ensemble* e, std::vector<int>& member, const double** rows);
+double ens_epot_of(const mdqt_ctx* s, const double* row);
+void ens_output_destroy(mdqt_ensemble* e);
 
 // mdqt_options.cpp (timing events)
 int mark(mdqt_ctx* s, int k);

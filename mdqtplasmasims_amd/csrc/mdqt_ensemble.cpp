@@ -260,6 +260,7 @@ extern "C" void mdqt_ensemble_destroy(mdqt_ensemble* e) {
     }
     if (e->dForce) (void)hipFree(e->dForce);
     if (e->dSub) (void)hipFree(e->dSub);
+    ens_output_destroy(e);
     e->ring.destroy();
     for (LaunchTimer& t : e->timers) t.destroy();
     delete e;
@@ -329,6 +330,11 @@ extern "C" int mdqt_ensemble_set_option(mdqt_ensemble* e, const char* name, int 
         e->qt_waves = value;
         return 0;
     }
+    if (!strcmp(name, "output_batch")) {
+        if (value != 0 && value != 1) return set_error("output_batch must be 0 (output() member by member) or 1 (one batched pass)");
+        e->output_batch = value;
+        return 0;
+    }
     for (mdqt_ctx* s : e->jobs)
         if (mdqt_set_option(s, name, value)) return -1;
     return 0;
@@ -388,8 +394,7 @@ extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
     int tsc = ratio;                                                                    // :1235
     while (a->t <= tend) {                                                              // :1248
         if ((a->c0 + 1) % sf == 0 && tsc == 1)                                          // :1365
-            for (mdqt_ctx* s : e->jobs)
-                if (output_async(s)) return -1;         // each member's own device pass and synchronisation
+            if (ens_output(e)) return -1;               // one device pass and synchronisation (option output_batch)
         if (tsc == ratio) {                                                             // :1369
             if (ens_range_flags(e, false)) return -1;
             if (ens_forces(e)) return -1;
@@ -410,11 +415,14 @@ extern "C" int mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on) {
     if (!e) return set_error("NULL ensemble");
     e->timing = on > 0;
     for (LaunchTimer& t : e->timers) t.reset();
+    for (LaunchTimer& t : e->obs_timers) t.reset();
     return 0;
 }
 
 // the two batched kernels' own durations (their dispatch timestamps) since the last call: out[6] = force
-// ms (sum), force launches, QT ms (sum), QT launches, median force launch (ms), median QT launch (ms); resets
+// ms (sum), force launches, QT ms (sum), QT launches, median force launch (ms), median QT launch (ms); with
+// n >= 12 also the batched output's potential and KDE launches: out[6..11] = potential ms (sum), launches, KDE
+// ms (sum), launches, median potential launch (ms), median KDE launch (ms); resets
 extern "C" int mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n) {
     if (!e || !out) return set_error("mdqt_ensemble_kernel_times: NULL argument");
     if (n < 6) return set_error("mdqt_ensemble_kernel_times: need 6 doubles");
@@ -426,6 +434,14 @@ extern "C" int mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n) 
         out[2 * k] = v[0];
         out[2 * k + 1] = v[1];
         out[4 + k] = v[2];
+    }
+    for (int k = 0; k < 2; ++k) {
+        double v[5];
+        if (e->obs_timers[k].stats(v)) return -1;
+        if (n < 12) continue;
+        out[6 + 2 * k] = v[0];
+        out[7 + 2 * k] = v[1];
+        out[10 + k] = v[2];
     }
     return 0;
 }

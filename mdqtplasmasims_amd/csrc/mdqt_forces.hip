@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void k_reduce_segments(const double* __restric
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int c = blockIdx.y;
     if (i >= nrows || c >= ncomp) return;
-    F[(size_t)c * S + i] = slot_sum16(Fpart + (size_t)c * S + i, plane, nseg);
+    reduce_segments_row(Fpart, F, nseg, S, plane, i, c);
 }
 
 #if defined(MDQT_EXPT_STAMPS)
@@ -142,11 +142,7 @@ __global__ __launch_bounds__(64 * N3W) void k_pairs_n3_pot(N3Args a) {
     __shared__ double accj[N3W][3][128];
     __shared__ double ia[N3W][3][64];
     __shared__ double mj[128];
-    const int2 IJ = a.pairs[blockIdx.x];
-    const PairC c = {a.L, a.micT, a.micGuard, a.Rcut, a.lDeb, a.invlDeb, 1. / a.L, a.rc2};
-    const bool rag = (a.N & 63) && IJ.y == a.ntiles - 1;
-    if (rag) n3_tile<VARIANT, GUARD, true, false, true>(a, c, IJ.x, IJ.y, pj, accj, mj, ia);
-    else n3_tile<VARIANT, GUARD, false, false, true>(a, c, IJ.x, IJ.y, pj, accj, mj, ia);
+    n3_pot_pair<VARIANT, GUARD>(a, blockIdx.x, pj, accj, mj, ia);   // mdqt_pairs.hpp
 }
 
 #if defined(MDQT_EXPT_STAMPS)

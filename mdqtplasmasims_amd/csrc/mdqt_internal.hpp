@@ -749,6 +749,34 @@ hipError_t launch_pump_kick_ens(const PumpStepArgs* jobs, int njobs, int max_n, 
                                 hipEvent_t ev1 = nullptr);
 hipError_t launch_tag_spin_up_ens(const PumpTagArgs* jobs, int njobs, int max_n, hipStream_t s);
 hipError_t launch_tagged_kde_ens(const PumpKdeArgs* jobs, int njobs, int max_N, hipStream_t s);
+// output() / Epotential() of an ensemble of SpeedUp jobs in batched launches (mdqt_ensemble_obs.hip; host:
+// mdqt_ensemble_output.cpp): `jobs` = device array of the members' argument blocks, grid (largest member's
+// workgroups, njobs); every kernel runs its single-job kernel's body (mdqt_pairs.hpp n3_pot_pair and
+// reduce_segments_row, mdqt_obs_device.hpp).
+constexpr int kObsRow = 64 + 3 * NBINS;   // a member's scratch row, dScr's layout: [0] sum vx, [8] <vx>,
+                                          // [16..19] the energy sums, [64..] the KDE bins
+struct EnsObsArgs {     // one member's observables
+    const double* V;    // [3][S]
+    const double* psi;  // [24][S]
+    const double* Upart;// [nslots][S] the potential launch's slots (component 0)
+    double* Urow;       // [S] their canonical sum per ion
+    double* kde;        // [nch][3][NBINS] the KDE partials
+    double* scr;        // [kObsRow] the member's row of the ensemble's scratch
+    double* pack;       // [4][N] the member's part of the ensemble's column buffer
+    int N, S, nslots;
+    int nch, chunk;     // KDE chunks clamp(N / 32, 1, kdeChunks) and their length ceil(N / nch)
+    int model;          // qt_model (k_output_pack's populations)
+};
+// k_pairs_n3_pot of every member: max_npairs = the largest a.npairs, guard = any member's
+hipError_t launch_potential_n3_ens(const N3Args* jobs, int njobs, int max_npairs, int variant, bool guard, hipStream_t s,
+                                   hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// k_reduce_segments (one component, plane S) into Urow, then k_sum_vx + k_energy_sums in one workgroup per
+// member: scr[0] = sum vx, scr[8] = <vx>, scr[16..19] the sums
+hipError_t launch_potential_sums_ens(const EnsObsArgs* jobs, int njobs, int max_N, hipStream_t s);
+// k_kde and k_kde_reduce of every member into scr[64..] (max_nch = the largest nch; reads scr[8])
+hipError_t launch_kde_ens(const EnsObsArgs* jobs, int njobs, int max_nch, hipStream_t s, hipEvent_t ev0 = nullptr,
+                          hipEvent_t ev1 = nullptr);
+hipError_t launch_output_pack_ens(const EnsObsArgs* jobs, int njobs, int max_N, hipStream_t s);
 
 // measureSpinUps (randomFrozenStartTag408Linear.cpp:600, :422Linear) / tagParticles
 // (MonteCarloFollowedByQTTagging408Linear.cpp:1022): tag[i] = 1 with probability of spin up

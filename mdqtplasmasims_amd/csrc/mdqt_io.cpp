@@ -81,6 +81,15 @@ int mdqt::output_async(mdqt_ctx* s) {
         if (mdqt_get_state(s, nullptr, V->data(), nullptr, N, nullptr, nullptr, nullptr)) return -1;
         if (mdqt_allreduce_sum(s, V->data(), (size_t)N)) return -1;  // vx column, zero-padded gather
     }
+    return output_files(s, o, P, pops, V);
+}
+
+// output() after its observables: energies.dat's line in place, the velocity distributions and the state
+// populations from the snapshots by the background writers, counter++ (o[7], P [3][NBINS], pops [N][3], V:
+// vx in [0, N))
+int mdqt::output_files(mdqt_ctx* s, const double* o, std::shared_ptr<std::vector<double>> P,
+                       std::shared_ptr<std::vector<double>> pops, std::shared_ptr<std::vector<double>> V) {
+    const int N = s->N;
     if (s->p.rank != 0) { s->counter++; return 0; }                 // files are rank 0's
     FILE* fa = open_in(s, "energies.dat", "a");                      // appended in order: here
     if (!fa) return -1;

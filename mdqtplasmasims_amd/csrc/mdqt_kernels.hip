@@ -10,6 +10,7 @@
 // device/host differences left are libm ulps (exp, sin, cos).  See DESIGN.md §Parity.
 #include "mdqt_device.hpp"
 #include "mdqt_pump_device.hpp"   // the body k_leapfrog_half shares with the pump ensemble's batched kernels
+#include "mdqt_obs_device.hpp"    // the observables' bodies, shared with the SpeedUp ensemble's batched output
 
 #include <math.h>
 
@@ -586,55 +587,24 @@ hipError_t launch_substeps(const SubstepArgs& a, const LaneTab* tab, int mode, i
 }
 
 // ------------------------------------------------------------------------------------------
-// Observables (output(), SpeedUp:917-1032).  Deterministic fixed-shape reductions.
+// Observables (output(), SpeedUp:917-1032).  Deterministic fixed-shape reductions; the bodies are
+// mdqt_obs_device.hpp's, shared with the ensemble's batched kernels (mdqt_ensemble_obs.hip).
 // ------------------------------------------------------------------------------------------
-constexpr int RT = 1024;
-
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int w = RT / 2; w > 0; w >>= 1) {
-        if (t < w) sh[t] = sh[t] + sh[t + w];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(RT) void k_sum_vx(const double* __restrict__ V, int n, double* out, double* avg,
                                                 int N) {
     __shared__ double sh[RT];
-    double acc = 0.;
-    for (int i = threadIdx.x; i < n; i += RT) acc += V[i];
-    const double r = block_sum(acc, sh);
+    const double r = sum_vx_body(V, n, sh);
     if (threadIdx.x == 0) {
         out[0] = r;
         if (avg) avg[0] = N > 0 ? r / (double)N : 0.;   // velXAvg (:938) on the device (world 1)
     }
 }
 
-// output()'s per-ion columns in one array [4][n]: vx and the S / P / D populations of
-// statePopulationsVsVTime (:1010-1024), the host loop's operations and order (pumping model 3:
-// P = 2, 3; D = 4)
 __global__ __launch_bounds__(256) void k_output_pack(const double* __restrict__ V, const double* __restrict__ psi,
                                                      int n, int S, int model, double* __restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    auto nrm = [&](int k) {
-        const double re = psi[(size_t)(2 * k) * S + i], im = psi[(size_t)(2 * k + 1) * S + i];
-        return re * re + im * im;
-    };
-    out[i] = V[i];
-    out[(size_t)n + i] = nrm(0) + nrm(1);
-    if (model == 3) {
-        out[2 * (size_t)n + i] = nrm(2) + nrm(3);
-        out[3 * (size_t)n + i] = nrm(4);
-    } else {
-        out[2 * (size_t)n + i] = nrm(2) + nrm(3) + nrm(4) + nrm(5);
-        out[3 * (size_t)n + i] = nrm(6) + nrm(7) + nrm(8) + nrm(9) + nrm(10) + nrm(11);
-    }
+    output_pack_ion(V, psi, i, n, S, model, out);
 }
 
 hipError_t launch_output_pack(const double* V, const double* psi, int n, int S, int model, double* out,
@@ -648,20 +618,7 @@ __global__ __launch_bounds__(RT) void k_energy_sums(const double* __restrict__ V
                                                     const double* __restrict__ vxAvg,
                                                     const double* __restrict__ urow, double* out) {
     __shared__ double sh[RT];
-    const double avg = vxAvg[0];
-    double ex = 0., ey = 0., ez = 0., u = 0.;
-    for (int i = threadIdx.x; i < n; i += RT) {
-        const double vx = V[i], vy = V[S + i], vz = V[2 * S + i];
-        ex += 0.5 * ((vx - avg) * (vx - avg));                  // :939-944
-        ey += 0.5 * (vy * vy);
-        ez += 0.5 * (vz * vz);
-        if (urow) u += urow[i];
-    }
-    const double rx = block_sum(ex, sh);
-    const double ry = block_sum(ey, sh);
-    const double rz = block_sum(ez, sh);
-    const double ru = block_sum(u, sh);
-    if (threadIdx.x == 0) { out[0] = rx; out[1] = ry; out[2] = rz; out[3] = ru; }
+    energy_sums_body(V, n, S, vxAvg[0], urow, out, sh);
 }
 
 hipError_t launch_sum_vx(const double* V, int n, double* out, hipStream_t s, double* avg, int N) {
@@ -675,50 +632,19 @@ hipError_t launch_energy_sums(const double* V, int n, int S, const double* vxAvg
     return hipGetLastError();
 }
 
-// Gaussian KDE of the velocity distributions (:957-979): bin j of axis c sums, over the
-// ions of chunk z in ascending order, exp(-V2 (b_j - v)^2) + exp(-V2 (b_j + v)^2).
-constexpr int KT = 256;
 __global__ __launch_bounds__(KT) void k_kde(const double* __restrict__ V, int n, int S,
                                             const double* __restrict__ vxAvg, double* Ppart,
                                             int chunk) {
     __shared__ double sv[KT];
-    const int j = blockIdx.x * KT + threadIdx.x;
     const int c = blockIdx.y;
-    const int z = blockIdx.z;
-    const double V2 = kKdeV2;                                    // 1 / (2 * 0.002^2), :967
-    const double b = (double)j * 0.0025;                         // vel[j], :340-344
-    const double avg = (c == 0) ? vxAvg[0] : 0.;
-    const int i0 = z * chunk, i1 = min(n, i0 + chunk);
-    double acc = 0.;
-    for (int it = i0; it < i1; it += KT) {
-        __syncthreads();
-        if (it + (int)threadIdx.x < i1) {
-            const double v = V[(size_t)c * S + it + threadIdx.x];
-            sv[threadIdx.x] = (c == 0) ? (v - avg) : v;
-        }
-        __syncthreads();
-        const int m = min(KT, i1 - it);
-        for (int k = 0; k < m; ++k) {
-            const double v = sv[k];
-            // exp(x) is exactly +0 for x < -745.14, i.e. for |b -+ v| >= 0.0773 (V2 d^2 >= 746.9):
-            // an ion whose two terms are 0 on every bin of the wave adds exact zeros there and is
-            // skipped (a wave spans 0.16 of the 5.0 bin range, an ion's terms 2 x 0.155): the same
-            // sums, ~15x fewer exp.  NaN velocities still take the exp path.
-            const bool near = !(fabs(b - v) >= kKdeSkip) || !(fabs(b + v) >= kKdeSkip);
-            if (!__builtin_amdgcn_ballot_w64(near)) continue;
-            acc += exp(-V2 * (b - v) * (b - v)) + exp(-V2 * (b + v) * (b + v));
-        }
-    }
-    if (j < NBINS) Ppart[((size_t)z * 3 + c) * NBINS + j] = acc;
+    kde_chunk(V, n, S, (c == 0) ? vxAvg[0] : 0., Ppart, chunk, blockIdx.x, c, blockIdx.z, sv);
 }
 
 __global__ __launch_bounds__(256) void k_kde_reduce(const double* __restrict__ Ppart, int nchunk,
                                                     double* __restrict__ Pout) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= 3 * NBINS) return;
-    double acc = Ppart[j];
-    for (int z = 1; z < nchunk; ++z) acc += Ppart[(size_t)z * 3 * NBINS + j];
-    Pout[j] = acc;
+    kde_reduce_bin(Ppart, nchunk, Pout, j);
 }
 
 hipError_t launch_kde(const double* V, int n, int S, const double* vxAvg, double* Ppart,

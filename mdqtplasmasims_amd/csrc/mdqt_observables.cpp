@@ -19,6 +19,23 @@ static int grow_upart(mdqt_ctx* s, size_t need) {
     return 0;
 }
 
+// does potential_rows take the Newton-3 tile kernel's POT mode for this context?
+bool mdqt::potential_on_tiles(const mdqt_ctx* s) {
+    return s->use_n3 && !s->use_n3b && s->p.world_size == 1 && s->local.empty() && s->force_variant <= 1 &&
+           s->n3_potential;
+}
+
+// the potential launch's block on the tiles: the force call's block with the plain table, into the
+// potential's own slots (one plane per slot: component 0) — pending force slots stay pending and untouched
+int mdqt::potential_n3_block(mdqt_ctx* s, N3Args& a) {
+    const size_t need = (size_t)s->nslots * s->S;
+    if (grow_upart(s, need)) return -1;
+    if (n3_force_args(s, a, true)) return -1;
+    a.P = s->dUpart;
+    a.arrive = nullptr;
+    return 0;
+}
+
 // device: scratch[0] = sum over owned rows of the full-row pair potential.  World 1, partials up
 // to 64 MB: the potential rows get a buffer of their own, so pending force slots stay pending
 // (the next substep launch sums them in its prologue: no reduce launch, and that launch stays the
@@ -28,14 +45,9 @@ static int potential_rows(mdqt_ctx* s, double* urow_dev) {
     // world 1 with the Newton-3 tile scheme: each distinct pair's potential once (the tile kernel's
     // POT mode), the ntiles slots of component 0 summed per ion (half the pair evaluations of the
     // rows; the same per-ion row sums up to summation order)
-    if (s->use_n3 && !s->use_n3b && s->p.world_size == 1 && s->local.empty() && s->force_variant <= 1 &&
-        s->n3_potential) {
-        const size_t need = (size_t)s->nslots * s->S;   // one plane per slot (component 0)
-        if (grow_upart(s, need)) return -1;
-        N3Args a;                                       // the force call's block with the plain table,
-        if (n3_force_args(s, a, true)) return -1;       // into the potential's own slots
-        a.P = s->dUpart;
-        a.arrive = nullptr;
+    if (potential_on_tiles(s)) {
+        N3Args a;
+        if (potential_n3_block(s, a)) return -1;
         HIPCHK(launch_potential_n3(a, s->force_variant, s->stream));
         HIPCHK(launch_reduce_segments(s->dUpart, urow_dev, s->nslots, s->nloc, s->S, 1, s->stream, (size_t)s->S));
         return 0;
@@ -167,16 +179,24 @@ int mdqt::observables_w1(mdqt_ctx* s, double out7[7], double* Pvel, double* pops
     HIPCHK(hipMemcpyAsync(h.data(), scr, h.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     if (pack) HIPCHK(hipMemcpyAsync(col.data(), s->dPack, col.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
+    observables_from_rows(s, h.data(), col.data(), out7, Pvel, pops, vx);
+    return 0;
+}
+
+// the host end of observables_w1 (and of the ensemble's batched pass, mdqt_ensemble_output.cpp): h = the
+// scratch row [kObsRow] as the device left it, col = the packed columns [4][N] (read only with pops or vx)
+void mdqt::observables_from_rows(mdqt_ctx* s, const double* h, const double* col, double out7[7], double* Pvel,
+                                 double* pops, double* vx) {
+    const int N = s->N;
     const double velXAvg = h[8];
-    finish_observables(s, h.data() + 16, velXAvg, h.data() + 64, out7, Pvel);
-    if (vx) memcpy(vx, col.data(), (size_t)N * sizeof(double));
+    finish_observables(s, h + 16, velXAvg, h + 64, out7, Pvel);
+    if (vx) memcpy(vx, col, (size_t)N * sizeof(double));
     if (pops)
         for (int i = 0; i < N; i++) {
             pops[3 * i + 0] = col[(size_t)N + i];
             pops[3 * i + 1] = col[2 * (size_t)N + i];
             pops[3 * i + 2] = col[3 * (size_t)N + i];
         }
-    return 0;
 }
 
 bool mdqt::observables_w1_applies(const mdqt_ctx* s) {

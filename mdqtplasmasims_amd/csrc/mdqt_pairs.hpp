@@ -492,4 +492,23 @@ __device__ __forceinline__ void n3_tile(const N3Args& a, const PairC& c, int I, 
     }
 }
 
+// Epotential() (:244-281) on the Newton-3 tiles, workgroup `wg` of a.npairs: each distinct pair's u once, to
+// both ions' rows (slot component 0; the caller sums the ntiles slots per ion).  The body of k_pairs_n3_pot
+// (mdqt_forces.hip) and of the ensemble's k_pairs_n3_pot_ens (mdqt_ensemble_obs.hip)
+template <int VARIANT, bool GUARD>
+__device__ __forceinline__ void n3_pot_pair(const N3Args& a, unsigned wg, double (*pj)[128], double (*accj)[3][128],
+                                            double* mj, double (*ia)[3][64]) {
+    const int2 IJ = a.pairs[wg];
+    const PairC c = {a.L, a.micT, a.micGuard, a.Rcut, a.lDeb, a.invlDeb, 1. / a.L, a.rc2};
+    const bool rag = (a.N & 63) && IJ.y == a.ntiles - 1;
+    if (rag) n3_tile<VARIANT, GUARD, true, false, true>(a, c, IJ.x, IJ.y, pj, accj, mj, ia);
+    else n3_tile<VARIANT, GUARD, false, false, true>(a, c, IJ.x, IJ.y, pj, accj, mj, ia);
+}
+
+// row i of component c of the partials' canonical sum (k_reduce_segments and the ensemble's k_reduce_segments_ens)
+__device__ __forceinline__ void reduce_segments_row(const double* __restrict__ Fpart, double* __restrict__ F, int nseg,
+                                                    int S, size_t plane, int i, int c) {
+    F[(size_t)c * S + i] = slot_sum16(Fpart + (size_t)c * S + i, plane, nseg);
+}
+
 }  // namespace mdqt

@@ -115,8 +115,9 @@ int mdqt::pump_output_buffers(mdqt_ctx* s) {
 // order.  V = the velocities [3][N], P = the tagged distribution [3][TKDE_BINS] (filled by `tagged`,
 // which runs after the energies as in output_pump, or beforehand by the caller: tagged == nullptr).
 // pool != nullptr: the 4001-line distribution file is formatted ("%lg", byte-identical) on that pool.
+// epot != nullptr: Epotential()'s value, computed by the caller (the pump ensemble's batched pass).
 int mdqt::pump_output_host(mdqt_ctx* s, const std::vector<double>& V, std::vector<double>& P,
-                           const std::function<int()>& tagged, FileWriter* pool) {
+                           const std::function<int()>& tagged, FileWriter* pool, const double* epot) {
     const int N = s->N;
     double EkinX = 0., EkinY = 0., EkinZ = 0.;
     for (int i = 0; i < N; i++) {                                // :812-817
@@ -126,7 +127,8 @@ int mdqt::pump_output_host(mdqt_ctx* s, const std::vector<double>& V, std::vecto
     }
     EkinX /= (double)N; EkinY /= (double)N; EkinZ /= (double)N;
     double e;
-    if (mdqt_epotential(s, &e)) return -1;                       // :821
+    if (epot) s->Epot = *epot;
+    else if (mdqt_epotential(s, &e)) return -1;                  // :821
     FILE* fa = open_in(s, "energies.dat", "a");                  // :825-829
     if (!fa) return -1;
     fprintf(fa, "%lg\t%lg\t%lg\t%lg\t%lg\t%lg\n", s->t, EkinX, EkinY, EkinZ, s->Epot,

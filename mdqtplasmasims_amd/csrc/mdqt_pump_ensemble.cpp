@@ -154,7 +154,8 @@ int pump_tag(mdqt_pump_ensemble* pe) {
 
 // output() :799-935 (and, vaf >= 0, Zfunc(vaf) + printVAF) of every member: the velocity read-backs and the
 // batched tagged distribution queued on the ensemble's stream, one synchronisation, then each member's host
-// sums and files by output_pump's own code (pump_output_host, pump_vaf_host; Epotential() each member's call)
+// sums and files by output_pump's own code (pump_output_host, pump_vaf_host; Epotential() each member's call, or with option output_batch 1 the base
+// ensemble's three batched launches under the same synchronisation)
 int pump_output(mdqt_pump_ensemble* pe, int vaf) {
     mdqt_ensemble* e = pe->base;
     const int J = (int)e->jobs.size();
@@ -181,13 +182,23 @@ int pump_output(mdqt_pump_ensemble* pe, int vaf) {
     pe->launches += 2;
     for (int k = 0; k < J; ++k)
         HIPCHK(hipMemcpyAsync(Ps[k].data(), e->jobs[k]->dTkde, Ps[k].size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    // option output_batch 1: Epotential() of the members on the tile potential in the ensemble's three batched
+    // launches (mdqt_ensemble_output.cpp), read back under the same synchronisation
+    std::vector<int> batched;
+    const double* rows = nullptr;
+    if (e->output_batch && ens_epotential_queue(e, batched, &rows)) return -1;
+    if (!batched.empty()) pe->launches += 3;
     HIPCHK(hipStreamSynchronize(e->stream));
+    size_t q = 0;
     for (int k = 0; k < J; ++k) {
         mdqt_ctx* s = e->jobs[k];
         const int N = s->N, S = s->S;
         std::vector<double> V((size_t)3 * N);                    // [3][N], as mdqt_get_state gives it
         for (int c = 0; c < 3; ++c) std::copy_n(Vs[k].begin() + (size_t)c * S, N, V.begin() + (size_t)c * N);
-        if (pump_output_host(s, V, Ps[k], nullptr, e->writer.get())) return -1;
+        double epot = 0.;
+        const bool have = q < batched.size() && batched[q] == k;
+        if (have) epot = ens_epot_of(s, rows + 64 * q++);
+        if (pump_output_host(s, V, Ps[k], nullptr, e->writer.get(), have ? &epot : nullptr)) return -1;
         if (vaf >= 0 && pump_vaf_host(s, V, vaf)) return -1;
     }
     return 0;

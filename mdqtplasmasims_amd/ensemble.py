@@ -14,15 +14,20 @@ state is bit for bit what :class:`~mdqtplasmasims_amd.engine.Simulation` gives f
     step();qstep() x n  :1376-1377     Ensemble.substeps(n)         mdqt_ensemble_substeps
     forces + ratio substeps, x n       Ensemble.md_steps(n)         mdqt_ensemble_md_steps
     main()            :1139-1383       Ensemble.run()               mdqt_ensemble_run
+    output()          :917-1032        Ensemble.output()            mdqt_ensemble_output
+    output()'s numbers                 Ensemble.observables()       mdqt_ensemble_observables
+    Epotential()      :244-281         Ensemble.epotential()        mdqt_ensemble_epotential
     =================================  ===========================  ==========================
 """
 from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
+
 from ._ensemble_base import _EnsembleBase
-from ._lib import MdqtParams, check, lib
-from .engine import Simulation, default_params
+from ._lib import MdqtParams, check, dptr, lib
+from .engine import NBINS, Simulation, default_params
 
 
 def job_params(base: MdqtParams, k: int) -> MdqtParams:
@@ -63,7 +68,8 @@ class Ensemble(_EnsembleBase):
         return [j.N for j in self.jobs]
 
     def set_option(self, name: str, value: int):
-        """"qt_waves" (the batched QT kernel's register budget) or any Simulation option, on every job"""
+        """"qt_waves" (the batched QT kernel's register budget), "output_batch" (1: output() of all jobs in one
+        device pass, 0: job after job, the default) or any Simulation option, on every job"""
         check(lib().mdqt_ensemble_set_option(self.h, name.encode(), int(value)), "ensemble_set_option")
 
     # ---- the reference's function seam, for every job at once ----
@@ -86,6 +92,32 @@ class Ensemble(_EnsembleBase):
     def synchronize(self):
         check(lib().mdqt_ensemble_synchronize(self.h), "ensemble_synchronize")
 
+    # ---- output() of every job in one device pass (option "output_batch") ----
+    def output(self):
+        """output() of every job; returns when the files are on disk"""
+        check(lib().mdqt_ensemble_output(self.h), "ensemble_output")
+
+    def observables(self, kde: bool = True, pops: bool = True):
+        """a list of what Simulation.observables() returns, job by job"""
+        n = self.N
+        o = np.zeros((len(n), 7))
+        P = np.zeros((len(n), 3, NBINS)) if kde else None
+        pp = np.zeros((sum(n), 3)) if pops else None
+        check(lib().mdqt_ensemble_observables(self.h, dptr(o), dptr(P), dptr(pp)), "ensemble_observables")
+        at = np.concatenate(([0], np.cumsum(n)))
+        return [(o[k], P[k] if kde else None, pp[at[k]:at[k + 1]] if pops else None) for k in range(len(n))]
+
+    def epotential(self):
+        """Epotential() of every job: [njobs]"""
+        out = np.zeros(len(self.jobs))
+        check(lib().mdqt_ensemble_epotential(self.h, dptr(out)), "ensemble_epotential")
+        return out
+
+    @property
+    def output_launches(self):
+        """kernel launches the batched output path has issued (a member's own fallback calls are not counted)"""
+        return int(lib().mdqt_ensemble_output_launches(self.h))
+
     # ---- timing ----
     def enable_timing(self, on: bool = True):
         """record the two batched kernels' dispatch timestamps at every launch"""
@@ -94,9 +126,15 @@ class Ensemble(_EnsembleBase):
     def kernel_times(self):
         """{force_ms, n_force, substep_ms, n_substep, force_median_ms, substep_median_ms} of the batched
         launches since the last call (synchronises and resets)"""
-        out = (C.c_double * 6)()
-        check(lib().mdqt_ensemble_kernel_times(self.h, out, 6), "ensemble_kernel_times")
-        return self._times(out, ("force_ms", "n_force", "substep_ms", "n_substep", "force_median_ms", "substep_median_ms"))
+        return {k: v for k, v in self.output_kernel_times().items() if "potential" not in k and "kde" not in k}
+
+    def output_kernel_times(self):
+        """kernel_times() and the batched output's potential and KDE launches: potential_ms, n_potential, kde_ms,
+        n_kde, potential_median_ms, kde_median_ms"""
+        out = (C.c_double * 12)()
+        check(lib().mdqt_ensemble_kernel_times(self.h, out, 12), "ensemble_kernel_times")
+        return self._times(out, ("force_ms", "n_force", "substep_ms", "n_substep", "force_median_ms", "substep_median_ms",
+                                 "potential_ms", "n_potential", "kde_ms", "n_kde", "potential_median_ms", "kde_median_ms"))
 
 
 __all__ = ["Ensemble", "job_params"]

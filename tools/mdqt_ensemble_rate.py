@@ -17,11 +17,22 @@ Prints ONE JSON line:
              fractions as the project counts them (QT 1,750 flop per particle-qstep, force 30 flop per
              pair, N (N - 1) / 2 pairs per job; against 78.6 TF)
 Rates are particle-qsteps/s summed over the jobs.  Any error exits non-zero; there is no CPU fallback.
+
+--mode output measures output() of all members instead: per J in --jobs, --outputs outputs --every MD steps
+apart after --skip uncounted ones, the wall time (ms, median / min / max over the outputs) of
+  members_observables:  for j in e.jobs: j.observables()   each member's device pass and synchronisation, no files
+  members_output:       for j in e.jobs: j.output()        ... and its files, formatted and flushed
+and, where the library has the batched output (this is skipped under MDQT_LIB with an older build), for
+output_batch 0 and 1: e.observables() and e.output() (files flushed inside), with the batched potential and
+KDE launches' own median durations.  The observables / output pairs split an output into the device pass with
+its synchronisations and the files' formatting.
 """
 import argparse
 import json
 import os
+import shutil
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,6 +55,55 @@ def timed(step, sync, steps, warmup):
     return time.perf_counter() - t0
 
 
+def stats_ms(xs):
+    xs = sorted(xs)
+    return dict(median=xs[len(xs) // 2] * 1e3, min=xs[0] * 1e3, max=xs[-1] * 1e3)
+
+
+def output_mode(M, a, params, jobs, out):
+    """the wall time of one output() of all members, by path (see the module docstring)"""
+    from mdqtplasmasims_amd._lib import lib
+    batched = hasattr(lib(), "mdqt_ensemble_output")
+    out["mode"] = "output"
+    out["outputs"], out["every"], out["skip"] = a.outputs, a.every, a.skip
+    out["output"] = []
+    for J in jobs:
+        paths = {"members_observables": (None, lambda e: [j.observables() for j in e.jobs]),
+                 "members_output": (None, lambda e: [j.output() for j in e.jobs])}
+        if batched:
+            for ob in (0, 1):
+                paths[f"observables_batch{ob}"] = (ob, lambda e: e.observables())
+                paths[f"output_batch{ob}"] = (ob, lambda e: e.output())
+        row = dict(jobs=J)
+        for name, (ob, call) in paths.items():
+            base = tempfile.mkdtemp(prefix="mdqt_output_")
+            try:
+                with M.Ensemble(njobs=J, seed=12346, job=1, saveDirectory=base + "/", **params) as e:
+                    if ob is not None:
+                        e.set_option("output_batch", ob)
+                    for j in e.jobs:
+                        j.setup_directories()
+                    e.init()
+                    if ob == 1:
+                        e.enable_timing(True)
+                    ts = []
+                    for k in range(a.skip + a.outputs):
+                        e.md_steps(a.every)
+                        e.synchronize()
+                        t0 = time.perf_counter()
+                        call(e)
+                        ts.append(time.perf_counter() - t0)
+                    row["N_total"] = sum(e.N)
+                    row[name] = stats_ms(ts[a.skip:])
+                    if ob == 1:
+                        kt = e.output_kernel_times()
+                        row[name]["potential_us"] = kt["potential_median_ms"] * 1e3
+                        row[name]["kde_us"] = kt["kde_median_ms"] * 1e3
+            finally:
+                shutil.rmtree(base, ignore_errors=True)
+        out["output"].append(row)
+
+
 def main():
     ap = argparse.ArgumentParser(formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
@@ -54,6 +114,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--qt-waves", type=int, default=0, help="Ensemble option qt_waves (0, 3)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--mode", choices=["rate", "output"], default="rate")
+    ap.add_argument("--outputs", type=int, default=25, help="--mode output: timed outputs")
+    ap.add_argument("--every", type=int, default=40, help="--mode output: MD steps between outputs (sampleFreq)")
+    ap.add_argument("--skip", type=int, default=5, help="--mode output: uncounted outputs first")
     ap.add_argument("--json", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
 
@@ -63,6 +127,16 @@ def main():
     streams = [int(x) for x in a.streams.split(",") if x]
     out = dict(tool="mdqt_ensemble_rate", config=a.config, steps=a.steps, warmup=a.warmup, qt_waves=a.qt_waves,
                unit="particle-qsteps/s", fp64_peak=FP64_PEAK)
+    if a.mode == "output":
+        output_mode(M, a, params, jobs, out)
+        out["unit"] = "ms per output of all members"
+        line = json.dumps(out)
+        print(line)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                f.write(line + "\n")
+        return
 
     # one Simulation alone
     with M.Simulation(seed=12346, job=1, **params) as s:
