@@ -149,7 +149,8 @@ int         mdqt_potentials_raw(int N, double L, double lDeb, const double* R, s
  * fn: 0 = sincos_tab (the 64-entry table form of the coupling phase, |x| < 2^20: out0 = sin, out1 =
  * cos), 1 = sincos_fast (Cody-Waite by pi/2, |x| < 2^20), 2 = sincos_q2 (the table form, the library
  * for |x| >= 2^20), 3 = rsq3 (out0 = 1/sqrt(x)), 4 = exp_neg (out0 = e^x, x <= 0), 5 = the pair
- * kernels' table 2^t on x = 64 t <= 0 (out0 = 2^(x/64)).  out1 may be NULL; fn 3-5 write 0 to it. */
+ * kernels' table 2^t on x = 64 t <= 0 (out0 = 2^(x/64)), 6 = the math library's exp as the velocity
+ * distributions call it (out0 = e^x, subnormal results included).  out1 may be NULL; fn 3-6 write 0 to it. */
 int         mdqt_device_math(int fn, const double* x, int n, double* out0, double* out1, int device);
 
 /* ---- diagnostics / output ---- */

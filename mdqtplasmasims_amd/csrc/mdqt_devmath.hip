@@ -1,4 +1,4 @@
-// mdqt_device_math (include/mdqt.h): the device math functions of the QT and pair kernels, evaluated
+// mdqt_device_math (include/mdqt.h): the device math functions of the QT, pair and observables kernels, evaluated
 // one element per thread through the same inline functions the kernels call, so that a test can hold
 // each of them to its stated error against an extended-precision value (tests/test_gpu_device_math.py).
 // No shared state; the two tables are read from their __constant__ arrays (the kernels stage the same
@@ -17,6 +17,7 @@ enum DevMathFn : int {
     DM_RSQ3 = 3,          // rsq3(x)
     DM_EXP_NEG = 4,       // exp_neg(x), x <= 0
     DM_EXP2_TAB = 5,      // exp2_neg_cut_tab(x, true, kExp2Tab64) = 2^(x/64), x <= 0
+    DM_EXP_LIB = 6,       // exp(x): the math library's, as the velocity distributions call it (kde_chunk)
     DM_NFN
 };
 
@@ -32,6 +33,7 @@ __global__ __launch_bounds__(256) void k_device_math(int fn, const double* __res
     case DM_SINCOS_Q2: sincos_q2(v, kSinCos64, a, b); break;
     case DM_RSQ3: a = rsq3(v); break;
     case DM_EXP_NEG: a = exp_neg(v); break;
+    case DM_EXP_LIB: a = exp(v); break;
     default: a = exp2_neg_cut_tab(v, true, kExp2Tab64); break;
     }
     out0[i] = a;

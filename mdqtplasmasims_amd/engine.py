@@ -98,7 +98,8 @@ def potentials_raw(R, L: float, lDeb: float, nseg: int = 0, device: int = -1, va
     return U
 
 
-DEVICE_MATH_FN = {"sincos_tab": 0, "sincos_fast": 1, "sincos_q2": 2, "rsq3": 3, "exp_neg": 4, "exp2_tab": 5}
+DEVICE_MATH_FN = {"sincos_tab": 0, "sincos_fast": 1, "sincos_q2": 2, "rsq3": 3, "exp_neg": 4, "exp2_tab": 5,
+                  "exp": 6}
 
 
 def device_math(fn, x, device: int = -1):

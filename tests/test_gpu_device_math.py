@@ -22,6 +22,9 @@ absolute error of sincos_tab) — none is fitted to the GPU:
   rsq3                    relative error <= 2 x 2^-53 on [2^-20, 2^20] and on (0.9, 1]
   exp_neg                 <= 1.1 ulp on [-40, 0]
   table 2^t               <= 2 ulp on t in [-60, 0]
+  library exp             <= 1 ulp on [-746.9, 0], the ulp clamped to 2^-1074 where the result is subnormal, and
+                          exactly +0 at and beyond -V2 kKdeSkip^2 = -746.91 (the velocity distributions' terms and
+                          their skip radius: tests/obs_truth.py takes E_EXP = 1 from this, docs/OBSERVABLES.md)
 
 Measured on an MI355X (every test prints its maximum and where):
 
@@ -39,7 +42,10 @@ Measured on an MI355X (every test prints its maximum and where):
                           series' truncation (0.32 ulp) came on top of the table entry's, the series' and
                           the product's roundings.  The series is now a fit (0.02 ulp) and the result one
                           FMA on the table entry, fma(te, g q, te), in the same six operations
-                          (mdqt_pairs.hpp): 1.00 ulp (1.01 in a C transcription on 3e7 arguments)"""
+                          (mdqt_pairs.hpp): 1.00 ulp (1.01 in a C transcription on 3e7 arguments)
+  library exp             0.83 ulp on normal results (x = -113.95), 0.88 ulp on subnormal ones (x = -708.75, in
+                          units of 2^-1074; none of the 44,791 subnormal results flushed); +0 at and beyond
+                          -746.91 on every argument"""
 import numpy as np
 import pytest
 
@@ -228,9 +234,55 @@ def test_exp2_table_error(dm):
     assert report("table 2^t", x, eu, "ulp") <= 2.0
 
 
+def ld_to_mp(t):
+    """a long double as an mpmath number, exactly (also below the double range)"""
+    import mpmath
+    m, e = np.frexp(LD(t))
+    hi = float(m)
+    return (mpmath.mpf(hi) + mpmath.mpf(float(m - LD(hi)))) * mpmath.mpf(2) ** int(e)
+
+
+def test_library_exp_error_and_underflow(dm):
+    """the math library's exp as kde_chunk and tagged_kde_chunk call it, over the whole range of their
+    arguments x = -V2 d^2: <= 1 ulp of the result against expl, with the ulp clamped to 2^-1074 where the result
+    is subnormal (x < -708.396), and exactly +0 at and beyond -V2 kKdeSkip^2, where the kernels skip the call"""
+    import mpmath
+    from tests import obs_truth as ot
+    rng = np.random.default_rng(7)
+    ln2 = np.log(2.0)
+    first_sub, last_nonzero = -1022 * ln2, -1075 * ln2         # e^x = 2^-1022; e^x = 2^-1075, the tie to zero
+    assert abs(first_sub + 708.3964185322641) < 1e-12 and abs(last_nonzero + 745.1332191019412) < 1e-12
+    skip = -ot.V2 * 0.0773 * 0.0773                            # the kernels' (-V2 d) d at d = kKdeSkip
+    assert -746.92 < skip < -746.90
+    x = np.concatenate([-rng.uniform(0, 746.9, NPTS), -log_uniform(rng, -40, np.log2(746.9), 60_000, signed=False),
+                        -rng.uniform(708.0, 746.9, 40_000), -np.abs(binade_edges(-40, 9)),
+                        neighbours(np.array([first_sub, last_nonzero, skip, -745.0, -746.0])),
+                        np.array([0.0, -0.0, -746.9])])
+    x = x[(x >= -746.9) & (x <= 0)]
+    xl = x.astype(LD)
+    tru = np.exp(xl)
+    mpmath.mp.dps = 40
+    for i in np.concatenate([np.linspace(0, x.size - 1, 150).astype(int), np.nonzero(x < -708.4)[0][:50]]):
+        m = mpmath.exp(mpmath.mpf(float(x[i])))
+        assert abs(ld_to_mp(tru[i]) - m) <= mpmath.mpf(2) ** -60 * m, x[i]
+    got = dm("exp", x)
+    ulp = np.maximum(ulp_of(tru), LD(2.0) ** -1074)
+    eu = np.abs(got.astype(LD) - tru) / ulp
+    sub = x < first_sub
+    report("library exp, normal results", x[~sub], eu[~sub], "ulp")
+    report("library exp, subnormal results (ulp = 2^-1074)", x[sub], eu[sub], "ulp")
+    assert np.count_nonzero(got[sub]) > 10_000                  # subnormal results are not flushed
+    assert report("library exp", x, eu, "ulp") <= 1.0
+    beyond = np.concatenate([neighbours(np.array([skip]))[[0, 1, 3]], skip * rng.uniform(1, 2, 1000),
+                             np.array([-747.0, -1000.0, -1e6, -1e300, -np.inf])])
+    beyond = beyond[beyond <= skip]
+    z = dm("exp", beyond)
+    assert beyond.size > 1000 and np.all(z == 0.0) and not np.signbit(z).any()
+
+
 def test_device_math_rejects_bad_arguments(dm):
     from mdqtplasmasims_amd import MdqtError
     with pytest.raises(MdqtError, match="unknown function"):
-        dm(6, np.zeros(4))
+        dm(7, np.zeros(4))
     with pytest.raises(MdqtError, match="bad arguments"):
         dm("rsq3", np.zeros(0))

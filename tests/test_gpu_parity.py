@@ -616,6 +616,7 @@ def test_sharded_local_group_bit_identical(eng, world):
 # ---------------------------------------------------------------------------------------------
 
 def test_observables_match_oracle(eng, orc):
+    """(norm-wise, one size; every element against a derived bound: tests/test_gpu_obs_accuracy.py)"""
     kw = dict(N0=500, seed=8, rng_mode=1)
     s = eng.Simulation(**kw).init()
     o = orc.OracleSim(nthreads=8, **kw).init()
@@ -639,7 +640,8 @@ def test_kde_skipping_matches_dense_sum(eng, orc):
     exact zeros on all its bins (|b -+ v| >= kKdeSkip = 0.0773, beyond exp's underflow for
     V2 = 1/(2 0.002^2); mdqt_internal.hpp asserts the threshold against V2): against the oracle's
     dense sum on velocities spread over and beyond the 2001 bins, with ions placed just inside and
-    just outside the skip distance of bin centres"""
+    just outside the skip distance of bin centres.  Norm-wise; every bin against a derived
+    bound, subnormal ones included: tests/test_gpu_obs_accuracy.py"""
     kw = dict(N0=500, seed=8, rng_mode=1)
     o = orc.OracleSim(nthreads=8, **kw).init()
     st = o.get_state()
