@@ -16,6 +16,7 @@
 #include "../../include/mdqt.h"
 #include "mdqt_batch.hpp"
 #include "mdqt_internal.hpp"
+#include "mdqt_main_loops.hpp"
 #include "mdqt_writer.hpp"
 
 // rccl.h is included only where a collective is issued (mdqt_step.cpp, mdqt_comm.cpp); the context
@@ -340,7 +341,10 @@ int output_files(mdqt_ctx* s, const double* o, std::shared_ptr<std::vector<doubl
                  std::shared_ptr<std::vector<double>> pops, std::shared_ptr<std::vector<double>> V);
 int write_conditions_async(mdqt_ctx* s, int c0);
 int read_ions_conditions(mdqt_ctx* s, int c0, std::vector<double>& R, std::vector<double>& V);
-int fusable_substeps(const mdqt_ctx* s, double tend, long c0, int ts);
+// the SpeedUp time loop's schedule (mdqt_main_loops.hpp) of a context, or of an ensemble's member 0
+inline SpeedUpSchedule speedup_schedule(const mdqt_ctx* s) {
+    return {s->dtQ, s->p.tmax + 0.0009, s->p.sampleFreq, s->ratio, MAXSUB};
+}
 
 // mdqt_pump.cpp: the pieces of the optical-pumping programs' main() the pump ensemble shares
 int pump_setup_directories(mdqt_ctx* s);
@@ -352,6 +356,7 @@ int pump_output_host(mdqt_ctx* s, const std::vector<double>& V, std::vector<doub
 int pump_vaf_host(mdqt_ctx* s, const std::vector<double>& V, int c1V);
 int pump_write_conditions(mdqt_ctx* s, int c0);
 int pump_read_conditions(mdqt_ctx* s, int c0);
+PumpSchedule pump_schedule(const mdqt_ctx* s);   // the pump time loop's, of a context or of an ensemble's member 0
 
 // mdqt_ensemble.cpp: the ensemble's machinery the pump ensemble reuses
 int ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, const char* what, bool pump);

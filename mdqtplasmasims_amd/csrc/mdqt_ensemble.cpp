@@ -13,7 +13,7 @@
 // (mdqt_batch.hpp: PinRing, 8 slots) and copied in stream order before the launches that read them; a slot
 // is reused after the event behind its copy has completed.  mdqt_ensemble_substeps and mdqt_ensemble_run copy one launch's blocks just
 // before it; mdqt_ensemble_md_steps builds the blocks of up to 64 MD steps ahead and copies them at once
-// (ens_md_steps has the reason and the numbers).
+// (ens_md_steps has the reason and the numbers).  mdqt_ensemble_run: mdqt_run's time loop (mdqt_main_loops.hpp) on a batched driver.
 
 #include <algorithm>
 
@@ -372,43 +372,34 @@ extern "C" int mdqt_ensemble_synchronize(mdqt_ensemble* e) {
     return ens_range_flags(e);
 }
 
-// main()'s time loop (SpeedUp:1248-1383) as mdqt_run has it (mdqt_io.cpp), for every job at once:
-// the members are in lockstep, so job 0's t and c0 drive the loop
+// main() (SpeedUp:1139-1383) for every job at once; the time loop itself is mdqt_run's, speedup_loop
+// (mdqt_main_loops.hpp): the members are in lockstep, so job 0's t and c0 drive it
 extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
     if (!e) return set_error("NULL ensemble");
     for (mdqt_ctx* s : e->jobs)
         if (mdqt_setup_directories(s)) return -1;
-    if (e->jobs[0]->p.newRun == 1) {
-        if (mdqt_ensemble_init(e)) return -1;
-    } else {
-        for (mdqt_ctx* s : e->jobs) {
-            s->c0 = s->p.c0;
-            if (mdqt_read_conditions(s, s->c0)) return -1;
-        }
-    }
+    const bool fresh = e->jobs[0]->p.newRun == 1;
+    for (mdqt_ctx* s : e->jobs)                         // one after the other, as mdqt_ensemble_init
+        if (fresh ? mdqt_init(s) : mdqt_read_conditions(s, s->p.c0)) return -1;
     if (ens_check(e, "mdqt_ensemble_run")) return -1;
     HIPCHK(hipSetDevice(e->dev));
-    mdqt_ctx* a = e->jobs[0];
-    const double tend = a->p.tmax + 0.0009;
-    const int sf = a->p.sampleFreq, ratio = a->ratio;
-    int tsc = ratio;                                                                    // :1235
-    while (a->t <= tend) {                                                              // :1248
-        if ((a->c0 + 1) % sf == 0 && tsc == 1)                                          // :1365
-            if (ens_output(e)) return -1;               // one device pass and synchronisation (option output_batch)
-        if (tsc == ratio) {                                                             // :1369
-            if (ens_range_flags(e, false)) return -1;
-            if (ens_forces(e)) return -1;
+    struct {                                            // the loop's driver: one batched call over the members
+        mdqt_ensemble* e;
+        double t() const { return e->jobs[0]->t; }
+        int c0() const { return e->jobs[0]->c0; }
+        int output() { return ens_output(e); }          // one device pass and synchronisation (option output_batch)
+        bool may_fuse_interval() { return false; }      // k_md_step is one system per launch
+        int start_interval(bool) {
+            if (ens_range_flags(e, false) || ens_forces(e)) return -1;
             for (mdqt_ctx* s : e->jobs) s->c0++;
-            tsc = 0;
+            return 0;
         }
-        // fuse the following iterations while they are pure step();qstep() (App. C-9)
-        const int n = fusable_substeps(a, tend, a->c0, tsc);
-        if (ens_substeps(e, n)) return -1;                                            // :1376-1377
-        tsc += n;
-    }
+        int substeps(int n) { return ens_substeps(e, n); }
+    } d{e};
+    if (speedup_loop(speedup_schedule(e->jobs[0]), d)) return -1;
     for (mdqt_ctx* s : e->jobs)
         if (write_conditions_async(s, s->c0)) return -1;                               // :1381
-    return flush_files(a);                              // the shared pool: every member's files
+    return flush_files(e->jobs[0]);                     // the shared pool: every member's files
 }
 
 extern "C" int mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on) {

@@ -1,5 +1,6 @@
 // ---------------------------------------------------------------------------------------------
-// files (reference formats, SpeedUp:725-1032) and the time loop (main, :1139-1383)
+// files (reference formats, SpeedUp:725-1032) and main() (:1139-1383): mdqt_run is the preamble, this context's
+// driver and the time loop that mdqt_ensemble_run shares (mdqt_main_loops.hpp: speedup_loop)
 // ---------------------------------------------------------------------------------------------
 
 #include <errno.h>
@@ -264,52 +265,26 @@ extern "C" int mdqt_read_conditions(mdqt_ctx* s, int c0) {    // readConditions,
     return 0;
 }
 
-// main()'s loop, looking ahead from s->t with MD step counter c0 and ts substeps of the interval done: how
-// many of the following iterations are pure step(); qstep() (App. C-9), i.e. can run as one launch — up to
-// MAXSUB, the end of the run, the next output (:1365) or the end of the interval, whichever comes first
-int mdqt::fusable_substeps(const mdqt_ctx* s, double tend, long c0, int ts) {
-    int n = 0;
-    double tt = s->t;
-    do {
-        n++; ts++; tt += s->dtQ;
-    } while (n < MAXSUB && tt <= tend && !((c0 + 1) % s->p.sampleFreq == 0 && ts == 1) && ts != s->ratio);
-    return n;
-}
-
-extern "C" int mdqt_run(mdqt_ctx* s) {                        // main(), SpeedUp:1139-1383
+// main(), SpeedUp:1139-1383; the time loop itself is speedup_loop (mdqt_main_loops.hpp)
+extern "C" int mdqt_run(mdqt_ctx* s) {
     if (!s) return set_error("NULL context");
     if (s->p.world_size > 1 && !s->comm) return set_error("mdqt_run: sharded run needs mdqt_comm_init first");
     if (mdqt_setup_directories(s)) return -1;
-    if (s->p.newRun == 1) {
-        if (mdqt_init(s)) return -1;
-    } else {
-        s->c0 = s->p.c0;
-        if (mdqt_read_conditions(s, s->c0)) return -1;
-    }
-    const double tend = s->p.tmax + 0.0009;
-    const int sf = s->p.sampleFreq, ratio = s->ratio;
-    int tsc = ratio;                                                                    // :1235
-    while (s->t <= tend) {                                                              // :1248
-        if ((s->c0 + 1) % sf == 0 && tsc == 1)                                          // :1365
-            if (output_async(s)) return -1;             // files formatted while the loop goes on
-        if (tsc == ratio) {                                                             // :1369
-            // a whole interval without an output or the end inside it: one k_md_step launch
-            if (fused_applies(s) && fusable_substeps(s, tend, (long)s->c0 + 1, 0) == ratio) {
-                if (local_reduce(s) || md_step_fused(s)) return -1;
-                s->last_fused = 1;
-                s->c0++;
-                continue;                                // tsc stays = ratio
-            }
-            s->last_fused = 0;
-            if (mdqt_allgather_positions(s)) return -1;                                 // §8e
-            if (mdqt_forces(s)) return -1;
+    if (s->p.newRun == 1 ? mdqt_init(s) : mdqt_read_conditions(s, s->p.c0)) return -1;
+    struct {                                            // the loop's driver: this context's own calls
+        mdqt_ctx* s;
+        double t() const { return s->t; }
+        int c0() const { return s->c0; }
+        int output() { return output_async(s); }        // files formatted while the loop goes on
+        bool may_fuse_interval() { return fused_applies(s); }
+        int start_interval(bool whole) {                // whole: the interval as one k_md_step launch; else §8e, forces()
+            s->last_fused = whole;
+            if (whole ? local_reduce(s) || md_step_fused(s) : mdqt_allgather_positions(s) || mdqt_forces(s)) return -1;
             s->c0++;
-            tsc = 0;
+            return 0;
         }
-        // fuse the following iterations while they are pure step();qstep() (App. C-9)
-        const int n = fusable_substeps(s, tend, s->c0, tsc);
-        if (mdqt_substeps(s, n)) return -1;                                            // :1376-1377
-        tsc += n;
-    }
+        int substeps(int n) { return mdqt_substeps(s, n); }
+    } d{s};
+    if (speedup_loop(speedup_schedule(s), d)) return -1;
     return mdqt_write_conditions(s, s->c0);             // :1381; also joins the writers
 }

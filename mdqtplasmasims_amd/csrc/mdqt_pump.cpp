@@ -1,6 +1,7 @@
 // ---------------------------------------------------------------------------------------------
-// The optical-pumping programs' main() — randomFrozenStartTag408Linear.cpp (":" lines below),
-// randomFrozenStartTag408Quad.cpp, randomFrozenStartTag422Linear.cpp (same flow).
+// The optical-pumping programs' main() — randomFrozenStartTag408Linear.cpp (":" lines below), 408Quad and
+// 422Linear (same flow): its pieces for one context, and mdqt_run_pump — the preamble, this context's driver
+// (its operations: a context's own calls) and the time loop both pump entry points share (mdqt_main_loops.hpp).
 // ---------------------------------------------------------------------------------------------
 
 #include <math.h>
@@ -273,69 +274,35 @@ extern "C" int mdqt_get_spin_up_list(mdqt_ctx* s, int* tags, int* n_up) {
     return 0;
 }
 
-extern "C" int mdqt_run_pump(mdqt_ctx* s) {                     // main() :981-1076
+PumpSchedule mdqt::pump_schedule(const mdqt_ctx* s) {
+    const double tpump = s->p.tpumpreal * 813490 * sqrt(s->p.density);      // :79
+    const double tendV0 = s->p.tstartV0 + tpump;                             // :80
+    return {s->dtQ, s->p.tmax + 0.0009, s->p.tstartV0, tendV0, s->p.sampleFreq, s->ratio, MAXSUB};
+}
+
+// main() :981-1076; the time loop itself is pump_loop (mdqt_main_loops.hpp)
+extern "C" int mdqt_run_pump(mdqt_ctx* s) {
     if (!s) return set_error("NULL context");
     if (s->p.qt_model < 1 || s->p.qt_model > 3) return set_error("mdqt_run_pump: qt_model must be 1, 2 or 3");
     if (s->p.world_size != 1) return set_error("mdqt_run_pump: world_size 1 only");
     if (pump_setup_directories(s)) return -1;
-    int recorded = 0;                                            // recordedSpinUps :81
     s->spinUp.clear();
     s->nSpinUp = 0;
     s->pumpBin0 = -2000;
-    if (s->p.newRun == 1) {                                      // :1036-1046
-        if (mdqt_init(s)) return -1;
-    } else {
-        if (pump_read_conditions(s, s->p.c0)) return -1;
-        recorded = 1;
-    }
-    const double tpump = s->p.tpumpreal * 813490 * sqrt(s->p.density);      // :79
-    const double tendV0 = s->p.tstartV0 + tpump;                             // :80
-    const double tstartV0 = s->p.tstartV0;
-    const double tend = s->p.tmax + 0.0009;
-    const int sf = s->p.sampleFreq, ratio = s->ratio;
-    int tsc = ratio;                                             // :1033
-    // quantum steps are queued while nothing else happens and run as one fused launch
-    int pending = 0;
-    double tv = s->t;                                            // the loop's t (s->t lags by `pending` qsteps)
-    auto flush = [&]() -> int {
-        if (pending > 0) {
-            if (run_substeps(s, pending, 0, 1, 1)) return -1;    // qstep() x pending :396-598
-            pending = 0;
-            if (s->t != tv) return set_error("mdqt_run_pump: time bookkeeping mismatch");
-        }
-        return 0;
-    };
-    while (tv <= tend) {                                         // :1050
-        if (recorded == 0 && tv >= tendV0) {                     // :1052-1058
-            if (flush()) return -1;
-            if (measure_spin_ups(s)) return -1;
-            recorded = 1;
-            if (output_pump(s)) return -1;
-            if (vaf_pump(s, 0)) return -1;
-        }
-        if ((s->c0 + 1) % sf == 0 && tsc == 1 && recorded == 1) {   // :1062-1069
-            if (flush()) return -1;
-            if (output_pump(s)) return -1;
-            if (vaf_pump(s, 1)) return -1;
-        }
-        if (tsc == ratio) {                                      // :1070-1074
-            if (flush()) return -1;
-            if (pump_md_step(s)) return -1;
-            s->c0++;
-            tsc = 0;
-        }
-        if (tv < tendV0 && tv > tstartV0) {                      // :1075-1077 qstep()
-            pending++;
-            tv += s->dtQ;                                        // qstep's t += dtQuant :597
-            if (pending == MAXSUB && flush()) return -1;
-        } else {                                                 // :1078-1080
-            if (flush()) return -1;
-            s->t += s->dtQ;
-            tv = s->t;
-        }
-        tsc++;
-    }
-    if (flush()) return -1;
+    const int recorded = s->p.newRun == 1 ? 0 : 1;               // recordedSpinUps :81
+    if (recorded ? pump_read_conditions(s, s->p.c0) : mdqt_init(s)) return -1;   // :1036-1046
+    struct {                                                     // the loop's driver: this context's own calls
+        mdqt_ctx* s;
+        double t() const { return s->t; }
+        int c0() const { return s->c0; }
+        int qsteps(int n) { return run_substeps(s, n, 0, 1, 1); }    // qstep() x n :396-598
+        int measure() { return measure_spin_ups(s); }
+        int output(int vaf) { return output_pump(s) || vaf_pump(s, vaf); }
+        int md_step(bool, bool) { return mdqt_pump_md_steps(s, 1); }   // pump_md_step does both of its own half drifts
+        int idle() { s->t += s->dtQ; return 0; }
+        int fail(const char* what) { return set_error("mdqt_run_pump: %s", what); }
+    } d{s};
+    if (pump_loop(pump_schedule(s), recorded, d)) return -1;
     if (flush_files(s)) return -1;
     return pump_write_conditions(s, s->c0);                      // :1084
 }

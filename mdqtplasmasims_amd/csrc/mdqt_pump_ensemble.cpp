@@ -12,11 +12,10 @@
 // k_pump_kick_ens (the canonical slot sum, the kick, the trailing half drift and — when nothing reads R, V or F
 // before the next step — that step's leading half drift).  A step whose leading drift was not folded into the
 // launch before it (the first of a call, the one after an output or the measurement, the t == 0 step with its
-// forces() first) starts with k_pump_drift_ens.  The step blocks change only with a member's size or pending
-// state: they are uploaded when they differ from what the device holds; the QT and tagging blocks go through the
-// pinned ring.
-
-#include <math.h>
+// forces() first) starts with k_pump_drift_ens.  In a run the time loop decides which steps lead and fold
+// (mdqt_main_loops.hpp: pump_loop, mdqt_run_pump's too); mdqt_pump_ensemble_run's driver hands that to pump_step.
+// The step blocks change only with a member's size or pending state: they are uploaded when they differ from
+// what the device holds; the QT and tagging blocks go through the pinned ring.
 
 #include <algorithm>
 
@@ -305,8 +304,8 @@ extern "C" unsigned long long mdqt_pump_ensemble_launches(const mdqt_pump_ensemb
     return pe && pe->base ? pe->launches + pe->base->force_launches : 0;
 }
 
-// main() :981-1076 for every member at once, as mdqt_run_pump has it (mdqt_pump.cpp): the members are in
-// lockstep, so member 0's t and c0 drive the loop
+// main() :981-1076 for every member at once; the time loop itself is mdqt_run_pump's, pump_loop
+// (mdqt_main_loops.hpp): the members are in lockstep, so member 0's t and c0 drive it
 extern "C" int mdqt_pump_ensemble_run(mdqt_pump_ensemble* pe) {
     if (!pe) return set_error("NULL ensemble");
     mdqt_ensemble* e = pe->base;
@@ -316,85 +315,35 @@ extern "C" int mdqt_pump_ensemble_run(mdqt_pump_ensemble* pe) {
         s->nSpinUp = 0;
         s->pumpBin0 = -2000;
     }
-    int recorded = 0;                                            // recordedSpinUps :81
-    if (e->jobs[0]->p.newRun == 1) {                             // :1036-1046
-        for (mdqt_ctx* s : e->jobs)
-            if (mdqt_init(s)) return -1;
-    } else {
-        for (mdqt_ctx* s : e->jobs)
-            if (pump_read_conditions(s, s->p.c0)) return -1;
-        recorded = 1;
-    }
+    const int recorded = e->jobs[0]->p.newRun == 1 ? 0 : 1;      // recordedSpinUps :81
+    for (mdqt_ctx* s : e->jobs)                                  // :1036-1046
+        if (recorded ? pump_read_conditions(s, s->p.c0) : mdqt_init(s)) return -1;
     std::fill(pe->tag_cap.begin(), pe->tag_cap.end(), 0);        // (readConditions allocates the tags anew)
     if (pump_check(pe, "mdqt_pump_ensemble_run")) return -1;
     HIPCHK(hipSetDevice(e->dev));
-    mdqt_ctx* a = e->jobs[0];
-    const double tpump = a->p.tpumpreal * 813490 * sqrt(a->p.density);      // :79
-    const double tendV0 = a->p.tstartV0 + tpump;                             // :80
-    const double tstartV0 = a->p.tstartV0;
-    const double tend = a->p.tmax + 0.0009;
-    const double dtQ = a->dtQ;
-    const int sf = a->p.sampleFreq, ratio = a->ratio;
-    int tsc = ratio;                                             // :1033
-    int pending = 0;                                             // queued qsteps (one fused launch)
-    double tv = a->t;                                            // the loop's t (the members' lags by `pending` qsteps)
-    bool lead_done = false;                                      // the next step's leading drift went with the last launch
-    auto flush = [&]() -> int {
-        if (pending > 0) {
-            if (pump_qsteps(pe, pending)) return -1;             // qstep() x pending :396-598
-            pending = 0;
-            if (a->t != tv) return set_error("mdqt_pump_ensemble_run: time bookkeeping mismatch");
-        }
-        return 0;
-    };
-    // After the MD step at hand (c0 already counted): does the loop reach the next MD step, at a t > 0, before
-    // anything reads R, V or F — the measurement, an output, the end of the run?  The loop's own conditions,
-    // run ahead on copies (both branches of the loop's tail advance t by the same t += dtQ).
-    auto folds = [&](double x, int c0n) -> bool {
-        for (int ts = 0;;) {
-            x += dtQ;
-            ts++;
-            if (!(x <= tend)) return false;
-            if (recorded == 0 && x >= tendV0) return false;
-            if ((c0n + 1) % sf == 0 && ts == 1 && recorded == 1) return false;
-            if (ts == ratio) return x > 0;
-        }
-    };
-    while (tv <= tend) {                                         // :1050
-        if (recorded == 0 && tv >= tendV0) {                     // :1052-1058
-            if (flush()) return -1;
+    struct {                                                     // the loop's driver: one batched call over the members
+        mdqt_pump_ensemble* pe;
+        std::vector<mdqt_ctx*>& jobs;
+        double t() const { return jobs[0]->t; }
+        int c0() const { return jobs[0]->c0; }
+        int qsteps(int n) { return pump_qsteps(pe, n); }         // qstep() x n :396-598
+        int measure() {
             if (pump_tag(pe)) return -1;
-            for (mdqt_ctx* s : e->jobs)
+            for (mdqt_ctx* s : jobs)
                 if (pump_spin_ups_file(s)) return -1;
-            recorded = 1;
-            if (pump_output(pe, 0)) return -1;
+            return 0;
         }
-        if ((a->c0 + 1) % sf == 0 && tsc == 1 && recorded == 1) {   // :1062-1069
-            if (flush()) return -1;
-            if (pump_output(pe, 1)) return -1;
+        int output(int vaf) { return pump_output(pe, vaf); }
+        int md_step(bool lead, bool fold) {
+            if (pump_step(pe, lead, fold)) return -1;
+            for (mdqt_ctx* s : jobs) s->c0++;
+            return 0;
         }
-        if (tsc == ratio) {                                      // :1070-1074
-            if (flush()) return -1;
-            const bool fold = folds(tv, a->c0 + 1);
-            if (pump_step(pe, !lead_done, fold)) return -1;
-            lead_done = fold;
-            for (mdqt_ctx* s : e->jobs) s->c0++;
-            tsc = 0;
-        }
-        if (tv < tendV0 && tv > tstartV0) {                      // :1075-1077 qstep()
-            pending++;
-            tv += dtQ;                                           // qstep's t += dtQuant :597
-            if (pending == MAXSUB && flush()) return -1;
-        } else {                                                 // :1078-1080
-            if (flush()) return -1;
-            for (mdqt_ctx* s : e->jobs) s->t += s->dtQ;
-            tv = a->t;
-        }
-        tsc++;
-    }
-    if (flush()) return -1;
-    if (lead_done) return set_error("mdqt_pump_ensemble_run: a folded drift without its step");
-    if (flush_files(a)) return -1;                               // the shared pool: every member's files
+        int idle() { for (mdqt_ctx* s : jobs) s->t += s->dtQ; return 0; }
+        int fail(const char* what) { return set_error("mdqt_pump_ensemble_run: %s", what); }
+    } d{pe, e->jobs};
+    if (pump_loop(pump_schedule(e->jobs[0]), recorded, d)) return -1;
+    if (flush_files(e->jobs[0])) return -1;                      // the shared pool: every member's files
     for (mdqt_ctx* s : e->jobs)
         if (pump_write_conditions(s, s->c0)) return -1;          // :1084
     return 0;

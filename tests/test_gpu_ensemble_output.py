@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.ensemble_helpers import assert_same, tree
+
 pytestmark = pytest.mark.gpu
 
 SEED = dict(seed=501, job=1, rng_mode=1)
@@ -55,13 +57,7 @@ def probe_ensemble(e):
     return [record(obs[k], c[k], ep[k], j.counters()["Epot"]) for k, j in enumerate(e.jobs)]
 
 
-def assert_same(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), f"{what}: {k} differs"
-
-
-def state(sim):
+def state(sim):              # this file's own: ensemble_helpers.snapshot has Epot0 as well, which these tests never compared
     st = sim.get_state()
     c = sim.counters()
     return dict(st, qstep=sim.qstep_index, c0=c["c0"], counter=c["counter"], Epot=c["Epot"], N=sim.N)
@@ -236,16 +232,6 @@ def test_kernel_times_keep_their_six_and_grow(M):
 
 
 # ---- 4. output() files ----
-def tree(base):
-    out = {}
-    for d, _, fs in os.walk(base):
-        for f in fs:
-            p = os.path.join(d, f)
-            with open(p, "rb") as fh:
-                out[os.path.relpath(p, base)] = fh.read()
-    return out
-
-
 @pytest.mark.parametrize("params, scheme", [(SMALL, 2), (MID, 0)])
 def test_output_files(M, tmp_path, params, scheme):
     a, b = str(tmp_path / "ens") + "/", str(tmp_path / "one") + "/"

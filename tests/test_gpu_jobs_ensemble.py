@@ -12,6 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.ensemble_helpers import assert_same, member_params, snapshot, tree
+
 pytestmark = pytest.mark.gpu
 
 SMALL = dict(N0=62, seed=501, job=1, rng_mode=1)            # the oracle's init(): N = SMALL_N for jobs 1 .. 6
@@ -26,23 +28,9 @@ def M():
     return M
 
 
-def snapshot(sim):
-    st = sim.get_state()
-    c = sim.counters()
-    return dict(st, qstep=sim.qstep_index, c0=c["c0"], counter=c["counter"], Epot=c["Epot"], Epot0=c["Epot0"],
-                N=sim.N)
-
-
-def assert_same(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), f"{what}: {k} differs"
-
-
 def single(M, params, k, options, calls):
     """job k of an ensemble of `params`, on a context of its own, after `calls`"""
-    p = dict(params, seed=params["seed"] + k, job=params["job"] + k)
-    with M.Simulation(**p) as s:
+    with M.Simulation(**member_params(params, k)) as s:
         for name, v in options.items():
             s.set_option(name, v)
         s.init()
@@ -276,16 +264,6 @@ def test_refused_options(M):
 
 
 # ---- 9. run() ----
-def tree(base):
-    out = {}
-    for d, _, fs in os.walk(base):
-        for f in fs:
-            p = os.path.join(d, f)
-            with open(p, "rb") as fh:
-                out[os.path.relpath(p, base)] = fh.read()
-    return out
-
-
 def test_run_writes_the_singles_files(M, tmp_path):
     a, b = str(tmp_path / "ens") + "/", str(tmp_path / "one") + "/"
     nj = 3

@@ -11,6 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.ensemble_helpers import tree
+
 pytestmark = pytest.mark.gpu
 
 BASE = dict(numVelAutoCorrsSteps=8, seed=41, job=5)
@@ -39,15 +41,6 @@ def single(k, **kw):
 def assert_same_state(a, b, what=""):
     for name, x, y in zip("RVAU", a.get_state(), b.get_state()):
         assert np.array_equal(x, y), (what, name)
-
-
-def tree(root):
-    out = {}
-    for d, _, files in os.walk(root):
-        for f in files:
-            p = os.path.join(d, f)
-            out[os.path.relpath(p, root)] = open(p, "rb").read()
-    return out
 
 
 # ---- 1. the anneal: both passes of the per-thread loop, both pair-energy forms ----

@@ -15,11 +15,12 @@ produces next — tag_particles() (uniforms) and a further monte_carlo (the chai
 state), both equal only if the stream position is.
 """
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
+
+from tests.ensemble_helpers import tree
 
 pytestmark = pytest.mark.gpu
 
@@ -262,15 +263,6 @@ def test_kernel_times_report_the_batched_launches(M):
 
 
 # ---- 4. run(): the batched observables, every stage and file ----
-def tree(root):
-    out = {}
-    for d, _, files in os.walk(root):
-        for f in files:
-            p = os.path.join(d, f)
-            out[os.path.relpath(p, root)] = open(p, "rb").read()
-    return out
-
-
 @pytest.mark.parametrize("N", [125, 1331])
 def test_run_writes_the_same_files_in_both_modes_and_alone(M, tmp_path, N):
     J = 3

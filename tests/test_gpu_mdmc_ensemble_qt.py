@@ -13,10 +13,11 @@ The members of a test start from the same positions, velocities and wavefunction
 40 ions, as tests/test_mdmc_qt.py's qstep test has them), so they differ in their Philox key (seed + k, job + k)
 alone: the no-jump evolution is deterministic, and two members ending with different wavefunctions have jumped.
 """
-import os
 
 import numpy as np
 import pytest
+
+from tests.ensemble_helpers import tree
 
 pytestmark = pytest.mark.gpu
 
@@ -262,15 +263,6 @@ def test_an_ensemble_without_qt_refuses_the_calls(M):
 
 
 # ---- 7. run(): the pump and recorded stage in batched launches, every file ----
-def tree(root):
-    out = {}
-    for d, _, files in os.walk(root):
-        for f in files:
-            p = os.path.join(d, f)
-            out[os.path.relpath(p, root)] = open(p, "rb").read()
-    return out
-
-
 @pytest.mark.parametrize("model", [2, 3])
 def test_qtt_run_writes_the_same_files_in_both_modes_and_alone(M, tmp_path, model):
     J, T, pre = 3, QTT_RUN["numVelAutoCorrsSteps"], QTT_RUN["numPreRecordMDSteps"]

@@ -8,12 +8,12 @@ The members' N come from the host-side init() (the oracle's, on the CPU): SMALL 
 context takes the owner-computes rows by default, so SMALL also runs with force_scheme 2, which puts them
 through the batched force kernel); MID has five- and six-tile members with ragged last tiles, so that the
 grids' "past my last tile / group / chunk" exits run."""
-import filecmp
-import os
 import subprocess
 
 import numpy as np
 import pytest
+
+from tests.ensemble_helpers import assert_same, assert_same_trees, member_params, snapshot, tree
 
 pytestmark = pytest.mark.gpu
 
@@ -35,23 +35,6 @@ QT = {1: dict(Om=4.0, detuning=0.0), 2: dict(Om=6.0, detuning=0.0), 3: dict(Om=4
 def M():
     import mdqtplasmasims_amd as M
     return M
-
-
-def snapshot(sim):
-    st = sim.get_state()
-    c = sim.counters()
-    return dict(st, qstep=sim.qstep_index, c0=c["c0"], counter=c["counter"], Epot=c["Epot"], Epot0=c["Epot0"],
-                N=sim.N)
-
-
-def assert_same(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), f"{what}: {k} differs"
-
-
-def member_params(params, k):
-    return dict(params, seed=params["seed"] + k, job=params["job"] + k)
 
 
 # ---- 1. MD steps: the t == 0 form, then five steps at t > 0 (leading drift, folded drifts, the last unfolded) ----
@@ -191,26 +174,12 @@ def test_kernel_times_count_the_batched_launches(M):
 
 
 # ---- 5. run() and 6. the resume, against run_pump() of every job into another directory ----
-def tree(d):
-    out = []
-    for root, _, names in os.walk(d):
-        out += [os.path.relpath(os.path.join(root, n), d) for n in names]
-    return sorted(out)
-
-
-def assert_same_trees(a, b):
-    fa, fb = tree(a), tree(b)
-    assert fa == fb, (fa, fb)
-    assert fa, "no files written"
-    for f in fa:
-        assert filecmp.cmp(os.path.join(a, f), os.path.join(b, f), shallow=False), f"{f} differs"
-
-
-def run_both(M, model, njobs, params, da, db):
+def run_both(M, model, njobs, params, da, db, launches=None):
     """the ensemble's run into da, the singles' into db: (final states, spin-up lists, c0) of both sides"""
     p = dict(params, **PROGRAM[model])
     with M.PumpEnsemble(njobs, pump_program=model, saveDirectory=str(da) + "/", **p) as e:
         e.run()
+        assert launches is None or e.launches() == launches
         got = [(snapshot(j), j.spin_up_list()) for j in e.jobs]
     want = []
     for k in range(njobs):
@@ -238,11 +207,19 @@ def test_run_and_resume(M, tmp_path, model):
     assert len(tree(tmp_path / "ens")) > len(names)
 
 
+# The run's launches, so that a fold the loop asks for and the driver drops shows (the files would not change).
+# RUN's schedule (tests/test_main_loops.py's loop at ratio 25, tendV0 = 0.1 + 0.0598...): 151 MD steps, 30 QT
+# launches, the tagging; with sampleFreq 1, 72 outputs and 72 led / 79 folded steps; with none, the tagging's
+# output and 2 led / 149 folded steps.  A step is a force and a kick launch, a led one a drift launch more, the
+# t == 0 step its forces() first, an output two launches: 2 x 151 + led + 1 + 30 + 1 + 2 x outputs.
+RUN_LAUNCHES = {1: 550, 100000: 338}
+
+
 @pytest.mark.parametrize("sampleFreq", [1, 100000])
 def test_run_every_step_an_output_and_none(M, tmp_path, sampleFreq):
     """sampleFreq 1: an output after every MD step once tagged, no folded drift there; sampleFreq beyond the
     run: every step but the measurement's and the last is folded"""
-    run_both(M, 1, 3, dict(RUN, sampleFreq=sampleFreq), tmp_path / "ens", tmp_path / "one")
+    run_both(M, 1, 3, dict(RUN, sampleFreq=sampleFreq), tmp_path / "ens", tmp_path / "one", RUN_LAUNCHES[sampleFreq])
 
 
 # ---- 7. a member stepped on its own ends the ensemble's stepping, before anything is launched ----
