@@ -90,6 +90,9 @@ void        mdqt_destroy(mdqt_ctx* c);
 const char* mdqt_last_error(void);                           /* thread-local message            */
 int         mdqt_device_count(void);                         /* HIP devices visible             */
 const char* mdqt_version(void);
+/* bytes the library's contexts and ensembles (mdqt, mdmc, mdlc) hold now, process-wide: space 0 = device
+ * memory, 1 = pinned host memory (other: -1).  Back at its earlier value once what was created is destroyed. */
+long long   mdqt_live_bytes(int space);
 
 /* ---- derived constants (SpeedUp:79-85, :146-149, :295-297, :1181-1215) ----
  * plus the engine's state: "force_scheme", "force_slots", "force_sort", "force_skip_radius",

@@ -141,6 +141,7 @@ SIGNATURES = [
     ("mdqt_create", C.c_int, [C.POINTER(MdqtParams), C.POINTER(C.c_void_p)]),
     ("mdqt_destroy", None, [C.c_void_p]),
     ("mdqt_last_error", C.c_char_p, []),
+    ("mdqt_live_bytes", C.c_longlong, [C.c_int]),
     ("mdqt_device_count", C.c_int, []),
     ("mdqt_version", C.c_char_p, []),
     ("mdqt_get_const", C.c_double, [C.c_void_p, C.c_char_p]),

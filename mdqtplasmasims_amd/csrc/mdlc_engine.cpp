@@ -24,8 +24,8 @@ struct mdlc_ctx {
     int N0 = 0, J = 0, S = 0, B = 0;
     int dev = 0;
     hipStream_t st = nullptr;
-    double *dVx = nullptr, *dPsi = nullptr, *dTp = nullptr, *dPart = nullptr, *dEk = nullptr;
-    double* hEk = nullptr;             // pinned: a chunk of the run's EkinX values [kChunk][J]
+    DevBuf<double> dVx, dPsi, dTp, dPart, dEk;
+    PinBuf<double> hEk;                // pinned: a chunk of the run's EkinX values [kChunk][J]
     std::vector<double> hVyz;          // [J][2][N0]: V[1], V[2] (drawn by init(), never read by qstep())
     uint64_t qidx = 0;
     std::vector<std::string> dirs;     // [J]
@@ -35,11 +35,6 @@ namespace {
 
 constexpr int kMaxLaunchSteps = 8192;  // steps per launch (a few ms): a launch's length never follows tmax
 constexpr int kChunk = 512;            // output intervals between two host synchronisations of mdlc_run
-
-int fail_free(mdlc_ctx* c, const char* what) {
-    mdlc_destroy(c);
-    return set_error("%s", what);
-}
 
 int check_params(const mdlc_params* p) {
     if (p->N0 < 1) return set_error("N0 must be >= 1");
@@ -152,10 +147,6 @@ extern "C" void mdlc_destroy(mdlc_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->dev);
     if (c->st) (void)hipStreamSynchronize(c->st);
-    void* ps[] = {c->dVx, c->dPsi, c->dTp, c->dPart, c->dEk};
-    for (void* q : ps)
-        if (q) (void)hipFree(q);
-    if (c->hEk) (void)hipHostFree(c->hEk);
     if (c->st) (void)hipStreamDestroy(c->st);
     delete c;
 }
@@ -167,35 +158,32 @@ extern "C" int mdlc_create(const mdlc_params* p, mdlc_ctx** out) {
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev < 1) return set_error("no HIP device available (%s)", hipGetErrorString(e));
-    mdlc_ctx* c = new mdlc_ctx();
+    std::unique_ptr<mdlc_ctx, void (*)(mdlc_ctx*)> guard(new mdlc_ctx(), mdlc_destroy);
+    mdlc_ctx* c = guard.get();
     c->p = *p;
     c->p.saveDirectory[sizeof(c->p.saveDirectory) - 1] = 0;
     if (p->device >= 0) {
-        if (p->device >= ndev) { delete c; return set_error("device %d >= device count %d", p->device, ndev); }
+        if (p->device >= ndev) return set_error("device %d >= device count %d", p->device, ndev);
         c->dev = p->device;
     } else {
         (void)hipGetDevice(&c->dev);
     }
-    if (hipSetDevice(c->dev) != hipSuccess || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
+    if (hipSetDevice(c->dev) != hipSuccess || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess)
         return set_error("cannot create a HIP stream on device %d", p->device);
-    }
     c->N0 = p->N0;
     c->J = p->njobs;
     c->B = (p->N0 + kLCBlock - 1) / kLCBlock;
     c->S = c->B * kLCBlock;
     const size_t n = (size_t)c->J * c->S, sz = n * sizeof(double);
-    bool ok = hipMalloc(&c->dVx, sz) == hipSuccess && hipMalloc(&c->dPsi, 6 * sz) == hipSuccess &&
-              hipMalloc(&c->dTp, sz) == hipSuccess &&
-              hipMalloc(&c->dPart, (size_t)c->J * c->B * sizeof(double)) == hipSuccess &&
-              hipMalloc(&c->dEk, (size_t)kChunk * c->J * sizeof(double)) == hipSuccess;
-    if (!ok) return fail_free(c, "mdlc_create: device allocation failed");
+    bool ok = c->dVx.alloc(n) == hipSuccess && c->dPsi.alloc(6 * n) == hipSuccess && c->dTp.alloc(n) == hipSuccess &&
+              c->dPart.alloc((size_t)c->J * c->B) == hipSuccess && c->dEk.alloc((size_t)kChunk * c->J) == hipSuccess;
+    if (!ok) return set_error("mdlc_create: device allocation failed");
     // the reference's globals start at zero (V, tPart, LC3:84, :91); psi gets its value in init()
     ok = hipMemsetAsync(c->dVx, 0, sz, c->st) == hipSuccess && hipMemsetAsync(c->dPsi, 0, 6 * sz, c->st) == hipSuccess &&
          hipMemsetAsync(c->dTp, 0, sz, c->st) == hipSuccess && hipStreamSynchronize(c->st) == hipSuccess;
-    if (!ok) return fail_free(c, "mdlc_create: device initialisation failed");
-    if (hipHostMalloc((void**)&c->hEk, (size_t)kChunk * c->J * sizeof(double), hipHostMallocDefault) != hipSuccess)
-        return fail_free(c, "mdlc_create: pinned allocation failed");
+    if (!ok) return set_error("mdlc_create: device initialisation failed");
+    if (c->hEk.alloc((size_t)kChunk * c->J) != hipSuccess)
+        return set_error("mdlc_create: pinned allocation failed");
     c->hVyz.assign((size_t)c->J * 2 * c->N0, 0.);
     c->dirs.resize(c->J);
     for (int k = 0; k < c->J; ++k) {
@@ -203,7 +191,7 @@ extern "C" int mdlc_create(const mdlc_params* p, mdlc_ctx** out) {
         directory_levels(&c->p, c->p.job + (uint32_t)k, lv);
         c->dirs[k] = lv[3];
     }
-    *out = c;
+    *out = guard.release();
     return 0;
 }
 

@@ -23,25 +23,26 @@ struct mdmc_ctx {
     std::normal_distribution<double> vd;
     int dev = 0;
     hipStream_t st = nullptr;
-    double *dR = nullptr, *dV = nullptr, *dA = nullptr, *dU = nullptr, *dD = nullptr;
-    double* dRn = nullptr;          // positions of the next MDStep, pre-advanced by k_vv_step
+    mdqt::DevBuf<double> dR, dV, dA, dU, dD;
+    mdqt::DevBuf<double> dRn;       // positions of the next MDStep, pre-advanced by k_vv_step
     bool rnValid = false;           // dRn == stepPositions(dR, dV, dA): cleared by every other writer
-    double *dSlots = nullptr, *dVS = nullptr, *dPart = nullptr, *dOut = nullptr;
-    double *dTemp = nullptr, *dMom = nullptr;   // per-step observables of the run (4 / 20 per step)
-    int capTemp = 0;
-    int2* dPairs = nullptr;
-    unsigned* dHist = nullptr;
-    int* dTags = nullptr;
-    uint32_t* dMT = nullptr;
-    unsigned long long* dAcc = nullptr;
-    double* hHits = nullptr;       // pinned ring of collision entries (i, vx, vy, vz), read by k_collide
+    mdqt::DevBuf<double> dSlots, dVS, dPart, dOut;
+    mdqt::DevBuf<double> dTemp, dMom;   // per-step observables of the run (4 / 20 per step)
+    int temp_rows() const { return (int)(dTemp.capacity() / 4); }   // steps they hold
+    mdqt::DevBuf<int2> dPairs;
+    mdqt::DevBuf<unsigned> dHist;
+    mdqt::DevBuf<int> dTags;
+    mdqt::DevBuf<uint32_t> dMT;
+    mdqt::DevBuf<unsigned long long> dAcc;
+    mdqt::PinBuf<double> hHits;    // pinned ring of collision entries (i, vx, vy, vz), read by k_collide
     int hitCap = 0, hitOff = 0;
     // pinned landing area of the run's per-step read-backs: [0, 20) moment sums, [20, 24) temperature sums,
     // [24, 24 + 3 TKDE_BINS) tagged distributions (QT only), then the g(r) histogram (unsigned [nbins]);
     // evDrain is recorded behind the copies into it, so the host waits for those and not for the MD step
     // queued after them
-    double* hStage = nullptr;
-    unsigned* hStageHist = nullptr;
+    mdqt::PinBuf<unsigned> hStageMem;
+    double* hStage = nullptr;          // views of hStageMem: the doubles,
+    unsigned* hStageHist = nullptr;    // the histogram behind them
     hipEvent_t evDrain = nullptr;
     std::string saveDir;
     // QT tagging variants (qt_model 1..3)
@@ -50,11 +51,11 @@ struct mdmc_ctx {
     int qtRatio = 0, pumpSteps = 0;
     mdqt::QTConst qc;
     mdqt::FastTab ftab;
-    mdqt::FastTab* dFTab = nullptr;   // [2]: by state, by lane (the same for the pumping models)
-    double* dPsi = nullptr;        // [24][S] component-major (re0, im0, re1, ...), as include/mdqt.h's engine
-    double* dTp = nullptr;         // [S] tPart
-    int* dFlags = nullptr;
-    double *dKdePart = nullptr, *dKde = nullptr;
+    mdqt::DevBuf<mdqt::FastTab> dFTab;   // [2]: by state, by lane (the same for the pumping models)
+    mdqt::DevBuf<double> dPsi;     // [24][S] component-major (re0, im0, re1, ...), as include/mdqt.h's engine
+    mdqt::DevBuf<double> dTp;      // [S] tPart
+    mdqt::DevBuf<int> dFlags;
+    mdqt::DevBuf<double> dKdePart, dKde;
     uint64_t qidx = 0;
     unsigned short x48[3] = {0x330E, 0xABCD, 0x1234};   // drand48's default state (no srand48 in QTT)
 };
@@ -66,10 +67,10 @@ struct mdmc_ensemble {
     std::vector<mdmc_ctx*> jobs;
     int dev = 0;
     hipStream_t stream = nullptr;
-    mdqt::MCArgs* dArgs = nullptr;     // [J] the blocks the next launch reads
-    mdqt::MCArgs* hArgs = nullptr;     // pinned [2][J]: the blocks of a full chunk, of a call's last chunk
-    uint32_t* hMT = nullptr;           // pinned [J][625]: the chains' mt19937 states coming back
-    unsigned long long* hAcc = nullptr;   // pinned [J]
+    mdqt::DevBuf<mdqt::MCArgs> dArgs;  // [J] the blocks the next launch reads
+    mdqt::PinBuf<mdqt::MCArgs> hArgs;  // pinned [2][J]: the blocks of a full chunk, of a call's last chunk
+    mdqt::PinBuf<uint32_t> hMT;        // pinned [J][625]: the chains' mt19937 states coming back
+    mdqt::PinBuf<unsigned long long> hAcc;   // pinned [J]
     bool timing = false;
     mdqt::LaunchTimer annealTimer;     // the anneal launches' own timestamps
     // wall time of the last run's stages (ms, with timing on): anneal, pre-record MD, QT pump, recorded MD,
@@ -81,8 +82,8 @@ struct mdmc_ensemble {
     unsigned long long mdLaunches = 0; // kernel launches the batched path has issued
     // device blocks of a stretch, one allocation: N3Args [2][J], VVArgs [2][J] (the two buffer parities of
     // the collisionless step), MDObsArgs [J], MDKdeXArgs [J], then VVArgs [J] of a step with collision draws
-    char* dBlocks = nullptr;
-    mdqt::N3Args* dN3 = nullptr;
+    mdqt::DevBuf<char> dBlocks;
+    mdqt::N3Args* dN3 = nullptr;       // views of dBlocks, these five
     mdqt::VVArgs* dVV = nullptr;
     mdqt::MDObsArgs* dObs = nullptr;
     mdqt::MDKdeXArgs* dKdeX = nullptr;
@@ -100,11 +101,11 @@ struct mdmc_ensemble {
     // ---- batched QT (mdmc_ensemble.cpp, "batched QT"; members with qt_model 1..3 only) ----
     static constexpr int kDistSlots = 4;   // recorded steps whose X distributions may be on their way at once
     unsigned long long qtLaunches = 0; // kernel launches the batched QT, tagging and distribution paths have issued
-    char* dQt = nullptr;               // [J] SubstepArgs of a QT chunk, or PumpTagArgs of the tagging: the next launch's
+    mdqt::DevBuf<char> dQt;            // [J] SubstepArgs of a QT chunk, or PumpTagArgs of the tagging: the next launch's
     mdqt::PinRing qtRing;              // their way over, in stream order
-    double* dDist = nullptr;           // [kDistSlots][J][TKDE_BINS]: the reduce's rows
-    double* hDist = nullptr;           // pinned, the same shape: one copy per slot brings all members' rows
-    double* hMom = nullptr;            // pinned [J][kTagMomentSums]: mdmc_ensemble_tagged_moments_qt's sums
+    mdqt::DevBuf<double> dDist;        // [kDistSlots][J][TKDE_BINS]: the reduce's rows
+    mdqt::PinBuf<double> hDist;        // pinned, the same shape: one copy per slot brings all members' rows
+    mdqt::PinBuf<double> hMom;         // pinned [J][kTagMomentSums]: mdmc_ensemble_tagged_moments_qt's sums
     hipEvent_t evDist[kDistSlots] = {};   // behind the copy into a slot of hDist
     mdqt::LaunchTimer qtTimer, distTimer;   // the batched QT launches'; the distribution's chunk kernel's
 };

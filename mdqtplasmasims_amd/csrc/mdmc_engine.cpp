@@ -22,11 +22,6 @@ using namespace mdqt;
 
 namespace {
 
-int fail_free(mdmc_ctx* c, const char* what) {
-    mdmc_destroy(c);
-    return set_error("%s", what);
-}
-
 double sqrt_threshold(double rc) {   // smallest x with sqrt(x) >= rc: sqrt(r2) < rc iff r2 < x
     double x = rc * rc;
     while (x > 0 && sqrt(x) >= rc) x = nextafter(x, 0.);
@@ -108,13 +103,6 @@ extern "C" void mdmc_destroy(mdmc_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->dev);
     if (c->st) (void)hipStreamSynchronize(c->st);
-    void* ps[] = {c->dR, c->dV, c->dA, c->dRn, c->dU, c->dD, c->dSlots, c->dVS, c->dPart, c->dOut,
-                  c->dTemp, c->dMom, c->dPairs, c->dHist, c->dTags, c->dMT, c->dAcc,
-                  c->dFTab, c->dPsi, c->dTp, c->dFlags, c->dKdePart, c->dKde};
-    for (void* q : ps)
-        if (q) (void)hipFree(q);
-    if (c->hHits) (void)hipHostFree(c->hHits);
-    if (c->hStage) (void)hipHostFree(c->hStage);
     if (c->evDrain) (void)hipEventDestroy(c->evDrain);
     if (c->st) (void)hipStreamDestroy(c->st);
     delete c;
@@ -132,19 +120,18 @@ extern "C" int mdmc_create(const mdmc_params* p, mdmc_ctx** out) {
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev < 1) return set_error("no HIP device available (%s)", hipGetErrorString(e));
-    mdmc_ctx* c = new mdmc_ctx();
+    std::unique_ptr<mdmc_ctx, void (*)(mdmc_ctx*)> guard(new mdmc_ctx(), mdmc_destroy);
+    mdmc_ctx* c = guard.get();
     c->p = *p;
     c->p.saveDirectory[sizeof(c->p.saveDirectory) - 1] = 0;
     if (p->device >= 0) {
-        if (p->device >= ndev) { delete c; return set_error("device %d >= device count %d", p->device, ndev); }
+        if (p->device >= ndev) return set_error("device %d >= device count %d", p->device, ndev);
         c->dev = p->device;
     } else {
         (void)hipGetDevice(&c->dev);
     }
-    if (hipSetDevice(c->dev) != hipSuccess || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
+    if (hipSetDevice(c->dev) != hipSuccess || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess)
         return set_error("cannot create a HIP stream on device %d", p->device);
-    }
     const int N = p->N;
     c->N = N;
     c->S = ((N + 63) / 64) * 64;
@@ -160,20 +147,20 @@ extern "C" int mdmc_create(const mdmc_params* p, mdmc_ctx** out) {
     c->npairs = c->nt * (c->nt + 1) / 2;
     const size_t S = c->S, sz = S * sizeof(double);
     const int nblk = autocorr_blocks(N);
-    bool ok = hipMalloc(&c->dR, 3 * sz) == hipSuccess && hipMalloc(&c->dV, 3 * sz) == hipSuccess &&
-              hipMalloc(&c->dA, 3 * sz) == hipSuccess && hipMalloc(&c->dRn, 3 * sz) == hipSuccess &&
-              hipMalloc(&c->dU, sz) == hipSuccess && hipMalloc(&c->dD, sz) == hipSuccess &&
-              hipMalloc(&c->dSlots, 3 * sz * c->nt) == hipSuccess &&
-              hipMalloc(&c->dVS, (size_t)3 * N * c->T * sizeof(double)) == hipSuccess &&
-              hipMalloc(&c->dPart, (size_t)nblk * 4 * c->T * sizeof(double)) == hipSuccess &&
+    bool ok = c->dR.alloc(3 * S) == hipSuccess && c->dV.alloc(3 * S) == hipSuccess &&
+              c->dA.alloc(3 * S) == hipSuccess && c->dRn.alloc(3 * S) == hipSuccess &&
+              c->dU.alloc(S) == hipSuccess && c->dD.alloc(S) == hipSuccess &&
+              c->dSlots.alloc(3 * S * c->nt) == hipSuccess &&
+              c->dVS.alloc((size_t)3 * N * c->T) == hipSuccess &&
+              c->dPart.alloc((size_t)nblk * 4 * c->T) == hipSuccess &&
               // dOut: the autocorrelations [4][T], the temperature sums and k_tag_moments' sums
-              hipMalloc(&c->dOut, (size_t)std::max(4 * c->T, kTagMomentSums) * sizeof(double)) == hipSuccess &&
-              hipMalloc(&c->dPairs, (size_t)c->npairs * sizeof(int2)) == hipSuccess &&
-              hipMalloc(&c->dHist, (size_t)(c->nbins > 0 ? c->nbins : 1) * sizeof(unsigned)) == hipSuccess &&
-              hipMalloc(&c->dTags, (size_t)4 * N * sizeof(int)) == hipSuccess &&
-              hipMalloc(&c->dMT, 625 * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc(&c->dAcc, sizeof(unsigned long long)) == hipSuccess;
-    if (!ok) return fail_free(c, "mdmc_create: device allocation failed");
+              c->dOut.alloc((size_t)std::max(4 * c->T, kTagMomentSums)) == hipSuccess &&
+              c->dPairs.alloc((size_t)c->npairs) == hipSuccess &&
+              c->dHist.alloc((size_t)(c->nbins > 0 ? c->nbins : 1)) == hipSuccess &&
+              c->dTags.alloc((size_t)4 * N) == hipSuccess &&
+              c->dMT.alloc(625) == hipSuccess &&
+              c->dAcc.alloc(1) == hipSuccess;
+    if (!ok) return set_error("mdmc_create: device allocation failed");
     // the reference's globals start at zero (R, V, A, U; MCMD:110-123)
     ok = hipMemsetAsync(c->dR, 0, 3 * sz, c->st) == hipSuccess && hipMemsetAsync(c->dV, 0, 3 * sz, c->st) == hipSuccess &&
          hipMemsetAsync(c->dA, 0, 3 * sz, c->st) == hipSuccess && hipMemsetAsync(c->dU, 0, sz, c->st) == hipSuccess &&
@@ -185,21 +172,21 @@ extern "C" int mdmc_create(const mdmc_params* p, mdmc_ctx** out) {
         for (int J = I; J < c->nt; ++J) h.push_back(make_int2(I, J));
     ok = ok && hipMemcpyAsync(c->dPairs, h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice, c->st) == hipSuccess &&
          hipStreamSynchronize(c->st) == hipSuccess;
-    if (!ok) return fail_free(c, "mdmc_create: device initialisation failed");
+    if (!ok) return set_error("mdmc_create: device initialisation failed");
     c->hitCap = 4 * 65536;
-    if (hipHostMalloc((void**)&c->hHits, (size_t)c->hitCap * 4 * sizeof(double), hipHostMallocDefault) != hipSuccess)
-        return fail_free(c, "mdmc_create: pinned allocation failed");
+    if (c->hHits.alloc((size_t)c->hitCap * 4) != hipSuccess)
+        return set_error("mdmc_create: pinned allocation failed");
     const size_t stageD = 24 + (p->qt_model != 0 ? (size_t)3 * TKDE_BINS : 0);
-    if (hipHostMalloc((void**)&c->hStage, stageD * sizeof(double) + (size_t)(c->nbins > 0 ? c->nbins : 1) * sizeof(unsigned),
-                      hipHostMallocDefault) != hipSuccess ||
+    if (c->hStageMem.alloc(2 * stageD + (size_t)(c->nbins > 0 ? c->nbins : 1)) != hipSuccess ||
         hipEventCreateWithFlags(&c->evDrain, hipEventDisableTiming) != hipSuccess)
-        return fail_free(c, "mdmc_create: pinned allocation failed");
-    c->hStageHist = reinterpret_cast<unsigned*>(c->hStage + stageD);
+        return set_error("mdmc_create: pinned allocation failed");
+    c->hStage = reinterpret_cast<double*>(c->hStageMem.get());
+    c->hStageHist = c->hStageMem + 2 * stageD;
     c->saveDir = c->p.saveDirectory;
     if (p->qt_model != 0) {
         // the QT tagging program's constants: 408 (QTT408Linear:115-121) / 422 (QTT422Linear:115-121)
         const int m = p->qt_model;
-        if (m < 1 || m > 3) return fail_free(c, "mdmc_create: qt_model must be 0 .. 3");
+        if (m < 1 || m > 3) return set_error("mdmc_create: qt_model must be 0 .. 3");
         const double nn = p->n;
         c->qt = m;
         c->gamToE = m == 3 ? 174.07 * .894 / sqrt(nn) : 174.07 / sqrt(nn);
@@ -209,26 +196,24 @@ extern "C" int mdmc_create(const mdmc_params* p, mdmc_ctx** out) {
         c->decayRatio = m == 3 ? 0.0753 : 0.0617;
         const double tpump = p->tpumpreal * 813490 * sqrt(nn);
         c->pumpSteps = (int)round(tpump / p->timeStep);
-        if (c->qtRatio < 1) return fail_free(c, "mdmc_create: QT substep ratio < 1");
+        if (c->qtRatio < 1) return set_error("mdmc_create: QT substep ratio < 1");
         build_pump_program(m, p->detuning, p->Om, c->dtQ, c->gamToE, c->pv2q, c->decayRatio, p->seed, p->job, c->qc,
                            c->ftab);
         const int nch = (N + 255) / 256;
-        ok = hipMalloc(&c->dFTab, 2 * sizeof(FastTab)) == hipSuccess &&
-             hipMalloc(&c->dPsi, (size_t)24 * S * sizeof(double)) == hipSuccess &&
-             hipMalloc(&c->dTp, (size_t)S * sizeof(double)) == hipSuccess &&
-             hipMalloc(&c->dFlags, sizeof(int)) == hipSuccess &&
-             hipMalloc(&c->dKdePart, (size_t)nch * 3 * TKDE_BINS * sizeof(double)) == hipSuccess &&
-             hipMalloc(&c->dKde, (size_t)3 * TKDE_BINS * sizeof(double)) == hipSuccess;
-        if (!ok) return fail_free(c, "mdmc_create: QT allocation failed");
+        ok = c->dFTab.alloc(2) == hipSuccess && c->dPsi.alloc((size_t)24 * S) == hipSuccess &&
+             c->dTp.alloc(S) == hipSuccess && c->dFlags.alloc(1) == hipSuccess &&
+             c->dKdePart.alloc((size_t)nch * 3 * TKDE_BINS) == hipSuccess &&
+             c->dKde.alloc((size_t)3 * TKDE_BINS) == hipSuccess;
+        if (!ok) return set_error("mdmc_create: QT allocation failed");
         ok = hipMemcpyAsync(c->dFTab, &c->ftab, sizeof(FastTab), hipMemcpyHostToDevice, c->st) == hipSuccess &&
              hipMemcpyAsync(c->dFTab + 1, &c->ftab, sizeof(FastTab), hipMemcpyHostToDevice, c->st) == hipSuccess &&
              hipMemsetAsync(c->dPsi, 0, (size_t)24 * S * sizeof(double), c->st) == hipSuccess &&
              hipMemsetAsync(c->dTp, 0, (size_t)S * sizeof(double), c->st) == hipSuccess &&
              hipMemsetAsync(c->dFlags, 0, sizeof(int), c->st) == hipSuccess &&
              hipStreamSynchronize(c->st) == hipSuccess;
-        if (!ok) return fail_free(c, "mdmc_create: QT initialisation failed");
+        if (!ok) return set_error("mdmc_create: QT initialisation failed");
     }
-    *out = c;
+    *out = guard.release();
     return 0;
 }
 

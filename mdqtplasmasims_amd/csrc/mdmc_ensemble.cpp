@@ -35,9 +35,9 @@ int md_blocks_create(mdmc_ensemble* e) {
     const size_t n3 = 2 * J * sizeof(N3Args), vv = 2 * J * sizeof(VVArgs), ob = J * sizeof(MDObsArgs);
     const size_t kx = J * sizeof(MDKdeXArgs);
     e->hdrBytes = n3 + vv + ob + kx;
-    if (hipMalloc((void**)&e->dBlocks, e->hdrBytes + J * sizeof(VVArgs)) != hipSuccess)
+    if (e->dBlocks.alloc(e->hdrBytes + J * sizeof(VVArgs)) != hipSuccess)
         return set_error("mdmc_ensemble_create: allocating the MD argument blocks of %zu jobs failed", J);
-    e->dN3 = reinterpret_cast<N3Args*>(e->dBlocks);
+    e->dN3 = reinterpret_cast<N3Args*>(e->dBlocks.get());
     e->dVV = reinterpret_cast<VVArgs*>(e->dBlocks + n3);
     e->dObs = reinterpret_cast<MDObsArgs*>(e->dBlocks + n3 + vv);
     e->dKdeX = reinterpret_cast<MDKdeXArgs*>(e->dBlocks + n3 + vv + ob);
@@ -66,10 +66,9 @@ constexpr int kQtSlots = 8;      // QT chunks / taggings whose blocks may be on 
 
 int qt_blocks_create(mdmc_ensemble* e) {
     const size_t J = e->jobs.size();
-    const size_t dist = (size_t)mdmc_ensemble::kDistSlots * J * TKDE_BINS * sizeof(double);
-    if (hipMalloc((void**)&e->dQt, J * sizeof(SubstepArgs)) != hipSuccess || hipMalloc((void**)&e->dDist, dist) != hipSuccess ||
-        hipHostMalloc((void**)&e->hDist, dist, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&e->hMom, J * kTagMomentSums * sizeof(double), hipHostMallocDefault) != hipSuccess)
+    const size_t dist = (size_t)mdmc_ensemble::kDistSlots * J * TKDE_BINS;
+    if (e->dQt.alloc(J * sizeof(SubstepArgs)) != hipSuccess || e->dDist.alloc(dist) != hipSuccess ||
+        e->hDist.alloc(dist) != hipSuccess || e->hMom.alloc(J * kTagMomentSums) != hipSuccess)
         return set_error("mdmc_ensemble_create: allocating the QT blocks and distribution rings of %zu jobs failed", J);
     if (e->qtRing.create(J * sizeof(SubstepArgs), kQtSlots, hipEventDisableTiming)) return -1;
     for (hipEvent_t& ev : e->evDist) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -136,7 +135,7 @@ int mdmc::ensemble_md_begin(mdmc_ensemble* e) {
     VVArgs* vv = reinterpret_cast<VVArgs*>(h + 2 * J * sizeof(N3Args));
     MDObsArgs* ob = reinterpret_cast<MDObsArgs*>(h + 2 * J * (sizeof(N3Args) + sizeof(VVArgs)));
     MDKdeXArgs* kx = reinterpret_cast<MDKdeXArgs*>(ob + J);
-    e->obsCap = e->jobs[0]->capTemp;
+    e->obsCap = e->jobs[0]->temp_rows();
     for (size_t k = 0; k < J; ++k) {
         mdmc_ctx* c = e->jobs[k];
         if (!c->rnValid) {                                                                    // :452-467
@@ -150,7 +149,7 @@ int mdmc::ensemble_md_begin(mdmc_ensemble* e) {
             mdmc::vv_args(c, nullptr, 0, vv[par * J + k]);
         }                                         // two swaps: the member's pointers are back
         obs_args(c, false, ob[k], kx[k]);
-        e->obsCap = std::min(e->obsCap, c->capTemp);
+        e->obsCap = std::min(e->obsCap, c->temp_rows());
         e->coll[k] = c->p.timeStep * c->collisionFreq > 0;
         e->skip[k] = 0;
     }
@@ -293,7 +292,7 @@ int mdmc::ensemble_qt_steps(mdmc_ensemble* e, int n) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (e->timing && e->qtTimer.take(&e0, &e1)) return -1;
         // a[0] picks the instance (the slot is read by the copy only, and not rewritten before take() hands it out again)
-        HIPCHK(launch_substeps_pump_ens(reinterpret_cast<const SubstepArgs*>(e->dQt), a[0], (int)J, max_n, e->jobs[0]->dFTab,
+        HIPCHK(launch_substeps_pump_ens(reinterpret_cast<const SubstepArgs*>(e->dQt.get()), a[0], (int)J, max_n, e->jobs[0]->dFTab,
                                         e->stream, e0, e1));
         ++e->qtLaunches;
         n -= m;
@@ -316,7 +315,7 @@ int mdmc::ensemble_qt_tag(mdmc_ensemble* e) {                      // tagParticl
         max_n = std::max(max_n, c->N);
     }
     if (e->qtRing.send(slot, e->dQt, J * sizeof(PumpTagArgs), e->stream)) return -1;
-    HIPCHK(launch_tag_spin_up_ens(reinterpret_cast<const PumpTagArgs*>(e->dQt), (int)J, max_n, e->stream));
+    HIPCHK(launch_tag_spin_up_ens(reinterpret_cast<const PumpTagArgs*>(e->dQt.get()), (int)J, max_n, e->stream));
     ++e->qtLaunches;
     return 0;
 }
@@ -421,7 +420,7 @@ extern "C" int mdmc_ensemble_tagged_moments_qt(mdmc_ensemble* e, double* out4, d
                               hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     for (size_t k = 0; k < J; ++k) mdmc::moments_qt_from_sums(e->hMom + kTagMomentSums * k, out4 + 4 * k);
-    if (distX) std::copy_n(e->hDist, J * TKDE_BINS, distX);
+    if (distX) std::copy_n(e->hDist.get(), J * TKDE_BINS, distX);
     return 0;
 }
 
@@ -447,23 +446,10 @@ extern "C" void mdmc_ensemble_destroy(mdmc_ensemble* e) {
     (void)hipSetDevice(e->dev);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (size_t k = e->jobs.size(); k-- > 0;) mdmc_destroy(e->jobs[k]);
-    if (e->dBlocks) (void)hipFree(e->dBlocks);
-    e->hdrRing.destroy();
-    e->vvRing.destroy();
-    e->qtRing.destroy();
-    if (e->dQt) (void)hipFree(e->dQt);
-    if (e->dDist) (void)hipFree(e->dDist);
-    if (e->hDist) (void)hipHostFree(e->hDist);
-    if (e->hMom) (void)hipHostFree(e->hMom);
     for (hipEvent_t ev : e->evDist)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evMember) (void)hipEventDestroy(ev);
-    for (LaunchTimer* t : {&e->annealTimer, &e->forceTimer, &e->vvTimer, &e->qtTimer, &e->distTimer}) t->destroy();
     if (e->evEns) (void)hipEventDestroy(e->evEns);
-    if (e->dArgs) (void)hipFree(e->dArgs);
-    if (e->hArgs) (void)hipHostFree(e->hArgs);
-    if (e->hMT) (void)hipHostFree(e->hMT);
-    if (e->hAcc) (void)hipHostFree(e->hAcc);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -495,10 +481,8 @@ extern "C" int mdmc_ensemble_create(const mdmc_params* p, int njobs, mdmc_ensemb
     HIPCHK(hipSetDevice(e->dev));
     const size_t J = (size_t)njobs;
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&e->dArgs, J * sizeof(MCArgs)) != hipSuccess ||
-        hipHostMalloc((void**)&e->hArgs, 2 * J * sizeof(MCArgs), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&e->hMT, J * 625 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&e->hAcc, J * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
+        e->dArgs.alloc(J) != hipSuccess || e->hArgs.alloc(2 * J) != hipSuccess ||
+        e->hMT.alloc(J * 625) != hipSuccess || e->hAcc.alloc(J) != hipSuccess)
         return set_error("mdmc_ensemble_create: allocating the argument blocks of %d jobs failed", njobs);
     if (md_blocks_create(e.get())) return -1;
     if (e->jobs[0]->qt && qt_blocks_create(e.get())) return -1;

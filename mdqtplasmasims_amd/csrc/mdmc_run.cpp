@@ -84,13 +84,10 @@ int write_pair_corr(Run& r, int stepNum) {
 
 // per-step observables buffered on the device, written when a stage ends
 int ensure_step_buffers(mdmc_ctx* c, int steps) {
-    if (steps <= c->capTemp) return 0;
-    if (c->dTemp) HIPCHK(hipFree(c->dTemp));
-    if (c->dMom) HIPCHK(hipFree(c->dMom));
-    c->dTemp = nullptr; c->dMom = nullptr;
-    HIPCHK(hipMalloc(&c->dTemp, (size_t)steps * 4 * sizeof(double)));
-    HIPCHK(hipMalloc(&c->dMom, (size_t)steps * 20 * sizeof(double)));
-    c->capTemp = steps;
+    if (steps <= c->temp_rows()) return 0;
+    c->dTemp.reset();                                  // temp_rows() speaks for both: dTemp goes first and comes last
+    HIPCHK(c->dMom.alloc((size_t)steps * 20));
+    HIPCHK(c->dTemp.alloc((size_t)steps * 4));
     return 0;
 }
 
@@ -248,7 +245,7 @@ int stage_anisotropy(Run& r) {
         mdmc_ctx* c = r.c[j];
         c->addLaserForce = 1;
         c->collisionFreq = 0;
-        if (ensure_step_buffers(c, std::max(nest, c->capTemp))) return -1;
+        if (ensure_step_buffers(c, std::max(nest, c->temp_rows()))) return -1;
     }
     if (stage_md_temp_axes(r, nest, "TemperaturesAlongAxesDuringForcePeriod.dat")) return -1;
     for (int j = 0; j < r.J; ++j) r.c[j]->addLaserForce = 0;     // :1155-1165

@@ -9,7 +9,7 @@ using namespace mdqt;
 
 int PinRing::create(size_t bytes, int slots, unsigned event_flags) {
     slot_bytes = bytes;
-    if (hipHostMalloc((void**)&base, bytes * (size_t)slots, hipHostMallocDefault) != hipSuccess)
+    if (base.alloc(bytes * (size_t)slots) != hipSuccess)
         return set_error("pinned allocation of %d argument slots of %zu bytes failed", slots, bytes);
     busy.assign((size_t)slots, 0);
     for (int i = 0; i < slots; ++i) {
@@ -39,9 +39,8 @@ int PinRing::send(int idx, void* dst, size_t bytes, hipStream_t s) {
 }
 
 void PinRing::destroy() {
-    if (base) (void)hipHostFree(base);
+    base.reset();
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    base = nullptr;
     ev.clear();
     busy.clear();
 }

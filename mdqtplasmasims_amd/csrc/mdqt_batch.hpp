@@ -8,6 +8,8 @@
 
 #include <vector>
 
+#include "mdqt_devbuf.hpp"
+
 namespace mdqt {
 
 constexpr int kEnsembleMaxJobs = 1024;   // njobs of every ensemble: 1 .. kEnsembleMaxJobs
@@ -16,7 +18,7 @@ constexpr int kEnsembleMaxJobs = 1024;   // njobs of every ensemble: 1 .. kEnsem
 // hipMemcpyAsync reads it in stream order, and the event recorded behind the copy says when the slot may be
 // written again (the host queues far ahead of the device, so a slot is not free when the call returns).
 struct PinRing {
-    char* base = nullptr;
+    PinBuf<char> base;
     size_t slot_bytes = 0;
     int next = 0;
     std::vector<hipEvent_t> ev;        // one per slot
@@ -26,10 +28,11 @@ struct PinRing {
     int take(char** slot, int* idx);   // the next slot, once the copy that last read it has run
     int send(int idx, void* dst, size_t bytes, hipStream_t s);   // one copy of the slot, its event behind it
     void destroy();
+    ~PinRing() { destroy(); }
 
     // blocks that seldom change: h goes to dst (through a slot) when it differs from `held`, what dst holds
     template <class T>
-    int send_if_changed(const std::vector<T>& h, std::vector<T>& held, T* dst, hipStream_t s) {
+    int send_if_changed(const std::vector<T>& h, std::vector<T>& held, void* dst, hipStream_t s) {
         const size_t bytes = h.size() * sizeof(T);
         if (h.empty() || (h.size() == held.size() && !memcmp(h.data(), held.data(), bytes))) return 0;
         char* slot = nullptr;
@@ -54,6 +57,7 @@ struct LaunchTimer {
     int stats(double* v);
     void reset() { used = 0; }
     void destroy();
+    ~LaunchTimer() { destroy(); }
 };
 
 }  // namespace mdqt

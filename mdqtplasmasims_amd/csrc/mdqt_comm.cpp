@@ -91,12 +91,7 @@ extern "C" int mdqt_allreduce_sum(mdqt_ctx* s, double* buf, size_t n) {
     if (s->p.world_size == 1 || n == 0) return 0;
     if (!s->comm) return set_error("mdqt_allreduce_sum: no communicator (mdqt_comm_init)");
     HIPCHK(hipSetDevice(s->dev));
-    if (n > s->dCommCap) {
-        if (s->dComm) HIPCHK(hipFree(s->dComm));
-        s->dComm = nullptr;
-        HIPCHK(hipMalloc(&s->dComm, n * sizeof(double)));
-        s->dCommCap = n;
-    }
+    HIPCHK(s->dComm.reserve(n));
     HIPCHK(hipMemcpyAsync(s->dComm, buf, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
     NCCLCHK(ncclAllReduce(s->dComm, s->dComm, n, ncclDouble, ncclSum, s->comm, s->stream));
     HIPCHK(hipMemcpyAsync(buf, s->dComm, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -149,8 +144,8 @@ int mdqt::local_reduce(mdqt_ctx* s) {
         HIPCHK(hipStreamSynchronize(q->stream));
     }
     HIPCHK(hipSetDevice(s->dev));
-    if (!s->dPeerParts) HIPCHK(hipMalloc((void**)&s->dPeerParts, W * sizeof(double*)));
-    HIPCHK(hipMemcpy((void*)s->dPeerParts, h.data(), W * sizeof(double*), hipMemcpyHostToDevice));
+    if (!s->dPeerParts) HIPCHK(s->dPeerParts.alloc((size_t)W));
+    HIPCHK(hipMemcpy(s->dPeerParts, h.data(), W * sizeof(double*), hipMemcpyHostToDevice));
     HIPCHK(launch_sum_rank_chunks(s->dPeerParts, W, s->p.rank, s->S, s->dF, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     s->rs_pending = false;

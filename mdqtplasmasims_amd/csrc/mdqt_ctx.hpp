@@ -15,6 +15,7 @@
 
 #include "../../include/mdqt.h"
 #include "mdqt_batch.hpp"
+#include "mdqt_devbuf.hpp"
 #include "mdqt_internal.hpp"
 #include "mdqt_main_loops.hpp"
 #include "mdqt_writer.hpp"
@@ -49,26 +50,24 @@ struct mdqt_ctx {
     double vel[mdqt::NBINS];
     // sizes
     int N = 0, S = 0, lo = 0, hi = 0, nloc = 0;
-    int capS = 0, capNseg = 0, nseg = 1, seglen = 1;
+    int capS = 0, nseg = 1, seglen = 1;
     // device
     int dev = 0;
     hipStream_t own = nullptr, stream = nullptr;
-    double *dR = nullptr, *dV = nullptr, *dF = nullptr, *dFpart = nullptr, *dPsi = nullptr,
-           *dTp = nullptr, *dScr = nullptr, *dKde = nullptr, *dUrow = nullptr;
-    double* dUpart = nullptr;      // potential-row partials of its own (small systems, world 1)
+    mdqt::DevBuf<double> dR, dV, dF, dFpart, dPsi, dTp, dScr, dKde, dUrow;
+    mdqt::DevBuf<double> dUpart;   // potential-row partials of its own (small systems, world 1)
     int n3_potential = 1;          // option "potential_n3": 1 = Newton-3 tiles where the forces use them
     int n3b_pairs = 1;             // option "force_n3b_pairs": the paired-wave block kernel (k_pairs_n3b_pw); A/B round 6
                                    // (r06e): N = 1M force call -4.3 %, C5 -2.3 %, C3 -2.3 %
     int pot_plan = 1;              // option "potential_plan": 1 = Epotential on the blocks takes the force call's
                                    // plan (skips, sub-tile groups, error-bounded forms); 0 = every pair to L/2 exactly
-    size_t capUpart = 0;
-    double* dPack = nullptr;       // output()'s per-ion columns [4][S] (world 1)
+    mdqt::DevBuf<double> dPack;    // output()'s per-ion columns [4][S] (world 1)
     int kdeChunks = 0;
     mdqt::LaneTab tab;                   // lane-per-state QT kernel tables (host copy)
-    mdqt::LaneTab* dTab = nullptr;       // device copy (uploaded once at create)
+    mdqt::DevBuf<mdqt::LaneTab> dTab;    // device copy (uploaded once at create)
     mdqt::FastTab ftab;                  // qt_math 2 row tables by state (host copy)
     mdqt::FastTab ftabL;                 // the same by lane of the lane-per-state kernel (model 0: kStateOfLane0)
-    mdqt::FastTab* dFTab = nullptr;      // device copies [2]: by state, by lane
+    mdqt::DevBuf<mdqt::FastTab> dFTab;   // device copies [2]: by state, by lane
     int substep_mode = 0;          // 0 auto, 1 thread-per-ion, 2 lane-per-state
     int force_variant = 1;         // 0 exact reference operations, 1 fast reciprocal form
     int qt_math = 2;               // 0 exact reference operations, 1 FMA-contracted, 2 reassociated (option "qt_math")
@@ -78,9 +77,8 @@ struct mdqt_ctx {
     bool use_n3 = false;
     bool use_n3b = false;          // Newton-3 block pairs (k_pairs_n3b): large N, one GPU or sharded
     mdqt::N3BArgs n3b;                   // its configuration (pointers and pair constants filled per call)
-    double* dSlots = nullptr;      // its slots [nd + R][3][Npad]
-    size_t capSlots = 0;
-    double* dFr = nullptr;         // sharded n3b: this rank's dense partial forces [world][3][S]
+    mdqt::DevBuf<double> dSlots;   // its slots [nd + R][3][Npad]
+    mdqt::DevBuf<double> dFr;      // sharded n3b: this rank's dense partial forces [world][3][S]
     // spatial order of the n3b scheme (mdqt_sort.hip; option "force_sort", default on)
     int sort_mode = 1;             // 0 off, 1 sorted + tile-pair skipping, 2 sorted, nothing skipped (tests)
     int ax1_mode = 1;              // option "force_ax1": the one-axis per-pair image instance (1, auto) or not (0)
@@ -96,9 +94,9 @@ struct mdqt_ctx {
     // exceeds eps gets the exact sum over those tile pairs added to its rows (k_tail_fix) — so every
     // ion meets eps whatever the configuration; the host widens r_t when that happened (tail_check)
     int tail_mode = 1;
-    double* dTail = nullptr;       // [4T]: the per-sub-tile sums of the current call
-    unsigned long long* dTailSt = nullptr;   // [8]: k_tail_max's running maxima and counters
-    int* dTailList = nullptr;      // [T]: this call's tiles over eps (this rank's)
+    mdqt::DevBuf<double> dTail;    // [4T]: the per-sub-tile sums of the current call
+    mdqt::DevBuf<unsigned long long> dTailSt;   // [8]: k_tail_max's running maxima and counters
+    mdqt::DevBuf<int> dTailList;   // [T]: this call's tiles over eps (this rank's)
     double tail_scale = 1.;        // r_t from 2 tail_scale B(r) <= eps: raised when a call exceeded eps
     unsigned long long tail_seen = 0;   // tiles over eps the host has reacted to
     int tail_warned = 0;                // stderr lines printed by tail_check
@@ -131,20 +129,18 @@ struct mdqt_ctx {
     // default: where the tail is exact (C3 / C5) the per-ion bound is then 1.5e-12, not 1's 5e-13
     int form_mode = 2;
     mutable double form_key[6][6] = {}, form_val[6][2] = {};   // tier_radius memo by level (N, L, lDeb, k, tail_exp, scale)
-    uint32_t* dKeys = nullptr;     // [2][N] Hilbert keys, sorted keys
-    int* dIon = nullptr;           // [2][N] identity, sorted index -> ion
-    void* dSortTmp = nullptr;
-    size_t sortTmpBytes = 0;
-    double* dRs = nullptr;         // [3][Npad] positions in sorted order
-    double* dBoxes = nullptr;      // [12][T] tile boxes, raw coordinate bounds
-    double* dSubBoxes = nullptr;   // [6][4T] the 16-ion sub-tiles' boxes (the block kernel's sub-tile groups)
-    uint2* dPlan = nullptr;        // [(Phi - Plo) nd][kN3BBlock^2] the block kernel's tile-pair words (k_n3b_plan)
+    mdqt::DevBuf<uint32_t> dKeys;  // [2][N] Hilbert keys, sorted keys
+    mdqt::DevBuf<int> dIon;        // [2][N] identity, sorted index -> ion
+    mdqt::DevBuf<char> dSortTmp;   // the radix sort's scratch (its capacity: the bytes)
+    mdqt::DevBuf<double> dRs;      // [3][Npad] positions in sorted order
+    mdqt::DevBuf<double> dBoxes;   // [12][T] tile boxes, raw coordinate bounds
+    mdqt::DevBuf<double> dSubBoxes;   // [6][4T] the 16-ion sub-tiles' boxes (the block kernel's sub-tile groups)
+    mdqt::DevBuf<uint2> dPlan;     // [(Phi - Plo) nd][kN3BBlock^2] the block kernel's tile-pair words (k_n3b_plan)
     int tmask_mode = 1;            // option force_reduce_mask: k_n3b_reduce reads only the j-slots written
     int balance_opt = 1;           // option force_balance: sharded block ranges by census weight (1) or count (0)
     bool balanced = false;         // the block ranges of this N have been weighted (n3b_balance)
     double balance_ratio = NAN;    // max / mean of the ranks' evaluated lane-steps (the weighted ranges)
     double balance_ratio_eq = NAN; // the same for the equal-count ranges
-    size_t capPlan = 0;
     int capSortN = 0;
     // overlapped MD step (option "overlap", OFF by default — measured slower): the
     // QT launch of step k runs on its own stream beside step k's force launch and waits on the
@@ -152,8 +148,7 @@ struct mdqt_ctx {
     int overlap_opt = 0;
     hipStream_t qs = nullptr;              // the QT stream
     hipEvent_t evQ = nullptr, evS = nullptr;
-    unsigned long long* dArrive = nullptr; // [ntiles] finished tile pairs per tile, monotonic
-    int arriveCap = 0;                     // tiles dArrive holds
+    mdqt::DevBuf<unsigned long long> dArrive;   // [ntiles] finished tile pairs per tile, monotonic
     unsigned long long arriveEpoch = 0;    // each counter's value after the last launch (T per launch)
     // one MD step in one launch (option "fused_step", OFF by default — measured slower, DESIGN.md
     // §8): k_md_step, see md_step_fused
@@ -161,39 +156,38 @@ struct mdqt_ctx {
     int last_fused = 0;                    // the last MD step ran as one k_md_step launch
     int last_qt_kernel = 0;                // QT kernel instance of the last substep launch (QTKernel codes)
     int last_qt_nseg = 0;                  // force partials that launch summed in its prologue
-    int* dSpinErr = nullptr;               // = dFlags + 1 (host-mapped, see hFlags)
-    unsigned long long* force_arrive = nullptr;   // set around a force launch of an overlapped step
+    int* dSpinErr = nullptr;               // = dFlags + 1 (a view: host-mapped, see hFlags)
+    unsigned long long* force_arrive = nullptr;   // a view of dArrive, set around a force launch of an overlapped step
     hipStream_t sub_stream = nullptr;             // set around the QT launch of an overlapped step
     unsigned long long sub_target = 0;
     // the optical-pumping programs' main() (mdqt_run_pump)
     std::vector<int> spinUp;       // SpinUpList (randomFrozenStartTag408Linear.cpp:105)
     int nSpinUp = 0;
-    int* dSpinUp = nullptr;        // device copy for the tagged distribution
-    double* dTkde = nullptr;       // tagged KDE partials + result
+    mdqt::DevBuf<int> dSpinUp;     // device copy for the tagged distribution
+    mdqt::DevBuf<double> dTkde;    // tagged KDE partials + result
     int pumpBin0 = -2000;          // velocity bins (j + pumpBin0) 0.0025: init() :306 / readConditions :723
     std::vector<double> vaHold;    // Vholder of Zfunc (:938-961)
     bool rs_pending = false;       // in-process group: F = sum of the ranks' dFr chunks, not formed yet
-    const double** dPeerParts = nullptr;   // device array of the group's dFr pointers
-    int nslots = 0, npairs = 0, capPairs = 0;
-    int2* dPairs = nullptr;        // (I, J) tile pair of every wave of the Newton-3 kernel; after the
+    mdqt::DevBuf<const double*> dPeerParts;   // device array of the group's dFr pointers
+    int nslots = 0, npairs = 0;
+    mdqt::DevBuf<int2> dPairs;     // (I, J) tile pair of every wave of the Newton-3 kernel; after the
                                    // npairs entries, the split table (nsplit > 0: ensure_aux)
     int nsplit = 0;                // tile pairs the split table runs in parts (halves / quarters)
     int nsplit_wg = 0;             // workgroups of the split table
     int split_opt = 1;             // option force_tile_split: 0 off, 1 halves, 2 quarters (+ diagonal halves)
     int split_cus = 0;             // option force_split_cus: the CU count the split table is cut for (0: the device's)
     // rng_mode 0: the reference's drand48 stream, consumed in ion order on the device
-    unsigned long long* dX48 = nullptr;   // [1] stream state + [48] jA + [48] jC
+    mdqt::DevBuf<unsigned long long> dX48;   // [1] stream state + [48] jA + [48] jC
     // the words the substep kernels raise, in host-pinned, device-mapped memory of this context: the
     // kernels store to them in the failure case only, the host reads them without a stream operation
     // ([0]: a position left [-L/8, 9L/8]; [1]: an overlapped / fused QT launch gave up its arrival wait)
-    volatile int* hFlags = nullptr;
-    int* dFlags = nullptr;         // the device address of hFlags
+    mdqt::PinBuf<volatile int> hFlags;
+    int* dFlags = nullptr;         // the device address of hFlags (a view)
     bool guard = false;            // host view: range-check every pair (see ForceArgs::guard)
-    double* dU = nullptr;                 // [5][S] uniforms of the current substep
+    mdqt::DevBuf<double> dU;              // [5][S] uniforms of the current substep
     ncclComm_t comm = nullptr;     // RCCL communicator over the world_size ranks (sharded runs)
-    double* dComm = nullptr;       // device staging for small all-reduces
+    mdqt::DevBuf<double> dComm;    // device staging for small all-reduces
     std::vector<mdqt_ctx*> local;  // in-process group (tests on one GPU): all-gather by D2D copies
-    size_t dCommCap = 0;
     // host-side state
     double t = 0.;
     uint64_t qidx = 0;
@@ -233,8 +227,8 @@ struct mdqt_ensemble {
     int dev = 0;
     hipStream_t stream = nullptr;                  // jobs[0]'s own stream, shared by every member
     std::unique_ptr<mdqt::FileWriter> writer;            // the members' output files (<= 16 threads in all)
-    mdqt::N3Args* dForce = nullptr;                      // [J] the batched force launch's blocks (Newton-3 members, packed)
-    mdqt::SubstepArgs* dSub = nullptr;                   // [sub_blocks] the batched QT launches' blocks: [launch][J]
+    mdqt::DevBuf<mdqt::N3Args> dForce;                   // [J] the batched force launch's blocks (Newton-3 members, packed)
+    mdqt::DevBuf<mdqt::SubstepArgs> dSub;                // [sub_blocks] the batched QT launches' blocks: [launch][J]
     int sub_blocks = 0;                            // max(J, 1024): mdqt_ensemble_md_steps builds launches ahead
     std::vector<mdqt::N3Args> force_held;                // what dForce holds
     mdqt::PinRing ring;                            // 8 slots: a launch's blocks of either kind, or md_steps' blocks ahead
@@ -246,13 +240,12 @@ struct mdqt_ensemble {
     // [J][kObsRow] in dScr's layout, the packed columns [sum 4 N_k]) and the pinned slot they come back to
     int output_batch = 0;                          // option "output_batch": 1 = one pass for all members, 0 = member by member
                                                    // (the default: docs/PROGRAMS.md "Batched output()" has the measurement)
-    mdqt::N3Args* dPot = nullptr;                  // [J] the potential launch's blocks (batched members, packed)
-    mdqt::EnsObsArgs* dObs = nullptr;              // [J] the observables' blocks (the same members)
+    mdqt::DevBuf<mdqt::N3Args> dPot;               // [J] the potential launch's blocks (batched members, packed)
+    mdqt::DevBuf<mdqt::EnsObsArgs> dObs;           // [J] the observables' blocks (the same members)
     std::vector<mdqt::N3Args> pot_held;            // what they hold
     std::vector<mdqt::EnsObsArgs> obs_held;
-    double* dObsRows = nullptr;                    // [J][kObsRow]
-    double* dObsCols = nullptr;                    // [obs_cols_cap]
-    size_t obs_cols_cap = 0;
+    mdqt::DevBuf<double> dObsRows;                 // [J][kObsRow]
+    mdqt::DevBuf<double> dObsCols;                 // [sum 4 N_k]
     mdqt::PinRing obs_ring;                        // one slot: the rows, then the columns
     unsigned long long output_launches = 0;        // kernel launches of the batched output path
     mdqt::LaunchTimer obs_timers[2];               // 0 = the batched potential launches, 1 = the batched KDE launches
@@ -262,11 +255,10 @@ struct mdqt_ensemble {
 // mdqt_ensemble's members, stream, argument ring, force launch and writer pool, and the pump kernels' blocks
 struct mdqt_pump_ensemble {
     mdqt_ensemble* base = nullptr;
-    mdqt::PumpStepArgs* dStep[2] = {nullptr, nullptr};   // [J] the leading drift's blocks, the kick launch's blocks
+    mdqt::DevBuf<mdqt::PumpStepArgs> dStep[2];           // [J] the leading drift's blocks, the kick launch's blocks
     std::vector<mdqt::PumpStepArgs> step_held[2];        // what they hold
-    mdqt::PumpTagArgs* dTag = nullptr;                   // [J]
-    mdqt::PumpKdeArgs* dKde = nullptr;                   // [J]
-    std::vector<int> kde_cap, tag_cap;                   // chunks / ints the ensemble allocated of each member's dTkde / dSpinUp
+    mdqt::DevBuf<mdqt::PumpTagArgs> dTag;                // [J]
+    mdqt::DevBuf<mdqt::PumpKdeArgs> dKde;                // [J]
     unsigned long long launches = 0;                     // the pump kernels' launches (the force launches: base)
     mdqt::LaunchTimer kick_timer;                        // the kick launches' timestamps
 };
@@ -375,7 +367,6 @@ int ens_epotential(mdqt_ensemble* e, double* Epot);
 // batched member member[q]'s Epotential() is ens_epot_of(job, rows + 64 q)
 int ens_epotential_queue(mdqt_ensemble* e, std::vector<int>& member, const double** rows);
 double ens_epot_of(const mdqt_ctx* s, const double* row);
-void ens_output_destroy(mdqt_ensemble* e);
 
 // mdqt_options.cpp (timing events)
 int mark(mdqt_ctx* s, int k);

@@ -3,6 +3,7 @@
 // each of them to its stated error against an extended-precision value (tests/test_gpu_device_math.py).
 // No shared state; the two tables are read from their __constant__ arrays (the kernels stage the same
 // values in LDS).
+#include "mdqt_devbuf.hpp"
 #include "mdqt_device.hpp"
 #include "mdqt_pairs.hpp"
 
@@ -52,21 +53,21 @@ extern "C" int mdqt_device_math(int fn, const double* x, int n, double* out0, do
     if (device >= 0 && (e = hipSetDevice(device)) != hipSuccess)
         return set_error("mdqt_device_math: hipSetDevice: %s", hipGetErrorString(e));
     const size_t bytes = (size_t)n * sizeof(double);
-    double *dx = nullptr, *d0 = nullptr, *d1 = nullptr;
+    DevBuf<double> dx, d0, d1;
     auto run = [&]() -> hipError_t {
         hipError_t r;
-        if ((r = hipMalloc(&dx, bytes)) != hipSuccess) return r;
-        if ((r = hipMalloc(&d0, bytes)) != hipSuccess) return r;
-        if (out1 && (r = hipMalloc(&d1, bytes)) != hipSuccess) return r;
+        if ((r = dx.alloc((size_t)n)) != hipSuccess) return r;
+        if ((r = d0.alloc((size_t)n)) != hipSuccess) return r;
+        if (out1 && (r = d1.alloc((size_t)n)) != hipSuccess) return r;
         if ((r = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice)) != hipSuccess) return r;
-        hipLaunchKernelGGL(k_device_math, dim3((n + 255) / 256), dim3(256), 0, 0, fn, dx, n, d0, d1);
+        hipLaunchKernelGGL(k_device_math, dim3((n + 255) / 256), dim3(256), 0, 0, fn, (const double*)dx, n, (double*)d0,
+                           (double*)d1);
         if ((r = hipGetLastError()) != hipSuccess) return r;
         if ((r = hipMemcpy(out0, d0, bytes, hipMemcpyDeviceToHost)) != hipSuccess) return r;
         if (out1 && (r = hipMemcpy(out1, d1, bytes, hipMemcpyDeviceToHost)) != hipSuccess) return r;
         return hipSuccess;
     };
     e = run();
-    (void)hipFree(dx); (void)hipFree(d0); (void)hipFree(d1);
     if (e != hipSuccess) return set_error("mdqt_device_math: %s", hipGetErrorString(e));
     return 0;
 }

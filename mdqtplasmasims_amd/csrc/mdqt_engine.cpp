@@ -70,6 +70,10 @@ extern "C" void mdqt_default_params_pump(mdqt_params* p, int qt_model) {
 
 extern "C" const char* mdqt_last_error(void) { return g_err.c_str(); }
 
+extern "C" long long mdqt_live_bytes(int space) {
+    return space == 0 ? DeviceSpace::live.load() : space == 1 ? PinnedSpace::live.load() : -1;
+}
+
 namespace mdqt {
 int set_error(const char* fmt, ...) {
     char buf[1024];
@@ -471,46 +475,27 @@ int mdqt::ensure_aux(mdqt_ctx* s) {
     const int nt_split = (s->N + 63) / 64;
     s->nsplit = s->use_n3 && s->npairs > 0 ? tile_split_count(s, nt_split) : 0;
     const int need = std::max(std::max(s->nseg, s->nslots + split_slots(s)), 2);
-    if (need > s->capNseg) {
-        if (s->dFpart) HIPCHK(hipFree(s->dFpart));
-        s->dFpart = nullptr;
-        HIPCHK(hipMalloc(&s->dFpart, (size_t)s->capS * 3 * need * sizeof(double)));
-        s->capNseg = need;
-    }
+    HIPCHK(s->dFpart.reserve((size_t)s->capS * 3 * need));
     if (s->use_n3b) {
-        const size_t need_s = (size_t)(s->n3b.nd + s->n3b.R) * 3 * s->n3b.Npad;
-        if (need_s > s->capSlots) {
-            if (s->dSlots) HIPCHK(hipFree(s->dSlots));
-            s->dSlots = nullptr;
-            HIPCHK(hipMalloc(&s->dSlots, need_s * sizeof(double)));
-            s->capSlots = need_s;
-        }
-        if (s->p.world_size > 1 && !s->dFr)
-            HIPCHK(hipMalloc(&s->dFr, (size_t)s->capS * 3 * s->p.world_size * sizeof(double)));
+        HIPCHK(s->dSlots.reserve((size_t)(s->n3b.nd + s->n3b.R) * 3 * s->n3b.Npad));
+        if (s->p.world_size > 1 && !s->dFr) HIPCHK(s->dFr.alloc((size_t)s->capS * 3 * s->p.world_size));
         if (s->sort_mode && s->N > s->capSortN) {
-            for (void* q : {(void*)s->dKeys, (void*)s->dIon, s->dSortTmp, (void*)s->dRs, (void*)s->dBoxes,
-                            (void*)s->dSubBoxes})
-                if (q) HIPCHK(hipFree(q));
-            s->dKeys = nullptr; s->dIon = nullptr; s->dSortTmp = nullptr; s->dRs = nullptr; s->dBoxes = nullptr;
-            s->dSubBoxes = nullptr;
             const int Nc = s->N;
             const int Tc = (Nc + 63) / 64;
-            HIPCHK(hipMalloc(&s->dKeys, (size_t)2 * Nc * sizeof(uint32_t)));
-            HIPCHK(hipMalloc(&s->dIon, (size_t)2 * Nc * sizeof(int)));
-            s->sortTmpBytes = spatial_order_tmp_bytes(Nc);
-            if (!s->sortTmpBytes) return set_error("radix sort scratch size query failed");
-            HIPCHK(hipMalloc(&s->dSortTmp, s->sortTmpBytes));
-            HIPCHK(hipMalloc(&s->dRs, (size_t)3 * Tc * 64 * sizeof(double)));
-            HIPCHK(hipMalloc(&s->dBoxes, (size_t)12 * Tc * sizeof(double)));
-            HIPCHK(hipMalloc(&s->dSubBoxes, (size_t)6 * 4 * Tc * sizeof(double)));
-            if (s->dTail) HIPCHK(hipFree(s->dTail));
-            if (s->dTailList) HIPCHK(hipFree(s->dTailList));
-            s->dTail = nullptr; s->dTailList = nullptr;
-            HIPCHK(hipMalloc(&s->dTail, (size_t)4 * Tc * sizeof(double)));
+            s->capSortN = 0;                         // until every buffer of the new size is there
+            HIPCHK(s->dKeys.alloc((size_t)2 * Nc));
+            HIPCHK(s->dIon.alloc((size_t)2 * Nc));
+            const size_t tmp_bytes = spatial_order_tmp_bytes(Nc);
+            if (!tmp_bytes) return set_error("radix sort scratch size query failed");
+            HIPCHK(s->dSortTmp.alloc(tmp_bytes));
+            HIPCHK(s->dRs.alloc((size_t)3 * Tc * 64));
+            HIPCHK(s->dBoxes.alloc((size_t)12 * Tc));
+            HIPCHK(s->dSubBoxes.alloc((size_t)6 * 4 * Tc));
+            HIPCHK(s->dTail.alloc((size_t)4 * Tc));
             HIPCHK(hipMemset(s->dTail, 0, (size_t)4 * Tc * sizeof(double)));
-            HIPCHK(hipMalloc(&s->dTailList, (size_t)Tc * sizeof(int)));
+            HIPCHK(s->dTailList.alloc((size_t)Tc));
             if (!s->dTailSt) {                       // [0, 8) the force calls', [8, 16) the potential calls'
-                HIPCHK(hipMalloc(&s->dTailSt, 16 * sizeof(unsigned long long)));
+                HIPCHK(s->dTailSt.alloc(16));
                 HIPCHK(hipMemset(s->dTailSt, 0, 16 * sizeof(unsigned long long)));
             }
             s->capSortN = Nc;
@@ -519,12 +504,7 @@ int mdqt::ensure_aux(mdqt_ctx* s) {
     }
     if (s->use_n3 && s->npairs > 0) {
         const int tot = s->npairs + (s->nsplit > 0 ? s->npairs + 3 * s->nsplit + s->npairs : 0);   // (bound)
-        if (tot > s->capPairs) {
-            if (s->dPairs) HIPCHK(hipFree(s->dPairs));
-            s->dPairs = nullptr;
-            HIPCHK(hipMalloc(&s->dPairs, (size_t)tot * sizeof(int2)));
-            s->capPairs = tot;
-        }
+        HIPCHK(s->dPairs.reserve((size_t)tot));
         const int nt = (s->N + 63) / 64;
         std::vector<int2> h;
         h.reserve(s->npairs);
@@ -565,31 +545,13 @@ int mdqt::ensure_aux(mdqt_ctx* s) {
     return 0;
 }
 
-static void free_device(mdqt_ctx* s) {
-    double** ps[] = {&s->dR, &s->dV, &s->dF, &s->dFpart, &s->dPsi, &s->dTp, &s->dScr, &s->dKde, &s->dUrow, &s->dU,
-                     &s->dUpart, &s->dPack};
-    for (double** q : ps) { if (*q) (void)hipFree(*q); *q = nullptr; }
-    s->capUpart = 0;
-    if (s->dPairs) (void)hipFree(s->dPairs);
-    s->dPairs = nullptr;
-    s->capPairs = 0;
-    if (s->dSlots) (void)hipFree(s->dSlots);
-    if (s->dFr) (void)hipFree(s->dFr);
-    for (void* q : {(void*)s->dKeys, (void*)s->dIon, s->dSortTmp, (void*)s->dRs, (void*)s->dBoxes, (void*)s->dSubBoxes})
-        if (q) (void)hipFree(q);
-    s->dKeys = nullptr; s->dIon = nullptr; s->dSortTmp = nullptr; s->dRs = nullptr; s->dBoxes = nullptr;
-    s->dSubBoxes = nullptr;
-    if (s->dTail) (void)hipFree(s->dTail);
-    if (s->dTailList) (void)hipFree(s->dTailList);
-    if (s->dTailSt) (void)hipFree(s->dTailSt);
-    s->dTail = nullptr; s->dTailList = nullptr; s->dTailSt = nullptr;
+// a new slab size S: what ensure_aux and the later calls size by it (or by N) starts over
+static void drop_sized(mdqt_ctx* s) {
+    s->dFpart.reset(); s->dUpart.reset(); s->dPairs.reset(); s->dSlots.reset(); s->dFr.reset(); s->dPlan.reset();
+    s->dKeys.reset(); s->dIon.reset(); s->dSortTmp.reset(); s->dRs.reset(); s->dBoxes.reset(); s->dSubBoxes.reset();
+    s->dTail.reset(); s->dTailList.reset(); s->dTailSt.reset(); s->dPeerParts.reset();
     s->capSortN = 0;
-    if (s->dPlan) (void)hipFree(s->dPlan);
-    s->dPlan = nullptr; s->capPlan = 0;
-    if (s->dPeerParts) (void)hipFree((void*)s->dPeerParts);
-    s->dSlots = nullptr; s->dFr = nullptr; s->dPeerParts = nullptr;
-    s->capSlots = 0;
-    s->capS = 0; s->capNseg = 0; s->kdeChunks = 0;
+    s->capS = 0; s->kdeChunks = 0;
 }
 
 // (re)size everything for N ions; device contents are NOT preserved (callers upload after)
@@ -601,20 +563,20 @@ int mdqt::resize(mdqt_ctx* s, int N) {
     choose_segments(s);
     const int W = s->p.world_size;
     if (S != s->capS) {
-        free_device(s);
+        drop_sized(s);
         HIPCHK(hipSetDevice(s->dev));
         const size_t sz = (size_t)S * sizeof(double);
-        HIPCHK(hipMalloc(&s->dR, sz * 3 * W));
-        HIPCHK(hipMalloc(&s->dV, sz * 3));
-        HIPCHK(hipMalloc(&s->dF, sz * 3));
-        HIPCHK(hipMalloc(&s->dPsi, sz * 24));
-        HIPCHK(hipMalloc(&s->dTp, sz));
-        HIPCHK(hipMalloc(&s->dUrow, sz));
-        if (s->p.rng_mode == 0) HIPCHK(hipMalloc(&s->dU, sz * 5));
-        HIPCHK(hipMalloc(&s->dScr, (64 + 3 * NBINS) * sizeof(double)));
+        HIPCHK(s->dR.alloc((size_t)S * 3 * W));
+        HIPCHK(s->dV.alloc((size_t)S * 3));
+        HIPCHK(s->dF.alloc((size_t)S * 3));
+        HIPCHK(s->dPsi.alloc((size_t)S * 24));
+        HIPCHK(s->dTp.alloc((size_t)S));
+        HIPCHK(s->dUrow.alloc((size_t)S));
+        if (s->p.rng_mode == 0) HIPCHK(s->dU.alloc((size_t)S * 5));
+        HIPCHK(s->dScr.alloc(64 + 3 * NBINS));
         s->kdeChunks = 512;                            // chunks of >= 32 ions (the bins near v = 0 hold
-        HIPCHK(hipMalloc(&s->dKde, (size_t)s->kdeChunks * 3 * NBINS * sizeof(double)));   // the work)
-        HIPCHK(hipMalloc(&s->dPack, sz * 4));
+        HIPCHK(s->dKde.alloc((size_t)s->kdeChunks * 3 * NBINS));   // the work)
+        HIPCHK(s->dPack.alloc((size_t)S * 4));
         s->capS = S;
         HIPCHK(hipMemsetAsync(s->dR, 0, sz * 3 * W, s->stream));
         HIPCHK(hipMemsetAsync(s->dV, 0, sz * 3, s->stream));
@@ -644,36 +606,26 @@ extern "C" int mdqt_create(const mdqt_params* p, mdqt_ctx** out) {
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev < 1) return set_error("no HIP device available (%s)", hipGetErrorString(e));
-    mdqt_ctx* s = new mdqt_ctx();
+    std::unique_ptr<mdqt_ctx, void (*)(mdqt_ctx*)> guard(new mdqt_ctx(), mdqt_destroy);
+    mdqt_ctx* s = guard.get();
     s->p = *p;
     s->p.saveDirectory[sizeof(s->p.saveDirectory) - 1] = 0;
     if (p->device >= 0) {
-        if (p->device >= ndev) { delete s; return set_error("device %d >= device count %d", p->device, ndev); }
+        if (p->device >= ndev) return set_error("device %d >= device count %d", p->device, ndev);
         s->dev = p->device;
     } else {
         (void)hipGetDevice(&s->dev);
     }
-    if (hipSetDevice(s->dev) != hipSuccess || hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking) != hipSuccess) {
-        delete s;
+    if (hipSetDevice(s->dev) != hipSuccess || hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking) != hipSuccess)
         return set_error("cannot create HIP stream on device %d", p->device);
-    }
     s->stream = s->own;
-    if (hipMalloc(&s->dTab, sizeof(LaneTab)) != hipSuccess || hipMalloc(&s->dFTab, 2 * sizeof(FastTab)) != hipSuccess) {
-        mdqt_destroy(s);
-        return set_error("hipMalloc lane tables");
-    }
+    if (s->dTab.alloc(1) != hipSuccess || s->dFTab.alloc(2) != hipSuccess) return set_error("hipMalloc lane tables");
     {
-        void *h = nullptr, *d = nullptr;
-        if (hipHostMalloc(&h, 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess) {
-            mdqt_destroy(s);
+        void* d = nullptr;
+        if (s->hFlags.alloc(2, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess)
             return set_error("hipHostMalloc flags");
-        }
-        s->hFlags = (volatile int*)h;
         s->hFlags[0] = s->hFlags[1] = 0;
-        if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
-            mdqt_destroy(s);
-            return set_error("hipHostGetDevicePointer flags");
-        }
+        if (hipHostGetDevicePointer(&d, (void*)s->hFlags.get(), 0) != hipSuccess) return set_error("hipHostGetDevicePointer flags");
         s->dFlags = (int*)d;
         s->dSpinErr = s->dFlags + 1;
     }
@@ -687,24 +639,19 @@ extern "C" int mdqt_create(const mdqt_params* p, mdqt_ctx** out) {
             Cc = (A * Cc + Cc) & 0xFFFFFFFFFFFFull;
             A = (A * A) & 0xFFFFFFFFFFFFull;
         }
-        if (hipMalloc(&s->dX48, sizeof h) != hipSuccess ||
-            hipMemcpy(s->dX48, h, sizeof h, hipMemcpyHostToDevice) != hipSuccess) {
-            mdqt_destroy(s);
+        if (s->dX48.alloc(97) != hipSuccess || hipMemcpy(s->dX48, h, sizeof h, hipMemcpyHostToDevice) != hipSuccess)
             return set_error("drand48 state upload failed");
-        }
     }
     if (hipMemcpy(s->dTab, &s->tab, sizeof(LaneTab), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(s->dFTab, &s->ftab, sizeof(FastTab), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(s->dFTab + 1, &s->ftabL, sizeof(FastTab), hipMemcpyHostToDevice) != hipSuccess) {
-        mdqt_destroy(s);
+        hipMemcpy(s->dFTab + 1, &s->ftabL, sizeof(FastTab), hipMemcpyHostToDevice) != hipSuccess)
         return set_error("upload of the lane table failed");
-    }
     s->t = 0.; s->qidx = 0; s->c0 = p->c0; s->counter = 0;
     s->x48 = srand48_state(p->seed);
     strncpy(s->saveDirectory, s->p.saveDirectory, sizeof(s->saveDirectory) - 1);
     s->saveDirectory[sizeof(s->saveDirectory) - 1] = 0;
-    if (resize(s, 0)) { mdqt_destroy(s); return -1; }
-    *out = s;
+    if (resize(s, 0)) return -1;
+    *out = guard.release();
     return 0;
 }
 
@@ -713,20 +660,10 @@ extern "C" void mdqt_destroy(mdqt_ctx* s) {
     s->writer.reset();                                   // joins the file writers
     (void)hipSetDevice(s->dev);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    free_device(s);
-    if (s->dTab) (void)hipFree(s->dTab);
-    if (s->dFTab) (void)hipFree(s->dFTab);
-    if (s->dComm) (void)hipFree(s->dComm);
-    if (s->dSpinUp) (void)hipFree(s->dSpinUp);
-    if (s->dArrive) (void)hipFree(s->dArrive);
     if (s->evQ) (void)hipEventDestroy(s->evQ);
     if (s->evS) (void)hipEventDestroy(s->evS);
     if (s->qs) (void)hipStreamDestroy(s->qs);
-    if (s->dTkde) (void)hipFree(s->dTkde);
-    if (s->dX48) (void)hipFree(s->dX48);
-    if (s->hFlags) (void)hipHostFree((void*)s->hFlags);
     comm_destroy(s);
-    for (LaunchTimer& t : s->timers) t.destroy();
     for (auto& c : s->bdcalls) {
         for (hipEvent_t ev : c.m) if (ev) (void)hipEventDestroy(ev);
         if (c.ag0) (void)hipEventDestroy(c.ag0);

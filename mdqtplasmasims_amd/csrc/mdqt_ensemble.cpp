@@ -258,11 +258,6 @@ extern "C" void mdqt_ensemble_destroy(mdqt_ensemble* e) {
         e->jobs[k]->shared_writer = nullptr;
         mdqt_destroy(e->jobs[k]);
     }
-    if (e->dForce) (void)hipFree(e->dForce);
-    if (e->dSub) (void)hipFree(e->dSub);
-    ens_output_destroy(e);
-    e->ring.destroy();
-    for (LaunchTimer& t : e->timers) t.destroy();
     delete e;
 }
 
@@ -301,8 +296,7 @@ int mdqt::ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, 
     HIPCHK(hipSetDevice(e->dev));
     e->sub_blocks = std::max(njobs, 1024);
     const size_t slot_bytes = std::max((size_t)e->sub_blocks * sizeof(SubstepArgs), (size_t)njobs * sizeof(N3Args));
-    if (hipMalloc(&e->dForce, (size_t)njobs * sizeof(N3Args)) != hipSuccess ||
-        hipMalloc(&e->dSub, (size_t)e->sub_blocks * sizeof(SubstepArgs)) != hipSuccess)
+    if (e->dForce.alloc((size_t)njobs) != hipSuccess || e->dSub.alloc((size_t)e->sub_blocks) != hipSuccess)
         return set_error("%s: allocating the argument blocks of %d jobs failed", what, njobs);
     if (e->ring.create(slot_bytes, kRingSlots, hipEventDisableTiming | hipEventDisableSystemFence)) return -1;
     *out = e.release();

@@ -57,18 +57,12 @@ int ens_observe(mdqt_ensemble* e, ObsWhat what, EnsObs& r, bool sync = true) {
     }
     const int nb = (int)r.member.size();
     if (nb == 0) return 0;
-    if (!e->dPot) {
-        if (hipMalloc(&e->dPot, (size_t)J * sizeof(N3Args)) != hipSuccess || hipMalloc(&e->dObs, (size_t)J * sizeof(EnsObsArgs)) != hipSuccess ||
-            hipMalloc(&e->dObsRows, (size_t)J * kObsRow * sizeof(double)) != hipSuccess)
-            return set_error("allocating the output blocks and rows of %d jobs failed", J);
-    }
-    if (total > e->obs_cols_cap) {
+    if (e->dPot.reserve((size_t)J) != hipSuccess || e->dObs.reserve((size_t)J) != hipSuccess ||
+        e->dObsRows.reserve((size_t)J * kObsRow) != hipSuccess)
+        return set_error("allocating the output blocks and rows of %d jobs failed", J);
+    if (total > e->dObsCols.capacity()) {
         HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->dObsCols) HIPCHK(hipFree(e->dObsCols));
-        e->dObsCols = nullptr;
-        e->obs_cols_cap = 0;
-        HIPCHK(hipMalloc(&e->dObsCols, total * sizeof(double)));
-        e->obs_cols_cap = total;
+        HIPCHK(e->dObsCols.reserve(total));
     }
     std::vector<N3Args> pot((size_t)nb);
     std::vector<EnsObsArgs> obs((size_t)nb);
@@ -134,15 +128,6 @@ int ens_observe(mdqt_ensemble* e, ObsWhat what, EnsObs& r, bool sync = true) {
 }
 
 }  // namespace
-
-void mdqt::ens_output_destroy(mdqt_ensemble* e) {
-    if (e->dPot) (void)hipFree(e->dPot);
-    if (e->dObs) (void)hipFree(e->dObs);
-    if (e->dObsRows) (void)hipFree(e->dObsRows);
-    if (e->dObsCols) (void)hipFree(e->dObsCols);
-    e->obs_ring.destroy();
-    for (LaunchTimer& t : e->obs_timers) t.destroy();
-}
 
 // output() of every member (the files are left to the writers: the caller flushes)
 int mdqt::ens_output(mdqt_ensemble* e) {

@@ -349,7 +349,7 @@ int mdqt::n3b_args(mdqt_ctx* s, N3BArgs& a) {
         SortArgs o;
         o.Rall = s->dR; o.N = s->N; o.S = s->S; o.Npad = a.Npad; o.L = s->L;
         o.keys = s->dKeys; o.keys2 = s->dKeys + s->N; o.ion = s->dIon; o.perm = s->dIon + s->N;
-        o.tmp = s->dSortTmp; o.tmp_bytes = s->sortTmpBytes; o.Rs = s->dRs; o.boxes = s->dBoxes;
+        o.tmp = s->dSortTmp; o.tmp_bytes = s->dSortTmp.capacity(); o.Rs = s->dRs; o.boxes = s->dBoxes;
         o.subboxes = s->dSubBoxes;
         HIPCHK(launch_spatial_order(o, s->stream));
         a.use_sort = s->sort_mode; a.Rs = s->dRs; a.perm = o.perm; a.boxes = s->dBoxes; a.subboxes = s->dSubBoxes;
@@ -362,12 +362,7 @@ int mdqt::n3b_args(mdqt_ctx* s, N3BArgs& a) {
         const size_t nplan = (size_t)std::max(a.Phi - a.Plo, 0) * a.nd * (kN3BBlock * kN3BBlock + 1);
         const int tmw = (a.nd + 63) / 64;
         const size_t need = nplan + (size_t)a.T * tmw;
-        if (need > s->capPlan) {
-            if (s->dPlan) HIPCHK(hipFree(s->dPlan));
-            s->dPlan = nullptr;
-            HIPCHK(hipMalloc((void**)&s->dPlan, need * sizeof(uint2)));
-            s->capPlan = need;
-        }
+        HIPCHK(s->dPlan.reserve(need));
         a.plan = s->dPlan;
         // (no masks for a rank without blocks: nothing would clear or fill them — ADVICE r05)
         const bool masks = s->tmask_mode && a.Phi > a.Plo;
@@ -407,14 +402,13 @@ static int run_census(mdqt_ctx* s, size_t extra, bool per_block, unsigned long l
     N3BArgs a;
     if (n3b_args(s, a)) return -1;
     if (all_blocks) { a.Plo = 0; a.Phi = a.NB; }
-    unsigned long long* d = nullptr;
-    HIPCHK(hipMalloc(&d, (2 * kCensus + extra) * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d;
+    HIPCHK(d.alloc(2 * kCensus + extra));
     unsigned long long* x = extra ? d + 2 * kCensus : nullptr;
     hipError_t e = launch_n3b_census(a, d, s->stream, per_block ? x : nullptr, per_block ? nullptr : x);
     if (e == hipSuccess) e = hipMemcpyAsync(h, extra ? x : d, (extra ? extra : 2 * kCensus) * sizeof(unsigned long long),
                                             hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return set_error("%s: %s", what, hipGetErrorString(e));
     return 0;
 }

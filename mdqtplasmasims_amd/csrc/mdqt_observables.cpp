@@ -8,17 +8,6 @@
 
 using namespace mdqt;
 
-// the potential rows' own partials buffer, at least `need` doubles
-static int grow_upart(mdqt_ctx* s, size_t need) {
-    if (need <= s->capUpart) return 0;
-    if (s->dUpart) HIPCHK(hipFree(s->dUpart));
-    s->dUpart = nullptr;
-    s->capUpart = 0;
-    HIPCHK(hipMalloc(&s->dUpart, need * sizeof(double)));
-    s->capUpart = need;
-    return 0;
-}
-
 // does potential_rows take the Newton-3 tile kernel's POT mode for this context?
 bool mdqt::potential_on_tiles(const mdqt_ctx* s) {
     return s->use_n3 && !s->use_n3b && s->p.world_size == 1 && s->local.empty() && s->force_variant <= 1 &&
@@ -29,7 +18,7 @@ bool mdqt::potential_on_tiles(const mdqt_ctx* s) {
 // potential's own slots (one plane per slot: component 0) — pending force slots stay pending and untouched
 int mdqt::potential_n3_block(mdqt_ctx* s, N3Args& a) {
     const size_t need = (size_t)s->nslots * s->S;
-    if (grow_upart(s, need)) return -1;
+    HIPCHK(s->dUpart.reserve(need));
     if (n3_force_args(s, a, true)) return -1;
     a.P = s->dUpart;
     a.arrive = nullptr;
@@ -85,7 +74,7 @@ static int potential_rows(mdqt_ctx* s, double* urow_dev) {
     double* buf = s->dFpart;
     const size_t need = (size_t)s->nseg * 3 * s->S;
     if (s->p.world_size == 1 && s->local.empty() && need * sizeof(double) <= ((size_t)64 << 20)) {
-        if (grow_upart(s, need)) return -1;
+        HIPCHK(s->dUpart.reserve(need));
         buf = s->dUpart;
     } else if (settle_forces(s)) {
         return -1;

@@ -18,16 +18,15 @@ extern "C" int mdqt_tag_spin_up(mdqt_ctx* s, int* tags, int* n_up) {
     if (s->p.qt_model == 0) return set_error("mdqt_tag_spin_up: qt_model 0 (laser cooling) has no spin tagging");
     HIPCHK(hipSetDevice(s->dev));
     const int n = s->nloc;
-    int* d = nullptr;
+    DevBuf<int> d;
     if (n > 0) {
-        HIPCHK(hipMalloc(&d, (size_t)n * sizeof(int)));
+        HIPCHK(d.alloc((size_t)n));
         HIPCHK(launch_tag_spin_up(s->dPsi, n, s->S, (uint64_t)s->lo, s->qidx, s->qc, d, s->stream));
     }
     std::vector<int> h((size_t)n, 0);
     if (n > 0) {
         HIPCHK(hipMemcpyAsync(h.data(), d, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(hipFree(d));
     }
     int cnt = 0;
     for (int i = 0; i < n; ++i) cnt += h[i];
@@ -95,7 +94,7 @@ static int measure_spin_ups(mdqt_ctx* s) {
     int n_up = 0;
     if (mdqt_tag_spin_up(s, s->spinUp.data(), &n_up)) return -1;
     s->nSpinUp = n_up;
-    if (!s->dSpinUp) HIPCHK(hipMalloc(&s->dSpinUp, (size_t)s->capS * sizeof(int)));
+    HIPCHK(s->dSpinUp.reserve((size_t)s->capS));
     HIPCHK(hipMemcpyAsync(s->dSpinUp, s->spinUp.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s->stream));
     return pump_spin_ups_file(s);
 }
@@ -103,9 +102,9 @@ static int measure_spin_ups(mdqt_ctx* s) {
 // output()'s device buffers: the tagged distribution's partials and result, the device copy of the tags
 int mdqt::pump_output_buffers(mdqt_ctx* s) {
     const int nch = (s->N + 255) / 256;
-    if (!s->dTkde) HIPCHK(hipMalloc(&s->dTkde, ((size_t)(nch > 0 ? nch : 1) + 1) * 3 * TKDE_BINS * sizeof(double)));
-    if (!s->dSpinUp) {
-        HIPCHK(hipMalloc(&s->dSpinUp, (size_t)s->capS * sizeof(int)));
+    HIPCHK(s->dTkde.reserve(((size_t)(nch > 0 ? nch : 1) + 1) * 3 * TKDE_BINS));
+    if (s->dSpinUp.capacity() < (size_t)s->capS) {
+        HIPCHK(s->dSpinUp.reserve((size_t)s->capS));
         HIPCHK(hipMemsetAsync(s->dSpinUp, 0, (size_t)s->capS * sizeof(int), s->stream));
     }
     return 0;
@@ -259,8 +258,7 @@ int mdqt::pump_read_conditions(mdqt_ctx* s, int c0) {         // :709-797
     s->spinUp = up;
     s->nSpinUp = 0;
     for (int k = 0; k < N; ++k) s->nSpinUp += up[k] ? 1 : 0;
-    if (s->dSpinUp) { (void)hipFree(s->dSpinUp); s->dSpinUp = nullptr; }
-    HIPCHK(hipMalloc(&s->dSpinUp, (size_t)s->capS * sizeof(int)));
+    HIPCHK(s->dSpinUp.reserve((size_t)s->capS));
     HIPCHK(hipMemcpyAsync(s->dSpinUp, up.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s->stream));
     s->t = t;
     s->c0 = c0;

@@ -90,28 +90,20 @@ int pump_qsteps(mdqt_pump_ensemble* pe, int n) {
     });
 }
 
-// a member's tag array and tagged-distribution buffers, of a size this ensemble knows (the context allocates
-// them once, for the N of that moment)
+// a member's tag array and tagged-distribution buffers at the member's present size
 int member_buffers(mdqt_pump_ensemble* pe, int k) {
     mdqt_ensemble* e = pe->base;
     mdqt_ctx* s = e->jobs[k];
     const int nch = std::max(1, (s->N + 255) / 256);
-    if (pe->kde_cap[k] < nch || pe->tag_cap[k] < s->capS) HIPCHK(hipStreamSynchronize(e->stream));
-    if (pe->kde_cap[k] < nch) {
-        if (s->dTkde) HIPCHK(hipFree(s->dTkde));
-        s->dTkde = nullptr;
-        HIPCHK(hipMalloc(&s->dTkde, ((size_t)nch + 1) * 3 * TKDE_BINS * sizeof(double)));
-        pe->kde_cap[k] = nch;
-    }
-    if (pe->tag_cap[k] < s->capS) {
-        if (s->dSpinUp) HIPCHK(hipFree(s->dSpinUp));
-        s->dSpinUp = nullptr;
-        HIPCHK(hipMalloc(&s->dSpinUp, (size_t)s->capS * sizeof(int)));
+    const size_t kde = ((size_t)nch + 1) * 3 * TKDE_BINS;
+    if (s->dTkde.capacity() < kde || s->dSpinUp.capacity() < (size_t)s->capS) HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(s->dTkde.reserve(kde));
+    if (s->dSpinUp.capacity() < (size_t)s->capS) {
+        HIPCHK(s->dSpinUp.reserve((size_t)s->capS));
         HIPCHK(hipMemsetAsync(s->dSpinUp, 0, (size_t)s->capS * sizeof(int), e->stream));
         if ((int)s->spinUp.size() >= s->N && tagged(s))
             HIPCHK(hipMemcpyAsync(s->dSpinUp, s->spinUp.data(), (size_t)s->N * sizeof(int), hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));                 // spinUp may change before the copy would run
-        pe->tag_cap[k] = s->capS;
     }
     return 0;
 }
@@ -221,10 +213,6 @@ extern "C" void mdqt_pump_ensemble_destroy(mdqt_pump_ensemble* pe) {
         (void)hipSetDevice(pe->base->dev);
         if (pe->base->stream) (void)hipStreamSynchronize(pe->base->stream);
     }
-    for (auto& d : pe->dStep) if (d) (void)hipFree(d);
-    if (pe->dTag) (void)hipFree(pe->dTag);
-    if (pe->dKde) (void)hipFree(pe->dKde);
-    pe->kick_timer.destroy();
     mdqt_ensemble_destroy(pe->base);
     delete pe;
 }
@@ -237,12 +225,8 @@ extern "C" int mdqt_pump_ensemble_create(const mdqt_params* p, int njobs, mdqt_p
     if (!pe) return set_error("mdqt_pump_ensemble_create: out of memory");
     if (ensemble_create(p, njobs, &pe->base, "mdqt_pump_ensemble_create", true)) return -1;
     HIPCHK(hipSetDevice(pe->base->dev));
-    pe->kde_cap.assign((size_t)njobs, 0);
-    pe->tag_cap.assign((size_t)njobs, 0);
-    if (hipMalloc(&pe->dStep[0], (size_t)njobs * sizeof(PumpStepArgs)) != hipSuccess ||
-        hipMalloc(&pe->dStep[1], (size_t)njobs * sizeof(PumpStepArgs)) != hipSuccess ||
-        hipMalloc(&pe->dTag, (size_t)njobs * sizeof(PumpTagArgs)) != hipSuccess ||
-        hipMalloc(&pe->dKde, (size_t)njobs * sizeof(PumpKdeArgs)) != hipSuccess)
+    if (pe->dStep[0].alloc((size_t)njobs) != hipSuccess || pe->dStep[1].alloc((size_t)njobs) != hipSuccess ||
+        pe->dTag.alloc((size_t)njobs) != hipSuccess || pe->dKde.alloc((size_t)njobs) != hipSuccess)
         return set_error("mdqt_pump_ensemble_create: allocating the argument blocks of %d jobs failed", njobs);
     *out = pe.release();
     return 0;
@@ -318,7 +302,6 @@ extern "C" int mdqt_pump_ensemble_run(mdqt_pump_ensemble* pe) {
     const int recorded = e->jobs[0]->p.newRun == 1 ? 0 : 1;      // recordedSpinUps :81
     for (mdqt_ctx* s : e->jobs)                                  // :1036-1046
         if (recorded ? pump_read_conditions(s, s->p.c0) : mdqt_init(s)) return -1;
-    std::fill(pe->tag_cap.begin(), pe->tag_cap.end(), 0);        // (readConditions allocates the tags anew)
     if (pump_check(pe, "mdqt_pump_ensemble_run")) return -1;
     HIPCHK(hipSetDevice(e->dev));
     struct {                                                     // the loop's driver: one batched call over the members

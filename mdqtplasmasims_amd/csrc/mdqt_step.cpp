@@ -252,15 +252,12 @@ static bool overlap_applies(const mdqt_ctx* s) {
 // every tile's counter, the waiters compare with the running epoch)
 int mdqt::arrive_setup(mdqt_ctx* s) {
     const int T = (s->N + 63) / 64;
-    if (s->dArrive && s->arriveCap >= T) return 0;
+    if (s->dArrive && s->dArrive.capacity() >= (size_t)T) return 0;
     HIPCHK(hipStreamSynchronize(s->stream));
     if (s->qs) HIPCHK(hipStreamSynchronize(s->qs));
-    if (s->dArrive) HIPCHK(hipFree(s->dArrive));
-    s->dArrive = nullptr;
-    HIPCHK(hipMalloc(&s->dArrive, (size_t)T * sizeof(unsigned long long)));
+    HIPCHK(s->dArrive.alloc((size_t)T));
     HIPCHK(hipMemset(s->dArrive, 0, (size_t)T * sizeof(unsigned long long)));
     HIPCHK(hipDeviceSynchronize());
-    s->arriveCap = T;
     s->arriveEpoch = 0;
     return 0;
 }
@@ -397,12 +394,13 @@ static int pairs_raw(int mode, int N, double L, double lDeb, const double* R, si
     std::vector<double> h((size_t)3 * S, 0.);
     for (int c = 0; c < 3; ++c)
         for (int i = 0; i < N; ++i) h[(size_t)c * S + i] = R[(size_t)c * ld + i];
-    double *dR = nullptr, *dP = nullptr, *dO = nullptr;
     hipStream_t st;
     HIPCHK(hipStreamCreate(&st));
-    HIPCHK(hipMalloc(&dR, h.size() * sizeof(double)));
-    HIPCHK(hipMalloc(&dP, (size_t)3 * S * nseg * sizeof(double)));
-    HIPCHK(hipMalloc(&dO, (size_t)3 * S * sizeof(double)));
+    std::unique_ptr<ihipStream_t, hipError_t (*)(hipStream_t)> st_owner(st, hipStreamDestroy);
+    DevBuf<double> dR, dP, dO;
+    HIPCHK(dR.alloc(h.size()));
+    HIPCHK(dP.alloc((size_t)3 * S * nseg));
+    HIPCHK(dO.alloc((size_t)3 * S));
     HIPCHK(hipMemcpyAsync(dR, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
     int oor = 0;
     for (size_t k = 0; k < (size_t)3 * N && !oor; ++k) {
@@ -418,8 +416,6 @@ static int pairs_raw(int mode, int N, double L, double lDeb, const double* R, si
     HIPCHK(launch_reduce_segments(dP, dO, nseg, N, S, mode == 0 ? 3 : 1, st));
     HIPCHK(hipMemcpyAsync(h.data(), dO, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipFree(dR)); HIPCHK(hipFree(dP)); HIPCHK(hipFree(dO));
-    HIPCHK(hipStreamDestroy(st));
     if (mode == 0) {
         for (int c = 0; c < 3; ++c)
             for (int i = 0; i < N; ++i) out[(size_t)c * ld + i] = h[(size_t)c * S + i];
