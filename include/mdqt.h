@@ -455,6 +455,26 @@ unsigned long long mdqt_ensemble_output_launches(const mdqt_ensemble* e);
  * medians.  Replaces no reference function */
 int         mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on);
 int         mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n);
+/* Parameter sweeps: npoints parameter points x njobs replicas in one ensemble (the thesis data are scans of the
+ * laser settings, each averaged over tens of jobs).  Member k is point k / njobs, replica r = k % njobs
+ * (point-major), with the point's parameters and job + r, seed + r; all points share job and seed, so replica r
+ * of every point starts from the same init() state (init() reads none of the swept fields).  The points may
+ * differ in detuning, detuningDP, Om, OmDP and fracOfSig only.  Refused, with the point index and the field in
+ * mdqt_last_error, before any context is created or HIP call made: another field that differs from point 0;
+ * points with fracOfSig == 0 beside points with fracOfSig != 0 (they run different QT kernel instances, and one
+ * launch is one instance); two identical points, or two whose run directory names are the same (the name holds
+ * the fields x 100 as integers: -1.001 and -1.002 collide); npoints < 1, njobs < 1, npoints x njobs > 1024; and
+ * what mdqt_ensemble_create refuses.  Every member is bit for bit the job it is on its own context: the batched
+ * QT kernels take each member's table (mdqt_ensemble_sweep_qt.hip), everything else in a launch was per member
+ * already.  One kernel instance serves a launch, so every batched call first checks that the members agree on
+ * what selects it and fails naming the first member that does not (an option set on one member only, such as
+ * qt_im01), before launching anything.  One point is allowed and takes the same kernels.  The handle is an
+ * mdqt_ensemble: every mdqt_ensemble_* call applies.
+ * mdqt_ensemble_sweep_params: host only — the same validation, and member k's parameters.
+ * mdqt_ensemble_points: the number of points (1 for mdqt_ensemble_create's ensembles). */
+int         mdqt_ensemble_create_sweep(const mdqt_params* points, int npoints, int njobs, mdqt_ensemble** out);
+int         mdqt_ensemble_sweep_params(const mdqt_params* points, int npoints, int njobs, int k, mdqt_params* out);
+int         mdqt_ensemble_points(const mdqt_ensemble* e);
 
 /* ---- ensembles of the optical-pumping programs ----
  * J independent jobs of randomFrozenStartTag408Linear.cpp / 408Quad / 422Linear (qt_model 1-3) on one device,

@@ -226,6 +226,10 @@ SIGNATURES = [
     ("mdqt_ensemble_observables", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     ("mdqt_ensemble_epotential", C.c_int, [C.c_void_p, _dp]),
     ("mdqt_ensemble_output_launches", C.c_ulonglong, [C.c_void_p]),
+    # parameter sweeps: points x replicas (points: an array of MdqtParams)
+    ("mdqt_ensemble_create_sweep", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    ("mdqt_ensemble_sweep_params", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.c_int, C.c_int, C.POINTER(MdqtParams)]),
+    ("mdqt_ensemble_points", C.c_int, [C.c_void_p]),
     # ensembles of the optical-pumping programs, and the single context's stepwise MD step
     ("mdqt_pump_md_steps", C.c_int, [C.c_void_p, C.c_int]),
     ("mdqt_pump_ensemble_create", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.POINTER(C.c_void_p)]),

@@ -17,6 +17,12 @@
 //   --output_batch=0|1 (with --njobs): output() of all jobs in one device pass (1) or job after job (0, the
 //   default); the same files either way.
 //
+//   --sweep=NAME:v1,v2,... (with --njobs=R; NAME one of detuning, detuningDP, Om, OmDP, fracOfSig; may be given
+//   for several names) runs a parameter scan as one ensemble (mdqt_ensemble_create_sweep): the points are the
+//   Cartesian product of the lists, the first-named axis slowest, every other parameter as given; each point
+//   has the R jobs <job> .. <job>+R-1 (seeds seed .. seed+R-1), and each job's files are those of the single
+//   run with the point's parameters; prints every N in member order (point-major).
+//
 //   --pump_program=m --pump_jobs=J does the same for the pumping programs (mdqt_pump_ensemble_run): the jobs
 //   <job> .. <job>+J-1 stepped in batched launches, each job's tree byte for byte that of
 //   `mdqt <job>+k --pump_program=m --seed=<seed>+k`; prints every N.
@@ -39,8 +45,41 @@ static void usage(void) {
             "       mdqt <job> --njobs=J [... as above]   jobs <job> .. <job>+J-1 as one ensemble (J >= 1;\n"
             "                  seeds seed .. seed+J-1; not with --pump_program: --pump_jobs)\n"
             "                  [--output_batch=0|1]   output() of all jobs in one device pass (1) or job after job (0)\n"
+            "                  [--sweep=NAME:v1,v2,... ...]   with --njobs=R: a scan of detuning | detuningDP | Om | OmDP |\n"
+            "                  fracOfSig, R jobs per point, as one ensemble (points: the product of the lists, the first\n"
+            "                  NAME slowest; points x R <= 1024; each NAME once)\n"
             "       mdqt <job> --pump_program=1|2|3 --pump_jobs=J [...]   the pump jobs <job> .. <job>+J-1 as one\n"
             "                  ensemble (1 <= J <= 1024; seeds seed .. seed+J-1; not with --njobs)\n");
+}
+
+// --sweep: one axis of the scan
+enum { kSweepNames = 5, kSweepMax = 1024 };
+static const char* const sweep_names[kSweepNames] = {"detuning", "detuningDP", "Om", "OmDP", "fracOfSig"};
+struct SweepAxis {
+    int field, n;
+    double v[kSweepMax];
+};
+static double* sweep_field(mdqt_params* p, int field) {
+    double* const f[kSweepNames] = {&p->detuning, &p->detuningDP, &p->Om, &p->OmDP, &p->fracOfSig};
+    return f[field];
+}
+// "NAME:v1,v2,..." -> the axis; 0 if it is one (a sweepable NAME, a non-empty list of numbers)
+static int parse_sweep(const char* v, SweepAxis* ax) {
+    const char* colon = strchr(v, ':');
+    if (!colon) return -1;
+    ax->field = -1;
+    for (int f = 0; f < kSweepNames; ++f)
+        if (strlen(sweep_names[f]) == (size_t)(colon - v) && !strncmp(v, sweep_names[f], (size_t)(colon - v))) ax->field = f;
+    if (ax->field < 0) return -1;
+    ax->n = 0;
+    for (const char* s = colon + 1;;) {
+        char* end = NULL;
+        const double x = strtod(s, &end);
+        if (end == s || (*end != ',' && *end != 0) || ax->n >= kSweepMax) return -1;
+        ax->v[ax->n++] = x;
+        if (!*end) return 0;
+        s = end + 1;
+    }
 }
 
 int main(int argc, char** argv) {
@@ -58,6 +97,8 @@ int main(int argc, char** argv) {
     long njobs = -1;                                        // --njobs: the jobs of an ensemble (-1: not given)
     long pump_jobs = -1;                                    // --pump_jobs: the jobs of a pump ensemble
     long output_batch = -1;                                 // --output_batch: the ensemble's option (-1: its default)
+    static SweepAxis axes[kSweepNames];                     // --sweep: the axes in the order given
+    int naxes = 0;
     for (int i = 2; i < argc; ++i) {
         const char* a = argv[i];
         if (strncmp(a, "--", 2) != 0 || !strchr(a, '=')) { usage(); return 2; }
@@ -89,6 +130,14 @@ int main(int argc, char** argv) {
             if (end == v || *end || output_batch < 0 || output_batch > 1) { usage(); return 2; }
             continue;
         }
+        if (!strcmp(key, "sweep")) {
+            SweepAxis* ax = &axes[naxes < kSweepNames ? naxes : 0];
+            if (naxes >= kSweepNames || parse_sweep(v, ax)) { usage(); return 2; }
+            for (int o = 0; o < naxes; ++o)
+                if (axes[o].field == ax->field) { usage(); return 2; }     // a NAME given twice
+            ++naxes;
+            continue;
+        }
         if (!strcmp(key, "pump_jobs")) {
             char* end = NULL;
             pump_jobs = strtol(v, &end, 10);
@@ -106,10 +155,32 @@ int main(int argc, char** argv) {
     if (njobs > 0 && pump) { usage(); return 2; }
     if (pump_jobs > 0 && (!pump || njobs > 0)) { usage(); return 2; }
     if (output_batch >= 0 && njobs < 1) { usage(); return 2; }
+    if (naxes > 0 && (njobs < 1 || pump)) { usage(); return 2; }
+    long npoints = 1;
+    for (int o = 0; o < naxes; ++o) {
+        npoints *= axes[o].n;
+        if (npoints * njobs > kSweepMax) { usage(); return 2; }
+    }
     if (!seed_given) p.seed = (uint32_t)(time(NULL) + job);   // SpeedUp:1219
     if (njobs > 0) {
         mdqt_ensemble* e = NULL;
-        if (mdqt_ensemble_create(&p, (int)njobs, &e)) {
+        int rc_create;
+        if (naxes > 0) {                                    // the points: the axes' product, the first axis slowest
+            static mdqt_params points[kSweepMax];
+            for (long q = 0; q < npoints; ++q) {
+                points[q] = p;
+                long rest = q;
+                for (int o = naxes - 1; o >= 0; --o) {
+                    *sweep_field(&points[q], axes[o].field) = axes[o].v[rest % axes[o].n];
+                    rest /= axes[o].n;
+                }
+            }
+            rc_create = mdqt_ensemble_create_sweep(points, (int)npoints, (int)njobs, &e);
+        } else {
+            rc_create = mdqt_ensemble_create(&p, (int)njobs, &e);
+        }
+        njobs *= npoints;                                   // the members
+        if (rc_create) {
             fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
             return 1;
         }

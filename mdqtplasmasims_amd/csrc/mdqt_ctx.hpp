@@ -236,6 +236,14 @@ struct mdqt_ensemble {
     bool timing = false;
     mdqt::LaunchTimer timers[2];                   // 0 = force launches, 1 = QT launches
     unsigned long long force_launches = 0;         // force launches issued by ens_forces (batched + the row members' own)
+    // a sweep ensemble (mdqt_ensemble_create_sweep): npoints parameter points x replicas, member k = point
+    // k / replicas; its QT launches are mdqt_ensemble_sweep_qt.hip's, which take the table per member
+    int npoints = 1;
+    bool sweep = false;                            // created through the sweep entry (one point included)
+    mdqt::DevBuf<mdqt::FastTab> dTabs;             // [npoints] the points' by-lane tables (their first replica's ftabL)
+    mdqt::DevBuf<int> dPoint;                      // [J] every member's point
+    std::vector<mdqt::FastTab> tabs_held;          // what they hold
+    std::vector<int> point_held;
     // the batched output() (mdqt_ensemble_output.cpp): the members' blocks, their results on the device (rows
     // [J][kObsRow] in dScr's layout, the packed columns [sum 4 N_k]) and the pinned slot they come back to
     int output_batch = 0;                          // option "output_batch": 1 = one pass for all members, 0 = member by member
@@ -351,12 +359,16 @@ int pump_read_conditions(mdqt_ctx* s, int c0);
 PumpSchedule pump_schedule(const mdqt_ctx* s);   // the pump time loop's, of a context or of an ensemble's member 0
 
 // mdqt_ensemble.cpp: the ensemble's machinery the pump ensemble reuses
-int ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, const char* what, bool pump);
+// members: npoints parameter points (mdqt_ensemble_create and the pump ensemble: one) x njobs replicas, point-major;
+// sweep: the ensemble owns the points' tables and launches the sweep QT kernels
+int ensemble_create(const mdqt_params* points, int npoints, int njobs, mdqt_ensemble** out, const char* what, bool pump,
+                    bool sweep = false);
 inline bool tagged(const mdqt_ctx* s) { return !s->spinUp.empty(); }   // measureSpinUps() has run (pump programs)
 int ens_check(const mdqt_ensemble* e, const char* what, bool pump = false);
 int ens_forces(mdqt_ensemble* e);
-// the fused step();qstep() (do_step 1) or qstep() (0) launches of every member: `launch` issues one
-using EnsQtLaunch = std::function<hipError_t(const SubstepArgs& first, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst)>;
+// the fused step();qstep() (do_step 1) or qstep() (0) launches of every member: `launch` issues one (blocks:
+// the host copies of the launch's blocks, member by member; 0 or, after set_error, -1)
+using EnsQtLaunch = std::function<int(const SubstepArgs* blocks, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst)>;
 int ens_qt_chunks(mdqt_ensemble* e, int n, int do_step, const EnsQtLaunch& launch);
 int ens_range_flags(mdqt_ensemble* e, bool drain = true);
 

@@ -122,16 +122,16 @@ int mdqt::ens_qt_chunks(mdqt_ensemble* e, int n, int do_step, const EnsQtLaunch&
         for (int k = 0; k < J; ++k) {
             mdqt_ctx* s = e->jobs[k];
             t = substep_args(s, h[k], m, do_step, do_qt, 1);
-            s->f_pending = false;
             maxn = std::max(maxn, h[k].n);
         }
         if (e->ring.send(idx, e->dSub, (size_t)J * sizeof(SubstepArgs), e->stream)) return -1;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (e->timing && e->timers[1].take(&e0, &e1)) return -1;
         int inst = 0;
-        HIPCHK(launch(h[0], maxn, e0, e1, &inst));
+        if (launch(h, maxn, e0, e1, &inst)) return -1;
         for (int k = 0; k < J; ++k) {
             mdqt_ctx* s = e->jobs[k];
+            s->f_pending = false;
             s->last_qt_kernel = inst;
             s->last_qt_nseg = h[k].nseg;
             s->t = t;
@@ -158,10 +158,48 @@ int mdqt::ens_range_flags(mdqt_ensemble* e, bool drain) {
 
 namespace {
 
+// A sweep ensemble's QT launch serves members with different parameters by ONE kernel instance, so before a
+// call changes anything the members' blocks of its first launch (m substeps) must agree on what the choice of
+// the instance reads (launch_substeps_r_sweep checks every launch again).  mdqt_ensemble_create_sweep's
+// fracOfSig rule keeps expdet_zero in step; an option set on one member only (qt_im01) ends up here.
+int sweep_check(mdqt_ensemble* e, int m, const char* what) {
+    const int J = (int)e->jobs.size();
+    const int do_qt = e->jobs[0]->p.qt_enabled ? 1 : 0;
+    if (m <= 0) return 0;
+    SubstepArgs a0, a;
+    substep_args(e->jobs[0], a0, m, 1, do_qt, 1);
+    for (int k = 1; k < J; ++k) {
+        substep_args(e->jobs[k], a, m, 1, do_qt, 1);
+        if (const char* field = sweep_choice_differs(a0, a))
+            return set_error("%s: job index %d differs from job index 0 in %s: one QT launch (one kernel instance) serves every "
+                             "member of a sweep ensemble; nothing was launched", what, k, field);
+    }
+    return 0;
+}
+
+// one sweep QT launch over the blocks at `dev` (host copies: h)
+int sweep_launch(mdqt_ensemble* e, const SubstepArgs* dev, const SubstepArgs* h, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst) {
+    int differs = -1;
+    const hipError_t r = launch_substeps_r_sweep(dev, h, (int)e->jobs.size(), maxn, e->dTabs, e->dPoint, e->qt_waves, e->stream,
+                                                 e0, e1, inst, &differs);
+    if (differs >= 0)
+        return set_error("the sweep ensemble's QT launch: job index %d differs from job index 0 in %s: one kernel instance "
+                         "serves every member; the launch was not issued", differs, sweep_choice_differs(h[0], h[differs]));
+    HIPCHK(r);
+    return 0;
+}
+
 // n x (step(); qstep()) of every member
 int ens_substeps(mdqt_ensemble* e, int n) {
-    return ens_qt_chunks(e, n, 1, [e](const SubstepArgs& first, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst) {
-        return launch_substeps_r_ens(e->dSub, first, (int)e->jobs.size(), maxn, e->jobs[0]->dFTab, e->qt_waves, e->stream, e0, e1, inst);
+    if (e->sweep) {
+        if (sweep_check(e, std::min(n, MAXSUB), "mdqt_ensemble_substeps")) return -1;
+        return ens_qt_chunks(e, n, 1, [e](const SubstepArgs* h, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst) {
+            return sweep_launch(e, e->dSub, h, maxn, e0, e1, inst);
+        });
+    }
+    return ens_qt_chunks(e, n, 1, [e](const SubstepArgs* h, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst) {
+        HIPCHK(launch_substeps_r_ens(e->dSub, h[0], (int)e->jobs.size(), maxn, e->jobs[0]->dFTab, e->qt_waves, e->stream, e0, e1, inst));
+        return 0;
     });
 }
 
@@ -177,6 +215,7 @@ int ens_md_steps(mdqt_ensemble* e, int n) {
     const int J = (int)e->jobs.size();
     const int ratio = e->jobs[0]->ratio, per_step = (ratio + MAXSUB - 1) / MAXSUB;
     const int do_qt = e->jobs[0]->p.qt_enabled ? 1 : 0;
+    if (e->sweep && n > 0 && sweep_check(e, std::min(ratio, MAXSUB), "mdqt_ensemble_md_steps")) return -1;   // before the forces
     bool tiles = true;
     for (const mdqt_ctx* s : e->jobs) tiles = tiles && s->use_n3;
     const int ahead = tiles ? std::min(64, e->sub_blocks / (J * per_step)) : 0;
@@ -224,8 +263,12 @@ int ens_md_steps(mdqt_ensemble* e, int n) {
             for (int c = 0; c < per_step; ++c, ++l) {
                 hipEvent_t e0 = nullptr, e1 = nullptr;
                 if (e->timing && e->timers[1].take(&e0, &e1)) return -1;
-                HIPCHK(launch_substeps_r_ens(e->dSub + (size_t)l * J, h[(size_t)l * J], J, maxn, e->jobs[0]->dFTab,
-                                             e->qt_waves, e->stream, e0, e1, &inst));
+                if (e->sweep) {
+                    if (sweep_launch(e, e->dSub + (size_t)l * J, h + (size_t)l * J, maxn, e0, e1, &inst)) return -1;
+                } else {
+                    HIPCHK(launch_substeps_r_ens(e->dSub + (size_t)l * J, h[(size_t)l * J], J, maxn, e->jobs[0]->dFTab,
+                                                 e->qt_waves, e->stream, e0, e1, &inst));
+                }
             }
         }
         for (int j = 0; j < J; ++j) {
@@ -249,6 +292,91 @@ extern "C" int mdqt_ensemble_job_params(const mdqt_params* base, int k, mdqt_par
     return 0;
 }
 
+namespace {
+
+// what mdqt_ensemble_create refuses in the parameters themselves (before any context or HIP call)
+int refuse_params(const mdqt_params* p, const char* what, bool pump) {
+    if (p->world_size != 1) return set_error("%s: world_size must be 1 (an ensemble's jobs are whole systems on one device)", what);
+    if (p->rng_mode != 1)
+        return set_error("%s: rng_mode must be 1 (Philox): the drand48 order needs one substep per launch "
+                         "and a resolve kernel per job", what);
+    if (!pump && p->qt_model != 0)
+        return set_error("%s: qt_model must be 0 (the SpeedUp program; the pump programs have mdqt_pump_ensemble_create)", what);
+    if (pump && (p->qt_model < 1 || p->qt_model > 3))
+        return set_error("%s: qt_model must be 1, 2 or 3 (the optical-pumping programs)", what);
+    return 0;
+}
+
+// The swept fields, and the name of the first other field in which b differs from a (nullptr: none).  Field by
+// field: the struct has padding.
+constexpr int kSweepFields = 5;
+const char* const kSweepName[kSweepFields] = {"detuning", "detuningDP", "Om", "OmDP", "fracOfSig"};
+double sweep_field(const mdqt_params& p, int f) {
+    const double v[kSweepFields] = {p.detuning, p.detuningDP, p.Om, p.OmDP, p.fracOfSig};
+    return v[f];
+}
+const char* fixed_field_differs(const mdqt_params& a, const mdqt_params& b) {
+#define FIXED(name) if (memcmp(&a.name, &b.name, sizeof a.name)) return #name;
+    FIXED(Ge) FIXED(tmax) FIXED(density) FIXED(sig0) FIXED(Te) FIXED(N0) FIXED(newRun) FIXED(c0) FIXED(sampleFreq)
+    FIXED(reNormalizewvFns) FIXED(qt_enabled) FIXED(rng_mode) FIXED(seed) FIXED(job) FIXED(device) FIXED(world_size)
+    FIXED(rank) FIXED(force_segments) FIXED(qt_model) FIXED(tpumpreal) FIXED(tstartV0)
+#undef FIXED
+    if (strncmp(a.saveDirectory, b.saveDirectory, sizeof a.saveDirectory)) return "saveDirectory";
+    return nullptr;
+}
+
+// mdqt_ensemble_create_sweep's refusals: host arithmetic only
+int sweep_validate(const mdqt_params* pts, int npoints, int njobs, const char* what) {
+    if (!pts) return set_error("%s: NULL argument", what);
+    if (npoints < 1) return set_error("%s: npoints must be >= 1", what);
+    if (njobs < 1) return set_error("%s: njobs must be >= 1", what);
+    if ((long long)npoints * njobs > kEnsembleMaxJobs)
+        return set_error("%s: npoints x njobs = %lld members, more than %d", what, (long long)npoints * njobs, kEnsembleMaxJobs);
+    if (refuse_params(pts, what, false)) return -1;
+    for (int q = 1; q < npoints; ++q) {
+        if (const char* f = fixed_field_differs(pts[0], pts[q]))
+            return set_error("%s: point %d differs from point 0 in %s: only detuning, detuningDP, Om, OmDP and fracOfSig "
+                             "may differ between the points (the others fix the box, the substep ratio, t and the outputs "
+                             "of every member)", what, q, f);
+        if ((pts[q].fracOfSig == 0.) != (pts[0].fracOfSig == 0.))
+            return set_error("%s: point %d has fracOfSig %g and point 0 has %g: a point with fracOfSig == 0 runs the QT kernel "
+                             "instance without the expansion detuning, one with fracOfSig != 0 cannot, and one launch is one "
+                             "instance (splitting a launch by instance is not supported: run the two groups as two ensembles)",
+                             what, q, pts[q].fracOfSig, pts[0].fracOfSig);
+    }
+    for (int q = 1; q < npoints; ++q)
+        for (int o = 0; o < q; ++o) {
+            int same = 0, collide = 0, first = -1;
+            for (int f = 0; f < kSweepFields; ++f) {
+                const double a = sweep_field(pts[o], f), b = sweep_field(pts[q], f);
+                same += !memcmp(&a, &b, sizeof a) || a == b;
+                collide += ref_udcast(a * 100) == ref_udcast(b * 100);     // mdqt_setup_directories' name
+                if (first < 0 && !(!memcmp(&a, &b, sizeof a) || a == b)) first = f;
+            }
+            if (same == kSweepFields)
+                return set_error("%s: point %d is identical to point %d (detuning, detuningDP, Om, OmDP and fracOfSig all equal): "
+                                 "both would write the same run directories", what, q, o);
+            if (collide == kSweepFields)
+                return set_error("%s: point %d and point %d give the same run directory name: %s %.17g and %.17g print alike "
+                                 "(the name holds the fields x 100 as integers)", what, q, o, kSweepName[first],
+                                 sweep_field(pts[q], first), sweep_field(pts[o], first));
+        }
+    return 0;
+}
+
+// the points' tables and the members' point indices, uploaded when they differ from what the device holds
+int sweep_upload(mdqt_ensemble* e) {
+    const int J = (int)e->jobs.size(), R = J / e->npoints;
+    std::vector<FastTab> tabs((size_t)e->npoints);
+    std::vector<int> point((size_t)J);
+    for (int q = 0; q < e->npoints; ++q) tabs[(size_t)q] = e->jobs[(size_t)q * R]->ftabL;
+    for (int k = 0; k < J; ++k) point[(size_t)k] = k / R;
+    return e->ring.send_if_changed(tabs, e->tabs_held, e->dTabs, e->stream) ||
+           e->ring.send_if_changed(point, e->point_held, e->dPoint, e->stream);
+}
+
+}  // namespace
+
 extern "C" void mdqt_ensemble_destroy(mdqt_ensemble* e) {
     if (!e) return;
     (void)hipSetDevice(e->dev);
@@ -262,20 +390,21 @@ extern "C" void mdqt_ensemble_destroy(mdqt_ensemble* e) {
 }
 
 // mdqt_ensemble_create, and the same members and machinery for mdqt_pump_ensemble_create (pump: qt_model 1-3)
-int mdqt::ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, const char* what, bool pump) {
+// The members are the points' replicas, point-major (one point: the jobs of mdqt_ensemble_create); sweep: the
+// caller has validated the points (sweep_validate).
+int mdqt::ensemble_create(const mdqt_params* p, int npoints, int replicas, mdqt_ensemble** out, const char* what, bool pump,
+                          bool sweep) {
     if (!p || !out) return set_error("%s: NULL argument", what);
     *out = nullptr;
-    if (njobs < 1 || njobs > kEnsembleMaxJobs) return set_error("%s: njobs must be 1 .. %d", what, kEnsembleMaxJobs);
-    if (p->world_size != 1) return set_error("%s: world_size must be 1 (an ensemble's jobs are whole systems on one device)", what);
-    if (p->rng_mode != 1)
-        return set_error("%s: rng_mode must be 1 (Philox): the drand48 order needs one substep per launch "
-                         "and a resolve kernel per job", what);
-    if (!pump && p->qt_model != 0)
-        return set_error("%s: qt_model must be 0 (the SpeedUp program; the pump programs have mdqt_pump_ensemble_create)", what);
-    if (pump && (p->qt_model < 1 || p->qt_model > 3))
-        return set_error("%s: qt_model must be 1, 2 or 3 (the optical-pumping programs)", what);
+    if (replicas < 1 || replicas > kEnsembleMaxJobs) return set_error("%s: njobs must be 1 .. %d", what, kEnsembleMaxJobs);
+    if (npoints < 1 || (long long)npoints * replicas > kEnsembleMaxJobs)
+        return set_error("%s: npoints x njobs must be 1 .. %d", what, kEnsembleMaxJobs);
+    if (refuse_params(p, what, pump)) return -1;
+    const int njobs = npoints * replicas;
     std::unique_ptr<mdqt_ensemble, void (*)(mdqt_ensemble*)> e(new (std::nothrow) mdqt_ensemble(), mdqt_ensemble_destroy);
     if (!e) return set_error("%s: out of memory", what);
+    e->npoints = npoints;
+    e->sweep = sweep;
     try {
         e->jobs.reserve((size_t)njobs);
         e->writer.reset(new FileWriter(std::min(16, 4 * njobs)));
@@ -285,7 +414,7 @@ int mdqt::ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, 
     for (int k = 0; k < njobs; ++k) {
         mdqt_params pk;
         mdqt_ctx* s = nullptr;
-        if (mdqt_ensemble_job_params(p, k, &pk) || mdqt_create(&pk, &s)) return -1;
+        if (mdqt_ensemble_job_params(p + k / replicas, k % replicas, &pk) || mdqt_create(&pk, &s)) return -1;
         e->jobs.push_back(s);
         s->shared_writer = e->writer.get();
         if (k == 0) { e->dev = s->dev; e->stream = s->own; }
@@ -295,17 +424,41 @@ int mdqt::ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out, 
     }
     HIPCHK(hipSetDevice(e->dev));
     e->sub_blocks = std::max(njobs, 1024);
-    const size_t slot_bytes = std::max((size_t)e->sub_blocks * sizeof(SubstepArgs), (size_t)njobs * sizeof(N3Args));
+    size_t slot_bytes = std::max((size_t)e->sub_blocks * sizeof(SubstepArgs), (size_t)njobs * sizeof(N3Args));
+    if (sweep) slot_bytes = std::max(slot_bytes, (size_t)npoints * sizeof(FastTab));   // (the point indices are smaller)
     if (e->dForce.alloc((size_t)njobs) != hipSuccess || e->dSub.alloc((size_t)e->sub_blocks) != hipSuccess)
         return set_error("%s: allocating the argument blocks of %d jobs failed", what, njobs);
     if (e->ring.create(slot_bytes, kRingSlots, hipEventDisableTiming | hipEventDisableSystemFence)) return -1;
+    if (sweep) {
+        if (e->dTabs.alloc((size_t)npoints) != hipSuccess || e->dPoint.alloc((size_t)njobs) != hipSuccess)
+            return set_error("%s: allocating the tables of %d points failed", what, npoints);
+        if (sweep_upload(e.get())) return -1;
+    }
     *out = e.release();
     return 0;
 }
 
 extern "C" int mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemble** out) {
-    return ensemble_create(p, njobs, out, "mdqt_ensemble_create", false);
+    return ensemble_create(p, 1, njobs, out, "mdqt_ensemble_create", false);
 }
+
+// member k of a sweep: point k / njobs, replica k % njobs (job + r, seed + r as mdqt_ensemble_job_params)
+extern "C" int mdqt_ensemble_sweep_params(const mdqt_params* points, int npoints, int njobs, int k, mdqt_params* out) {
+    if (!points || !out) return set_error("mdqt_ensemble_sweep_params: NULL argument");
+    if (sweep_validate(points, npoints, njobs, "mdqt_ensemble_sweep_params")) return -1;
+    if (k < 0 || k >= npoints * njobs)
+        return set_error("mdqt_ensemble_sweep_params: job index %d outside [0, %d)", k, npoints * njobs);
+    return mdqt_ensemble_job_params(points + k / njobs, k % njobs, out);
+}
+
+extern "C" int mdqt_ensemble_create_sweep(const mdqt_params* points, int npoints, int njobs, mdqt_ensemble** out) {
+    if (!points || !out) return set_error("mdqt_ensemble_create_sweep: NULL argument");
+    *out = nullptr;
+    if (sweep_validate(points, npoints, njobs, "mdqt_ensemble_create_sweep")) return -1;
+    return ensemble_create(points, npoints, njobs, out, "mdqt_ensemble_create_sweep", false, true);
+}
+
+extern "C" int mdqt_ensemble_points(const mdqt_ensemble* e) { return e ? e->npoints : -1; }
 
 extern "C" int mdqt_ensemble_size(const mdqt_ensemble* e) { return e ? (int)e->jobs.size() : -1; }
 
@@ -331,6 +484,10 @@ extern "C" int mdqt_ensemble_set_option(mdqt_ensemble* e, const char* name, int 
     }
     for (mdqt_ctx* s : e->jobs)
         if (mdqt_set_option(s, name, value)) return -1;
+    if (e->sweep) {                                 // an option may rebuild the members' tables: the points' copies follow
+        HIPCHK(hipSetDevice(e->dev));
+        if (sweep_upload(e)) return -1;
+    }
     return 0;
 }
 
@@ -376,6 +533,7 @@ extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
     for (mdqt_ctx* s : e->jobs)                         // one after the other, as mdqt_ensemble_init
         if (fresh ? mdqt_init(s) : mdqt_read_conditions(s, s->p.c0)) return -1;
     if (ens_check(e, "mdqt_ensemble_run")) return -1;
+    if (e->sweep && sweep_check(e, std::min(e->jobs[0]->ratio, MAXSUB), "mdqt_ensemble_run")) return -1;
     HIPCHK(hipSetDevice(e->dev));
     struct {                                            // the loop's driver: one batched call over the members
         mdqt_ensemble* e;

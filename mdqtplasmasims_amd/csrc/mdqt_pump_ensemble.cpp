@@ -82,11 +82,11 @@ int pump_step(mdqt_pump_ensemble* pe, bool lead, bool fold) {
 
 // n x qstep() of every member (QT only: run_substeps(s, n, 0, 1, 1)), chunks of at most MAXSUB
 int pump_qsteps(mdqt_pump_ensemble* pe, int n) {
-    return ens_qt_chunks(pe->base, n, 0, [pe](const SubstepArgs& first, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst) {
+    return ens_qt_chunks(pe->base, n, 0, [pe](const SubstepArgs* h, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst) {
         mdqt_ensemble* e = pe->base;
-        const hipError_t r = launch_substeps_pump_ens(e->dSub, first, (int)e->jobs.size(), maxn, e->jobs[0]->dFTab, e->stream, e0, e1, inst);
-        if (r == hipSuccess) pe->launches++;
-        return r;
+        HIPCHK(launch_substeps_pump_ens(e->dSub, h[0], (int)e->jobs.size(), maxn, e->jobs[0]->dFTab, e->stream, e0, e1, inst));
+        pe->launches++;
+        return 0;
     });
 }
 
@@ -223,7 +223,7 @@ extern "C" int mdqt_pump_ensemble_create(const mdqt_params* p, int njobs, mdqt_p
     std::unique_ptr<mdqt_pump_ensemble, void (*)(mdqt_pump_ensemble*)> pe(new (std::nothrow) mdqt_pump_ensemble(),
                                                                          mdqt_pump_ensemble_destroy);
     if (!pe) return set_error("mdqt_pump_ensemble_create: out of memory");
-    if (ensemble_create(p, njobs, &pe->base, "mdqt_pump_ensemble_create", true)) return -1;
+    if (ensemble_create(p, 1, njobs, &pe->base, "mdqt_pump_ensemble_create", true)) return -1;
     HIPCHK(hipSetDevice(pe->base->dev));
     if (pe->dStep[0].alloc((size_t)njobs) != hipSuccess || pe->dStep[1].alloc((size_t)njobs) != hipSuccess ||
         pe->dTag.alloc((size_t)njobs) != hipSuccess || pe->dKde.alloc((size_t)njobs) != hipSuccess)

@@ -22,6 +22,7 @@ state is bit for bit what :class:`~mdqtplasmasims_amd.engine.Simulation` gives f
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 
 import numpy as np
 
@@ -34,6 +35,43 @@ def job_params(base: MdqtParams, k: int) -> MdqtParams:
     """job k's parameters of an ensemble created from `base` (job + k, seed + k; host only)"""
     out = MdqtParams()
     check(lib().mdqt_ensemble_job_params(C.byref(base), int(k), C.byref(out)), "ensemble_job_params")
+    return out
+
+
+SWEEP_FIELDS = ("detuning", "detuningDP", "Om", "OmDP", "fracOfSig")
+
+
+def _sweep_points(base: MdqtParams, sweep):
+    """(the points' swept values as dicts, the points as a C array): the Cartesian product of the lists of
+    `sweep` ({name: values}), the first-named axis slowest — or, where `sweep` is a list of {name: value} dicts,
+    those points as they stand; every other field from `base`"""
+    if isinstance(sweep, dict):
+        names = list(sweep)
+        for name in names:
+            if len(sweep[name]) < 1:
+                raise ValueError(f"sweep: no values for {name!r}")
+        values = [dict(zip(names, v)) for v in itertools.product(*(sweep[n] for n in names))]
+    else:
+        values = [dict(point) for point in sweep]
+        if not values:
+            raise ValueError("sweep: no points")
+    for name in {n for point in values for n in point}:
+        if name not in SWEEP_FIELDS:
+            raise ValueError(f"sweep: {name!r} is not one of {', '.join(SWEEP_FIELDS)}")
+    arr = (MdqtParams * len(values))()
+    for q, point in enumerate(values):
+        C.memmove(C.byref(arr[q]), C.byref(base), C.sizeof(MdqtParams))
+        for name, v in point.items():
+            setattr(arr[q], name, float(v))
+    return values, arr
+
+
+def sweep_params(base: MdqtParams, sweep, njobs: int, k: int) -> MdqtParams:
+    """member k's parameters of a sweep ensemble of `njobs` replicas per point (point k // njobs, replica k % njobs:
+    job + r, seed + r), after the checks mdqt_ensemble_create_sweep makes of the points (host only)"""
+    _, arr = _sweep_points(base, sweep)
+    out = MdqtParams()
+    check(lib().mdqt_ensemble_sweep_params(arr, len(arr), int(njobs), int(k), C.byref(out)), "ensemble_sweep_params")
     return out
 
 
@@ -50,17 +88,36 @@ class _Member(Simulation):
 
 
 class Ensemble(_EnsembleBase):
-    """``njobs`` independent jobs (job + k, seed + k) resident on one MI355X, stepped together."""
+    """``njobs`` independent jobs (job + k, seed + k) resident on one MI355X, stepped together.
+
+    ``sweep={"detuningDP": [0.0, 1.0], "Om": [0.5, 1.0]}`` makes it a parameter scan (mdqt_ensemble_create_sweep):
+    the points are the product of the lists (the first name slowest) — or, given as a list of dicts, those points —
+    each with ``njobs`` replicas; ``jobs`` is flat in member order (point-major), ``points`` lists the swept
+    values, ``member(p, r)`` is replica r of point p.
+    """
 
     _DESTROY = "mdqt_ensemble_destroy"
 
-    def __init__(self, njobs: int, **params):
+    def __init__(self, njobs: int, sweep=None, **params):
         self.params = default_params(**params)
+        self.njobs = int(njobs)
         h = C.c_void_p()
-        check(lib().mdqt_ensemble_create(C.byref(self.params), int(njobs), C.byref(h)), "mdqt_ensemble_create")
+        if sweep is None:
+            self.points = [{}]
+            check(lib().mdqt_ensemble_create(C.byref(self.params), self.njobs, C.byref(h)), "mdqt_ensemble_create")
+            member = [job_params(self.params, k) for k in range(lib().mdqt_ensemble_size(h))]
+        else:
+            self.points, arr = _sweep_points(self.params, sweep)
+            check(lib().mdqt_ensemble_create_sweep(arr, len(arr), self.njobs, C.byref(h)), "mdqt_ensemble_create_sweep")
+            member = [job_params(arr[k // self.njobs], k % self.njobs) for k in range(lib().mdqt_ensemble_size(h))]
         self.h = h
-        self.jobs = [_Member(self, lib().mdqt_ensemble_job(h, k), job_params(self.params, k))
-                     for k in range(lib().mdqt_ensemble_size(h))]
+        self.jobs = [_Member(self, lib().mdqt_ensemble_job(h, k), p) for k, p in enumerate(member)]
+
+    def member(self, p: int, r: int):
+        """replica r of point p (``jobs[p * njobs + r]``)"""
+        if not (0 <= p < len(self.points) and 0 <= r < self.njobs):
+            raise IndexError(f"member({p}, {r}) of {len(self.points)} points x {self.njobs} replicas")
+        return self.jobs[p * self.njobs + r]
 
     @property
     def N(self):
@@ -137,4 +194,4 @@ class Ensemble(_EnsembleBase):
                                  "potential_ms", "n_potential", "kde_ms", "n_kde", "potential_median_ms", "kde_median_ms"))
 
 
-__all__ = ["Ensemble", "job_params"]
+__all__ = ["Ensemble", "job_params", "sweep_params", "SWEEP_FIELDS"]

@@ -17,6 +17,8 @@ Prints ONE JSON line:
              fractions as the project counts them (QT 1,750 flop per particle-qstep, force 30 flop per
              pair, N (N - 1) / 2 pairs per job; against 78.6 TF)
 Rates are particle-qsteps/s summed over the jobs.  Any error exits non-zero; there is no CPU fallback.
+--sweep NAME:v1,v2 makes the ensembles sweep ensembles (parameter points x jobs, J members in all): one value times
+the sweep QT kernels on the uniform ensemble's own jobs, two or more a scan of the same J.
 
 --mode output measures output() of all members instead: per J in --jobs, --outputs outputs --every MD steps
 apart after --skip uncounted ones, the wall time (ms, median / min / max over the outputs) of
@@ -113,6 +115,10 @@ def main():
                     "window of one C2 job is 4 ms and measures the clock ramp as much as the kernels)")
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--qt-waves", type=int, default=0, help="Ensemble option qt_waves (0, 3)")
+    ap.add_argument("--sweep", action="append", default=[], metavar="NAME:v1,v2",
+                    help="--mode rate: the ensembles are sweep ensembles (Ensemble(sweep=...)) of J members in all: the\n"
+                    "points are the product of the lists (may be given per NAME), J / points jobs each; one value\n"
+                    "= the sweep kernels on the uniform ensemble's jobs")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--mode", choices=["rate", "output"], default="rate")
     ap.add_argument("--outputs", type=int, default=25, help="--mode output: timed outputs")
@@ -125,8 +131,21 @@ def main():
     params = dict(CONFIGS[a.config], device=a.device)
     jobs = [int(x) for x in a.jobs.split(",") if x]
     streams = [int(x) for x in a.streams.split(",") if x]
+    sweep = {}
+    for item in a.sweep:
+        name, _, values = item.partition(":")
+        if name in sweep or not values:
+            ap.error(f"--sweep {item}: NAME:v1,v2,..., each NAME once")
+        sweep[name] = [float(v) for v in values.split(",")]
+    npoints = 1
+    for values in sweep.values():
+        npoints *= len(values)
+    if any(J % npoints for J in jobs) and sweep and a.mode == "rate":
+        ap.error(f"--sweep: every J of --jobs must be a multiple of the {npoints} points")
     out = dict(tool="mdqt_ensemble_rate", config=a.config, steps=a.steps, warmup=a.warmup, qt_waves=a.qt_waves,
                unit="particle-qsteps/s", fp64_peak=FP64_PEAK)
+    if sweep:
+        out["sweep"] = sweep
     if a.mode == "output":
         output_mode(M, a, params, jobs, out)
         out["unit"] = "ms per output of all members"
@@ -174,7 +193,8 @@ def main():
     # the ensemble
     out["ensemble"] = []
     for J in jobs:
-        with M.Ensemble(njobs=J, seed=12346, job=1, **params) as e:
+        with (M.Ensemble(njobs=J // npoints, sweep=sweep, seed=12346, job=1, **params) if sweep else
+              M.Ensemble(njobs=J, seed=12346, job=1, **params)) as e:
             if a.qt_waves:
                 e.set_option("qt_waves", a.qt_waves)
             e.init()
