@@ -11,6 +11,15 @@
  * job .. job + njobs - 1) and steps them in one launch.  Job k is exactly the single-job context
  * with job = k: same velocities, same draws, same files, bit for bit.
  *
+ * Parameter scan: the reference is recompiled and rerun for every laser setting, into the tree
+ * Om%d/Det%dNumIons%dInitialTemp%duK/job%d/ (LC3:371-380).  mdlc_create_sweep holds npoints parameter points x
+ * R replicas (R = njobs) in one context, stepped in one set of launches.  Member k is point k / R, replica
+ * r = k % R (point-major), and is exactly the single-job context of that point's parameters with job = job + r.
+ * The points may differ in detuning, Om and temperature (the fields the directory name has a level for) and in
+ * nothing else.  All points share seed and job, so replica r of every point draws the same u1 / randDir stream
+ * (common random numbers), and where the temperature is equal it starts from the same velocities.  Every entry
+ * point below works on such a context; where a buffer is job-major it is member-major.
+ *
  * RNG.  Velocities: the reference's std::mt19937 (seeded from std::random_device, LC3:45-46; here
  * job number j's engine is mt19937(seed + j), as the reference's srand48(time + job), LC3:389)
  * with its std::normal_distribution (LC3:83), consumed in init()'s order after the one uniform
@@ -58,8 +67,18 @@ typedef struct mdlc_ctx mdlc_ctx;
 void        mdlc_default_params(mdlc_params* p);               /* LC3:54-88, :393 defaults      */
 int         mdlc_create(const mdlc_params* p, mdlc_ctx** out);
 void        mdlc_destroy(mdlc_ctx* c);
-/* "N0", "njobs", "dt", "stride" (ions per job padded to whole workgroups), "iterations" and
- * "outputs" (main()'s loop counts for tmax, dt, sampleFreq), "qstep_index" */
+/* A parameter scan: points[npoints], each with R = points[0].njobs replicas; members point-major.  Refused,
+ * before any GPU call and naming the point and the field: npoints < 1; a point that mdlc_create refuses; a
+ * field other than detuning, Om and temperature that differs from point 0; two identical points; two points
+ * whose directory names collide (Om x 100, detuning x 100 and temperature x 1000000 as integers: detuning
+ * -0.501 and -0.502); more than one launch grid of workgroups. */
+int         mdlc_create_sweep(const mdlc_params* points, int npoints, mdlc_ctx** out);
+/* member k's parameters as a single job (its point's fields, job + r, njobs = 1), after the same refusals;
+ * without a context or a GPU */
+int         mdlc_sweep_params(const mdlc_params* points, int npoints, int k, mdlc_params* out);
+/* "N0", "njobs" (the replicas R of a scan), "npoints" (1 unless a scan), "members" (npoints x njobs), "dt",
+ * "stride" (ions per job padded to whole workgroups), "iterations" and "outputs" (main()'s loop counts for
+ * tmax, dt, sampleFreq), "qstep_index" */
 double      mdlc_get_const(const mdlc_ctx* c, const char* name);
 
 /* init()'s velocity draws (:119-124) for one job, without a context or a GPU: V [3][N0] from

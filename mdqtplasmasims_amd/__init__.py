@@ -14,8 +14,8 @@ from ._lib import MdqtError, LIB_PATH, CLI_PATH  # noqa: F401
 from .engine import Simulation, default_params, device_count, slab  # noqa: F401
 from .ensemble import Ensemble, job_params, sweep_params  # noqa: F401
 from .pump_ensemble import PumpEnsemble  # noqa: F401
-from .mdlc import LaserCooling, default_params as mdlc_default_params  # noqa: F401
+from .mdlc import LaserCooling, default_params as mdlc_default_params, sweep_params as mdlc_sweep_params  # noqa: F401
 from .mdmc_ensemble import MonteCarloEnsemble, mdmc_job_params  # noqa: F401
 
 __all__ = ["Simulation", "Ensemble", "job_params", "sweep_params", "MdqtError", "default_params", "device_count", "slab", "LIB_PATH", "CLI_PATH",
-           "LaserCooling", "mdlc_default_params", "MonteCarloEnsemble", "mdmc_job_params", "PumpEnsemble"]
+           "LaserCooling", "mdlc_default_params", "mdlc_sweep_params", "MonteCarloEnsemble", "mdmc_job_params", "PumpEnsemble"]

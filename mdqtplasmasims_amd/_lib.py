@@ -69,6 +69,9 @@ _u64p = C.POINTER(C.c_uint64)
 MDLC_SIGNATURES = [
     ("mdlc_default_params", None, [C.POINTER(MdlcParams)]),
     ("mdlc_create", C.c_int, [C.POINTER(MdlcParams), C.POINTER(C.c_void_p)]),
+    # a parameter scan: points x replicas (points: an array of MdlcParams)
+    ("mdlc_create_sweep", C.c_int, [C.POINTER(MdlcParams), C.c_int, C.POINTER(C.c_void_p)]),
+    ("mdlc_sweep_params", C.c_int, [C.POINTER(MdlcParams), C.c_int, C.c_int, C.POINTER(MdlcParams)]),
     ("mdlc_destroy", None, [C.c_void_p]),
     ("mdlc_get_const", C.c_double, [C.c_void_p, C.c_char_p]),
     ("mdlc_sample_velocities", C.c_int, [C.c_uint32, C.c_int, C.c_double, _dp]),

@@ -1,7 +1,8 @@
 // Host engine of the three-level laser-cooling program (laserCoolNoPlasmaThreeState.cpp, "LC3"):
 // the C ABI of include/mdlc.h.  Owns the device-resident state of an ensemble of jobs (vx, psi,
 // tPart), draws init()'s velocities from the reference's std::mt19937 stream, drives the gfx950
-// kernels of mdlc_kernels.hip and reproduces main()'s loop, directories and energies.dat.
+// kernels of mdlc_kernels.hip and reproduces main()'s loop, directories and energies.dat.  A parameter scan
+// (mdlc_create_sweep) is the same context over npoints x R members, stepped by mdlc_sweep_kernels.hip.
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
@@ -20,8 +21,12 @@
 using namespace mdqt;
 
 struct mdlc_ctx {
-    mdlc_params p;
-    int N0 = 0, J = 0, S = 0, B = 0;
+    mdlc_params p;                     // point 0: the fixed fields of every member
+    std::vector<mdlc_params> pts;      // [npoints] the parameter points (an ordinary context: p alone)
+    int npoints = 1, R = 0;            // members: npoints x R, point-major (member k: point k / R, job p.job + k % R)
+    bool sweep = false;                // made by mdlc_create_sweep: stepped by k_lc_steps_sweep
+    DevBuf<LCPoint> dPts;              // [npoints] the points' laser constants, written once at create
+    int N0 = 0, J = 0, S = 0, B = 0;   // J: the members
     int dev = 0;
     hipStream_t st = nullptr;
     DevBuf<double> dVx, dPsi, dTp, dPart, dEk;
@@ -36,19 +41,92 @@ namespace {
 constexpr int kMaxLaunchSteps = 8192;  // steps per launch (a few ms): a launch's length never follows tmax
 constexpr int kChunk = 512;            // output intervals between two host synchronisations of mdlc_run
 
-int check_params(const mdlc_params* p) {
-    if (p->N0 < 1) return set_error("N0 must be >= 1");
-    if (p->njobs < 1) return set_error("njobs must be >= 1");
-    if (!(p->dt > 0)) return set_error("dt must be positive");
-    if (p->sampleFreq < 1) return set_error("sampleFreq must be >= 1");
-    if (!(p->temperature >= 0)) return set_error("temperature must be >= 0");
+constexpr long long kMaxGrid = 0x7fffffffLL;   // workgroups of one launch
+
+// what is wrong with p (nullptr: nothing)
+const char* params_refusal(const mdlc_params* p) {
+    if (p->N0 < 1) return "N0 must be >= 1";
+    if (p->njobs < 1) return "njobs must be >= 1";
+    if (!(p->dt > 0)) return "dt must be positive";
+    if (p->sampleFreq < 1) return "sampleFreq must be >= 1";
+    if (!(p->temperature >= 0)) return "temperature must be >= 0";
     const long long S = ((long long)p->N0 + kLCBlock - 1) / kLCBlock * kLCBlock;
-    if (S * p->njobs / kLCBlock > 0x7fffffffLL) return set_error("N0 x njobs is too large for one launch grid");
+    if (S * p->njobs / kLCBlock > kMaxGrid) return "N0 x njobs is too large for one launch grid";
+    return nullptr;
+}
+
+int check_params(const mdlc_params* p) {
+    const char* r = params_refusal(p);
+    return r ? set_error("%s", r) : 0;
+}
+
+// The swept fields (the reference's directory name has a level for each, LC3:371-375, with these scales), and
+// the name of the first other field in which b differs from a (nullptr: none).  Field by field: the struct has
+// padding.
+constexpr int kSweepFields = 3;
+const char* const kSweepName[kSweepFields] = {"detuning", "Om", "temperature"};
+const double kSweepScale[kSweepFields] = {100, 100, 1000000};
+double sweep_field(const mdlc_params& p, int f) {
+    const double v[kSweepFields] = {p.detuning, p.Om, p.temperature};
+    return v[f];
+}
+const char* fixed_field_differs(const mdlc_params& a, const mdlc_params& b) {
+#define FIXED(name) if (memcmp(&a.name, &b.name, sizeof a.name)) return #name;
+    FIXED(N0) FIXED(tmax) FIXED(applyForce) FIXED(sampleFreq) FIXED(vKick) FIXED(dt) FIXED(seed) FIXED(job)
+    FIXED(device) FIXED(njobs)
+#undef FIXED
+    if (strncmp(a.saveDirectory, b.saveDirectory, sizeof a.saveDirectory)) return "saveDirectory";
+    return nullptr;
+}
+
+// mdlc_create_sweep's refusals: host arithmetic only
+int sweep_validate(const mdlc_params* pts, int npoints, const char* what) {
+    if (!pts) return set_error("%s: NULL argument", what);
+    if (npoints < 1) return set_error("%s: npoints must be >= 1", what);
+    for (int q = 0; q < npoints; ++q) {
+        if (const char* r = params_refusal(pts + q)) return set_error("%s: point %d: %s", what, q, r);
+        if (const char* f = fixed_field_differs(pts[0], pts[q]))
+            return set_error("%s: point %d differs from point 0 in %s: only detuning, Om and temperature may differ between "
+                             "the points (the others fix the stride, the loop counts, the outputs and the Philox keys of "
+                             "every member; the directory name has no level for vKick)", what, q, f);
+    }
+    for (int q = 1; q < npoints; ++q)
+        for (int o = 0; o < q; ++o) {
+            int same = 0, collide = 0, first = -1;
+            for (int f = 0; f < kSweepFields; ++f) {
+                const double a = sweep_field(pts[o], f), b = sweep_field(pts[q], f);
+                const bool eq = !memcmp(&a, &b, sizeof a) || a == b;
+                same += eq;
+                collide += ref_udcast(a * kSweepScale[f]) == ref_udcast(b * kSweepScale[f]);   // directory_levels' name
+                if (first < 0 && !eq) first = f;
+            }
+            if (same == kSweepFields)
+                return set_error("%s: point %d is identical to point %d (detuning, Om and temperature all equal): both would "
+                                 "write the same run directories", what, q, o);
+            if (collide == kSweepFields)
+                return set_error("%s: point %d and point %d give the same run directory name: %s %.17g and %.17g print alike "
+                                 "(the name holds Om x 100, detuning x 100 and temperature x 1000000 as integers)", what, q, o,
+                                 kSweepName[first], sweep_field(pts[q], first), sweep_field(pts[o], first));
+        }
+    const long long B = ((long long)pts[0].N0 + kLCBlock - 1) / kLCBlock;
+    if (B * pts[0].njobs * npoints > kMaxGrid)
+        return set_error("%s: npoints x njobs x workgroups per job = %d x %d x %lld is too large for one launch grid", what,
+                         npoints, pts[0].njobs, B);
     return 0;
+}
+
+// what differs between the points in LCArgs
+LCPoint laser_point(const mdlc_params& p) {
+    LCPoint l;
+    l.mi0 = p.dt * p.detuning;             // Im M11, M22 at v = 0: -dt (-detuning) (:192-193)
+    l.cim = p.dt * (p.Om / 2);             // -i dt (-Om/2) (:194)
+    l.ks = 1 * p.vKick * p.Om * p.dt;      // :189
+    return l;
 }
 
 LCArgs make_args(const mdlc_ctx* c, int nsteps) {
     const mdlc_params& p = c->p;
+    const LCPoint l = laser_point(p);      // (a scan's kernel reads its points' instead)
     LCArgs a;
     memset(&a, 0, sizeof a);
     a.vx = c->dVx; a.psi = c->dPsi; a.tPart = c->dTp; a.part = c->dPart;
@@ -56,18 +134,26 @@ LCArgs make_args(const mdlc_ctx* c, int nsteps) {
     a.q0 = c->qidx; a.seed = p.seed; a.job0 = p.job; a.applyForce = p.applyForce ? 1 : 0;
     a.dt = p.dt;
     a.mre = 1. - p.dt * 0.5;               // Re M11 = Re M22: 1 + dt Im(hamDecayTerm) (:203, :223)
-    a.mi0 = p.dt * p.detuning;             // Im M11, M22 at v = 0: -dt (-detuning) (:192-193)
-    a.cim = p.dt * (p.Om / 2);             // -i dt (-Om/2) (:194)
-    a.ks = 1 * p.vKick * p.Om * p.dt;      // :189
+    a.mi0 = l.mi0; a.cim = l.cim; a.ks = l.ks;
     a.vKick = p.vKick;
     return a;
 }
+
+// one launch of nsteps qsteps (0: the partial sums only) for every member
+hipError_t launch_steps(const mdlc_ctx* c, int nsteps, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+    if (c->npoints > 1 || c->sweep) return launch_lc_steps_sweep(make_args(c, nsteps), c->dPts, c->R, c->J, c->st, ev0, ev1);
+    return launch_lc_steps(make_args(c, nsteps), c->J, c->st, ev0, ev1);
+}
+
+// member k's point and job number
+const mdlc_params& member_point(const mdlc_ctx* c, int k) { return c->pts[(size_t)(k / c->R)]; }
+uint32_t member_job(const mdlc_ctx* c, int k) { return c->p.job + (uint32_t)(k % c->R); }
 
 // qstep() x n on the stream, in launches of at most kMaxLaunchSteps
 int qsteps_async(mdlc_ctx* c, long long n) {
     while (n > 0) {
         const int k = (int)(n < kMaxLaunchSteps ? n : kMaxLaunchSteps);
-        HIPCHK(launch_lc_steps(make_args(c, k), c->J, c->st));
+        HIPCHK(launch_steps(c, k));
         c->qidx += (uint64_t)k;
         n -= k;
     }
@@ -76,7 +162,7 @@ int qsteps_async(mdlc_ctx* c, long long n) {
 
 // EkinX of every job into dst[J] (device), from the last launch's workgroup partials
 int ekin_async(mdlc_ctx* c, double* dst, bool fresh) {
-    if (!fresh) HIPCHK(launch_lc_steps(make_args(c, 0), c->J, c->st));
+    if (!fresh) HIPCHK(launch_steps(c, 0));
     HIPCHK(launch_lc_ekin(c->dPart, c->J, c->B, c->N0, dst, c->st));
     return 0;
 }
@@ -151,17 +237,20 @@ extern "C" void mdlc_destroy(mdlc_ctx* c) {
     delete c;
 }
 
-extern "C" int mdlc_create(const mdlc_params* p, mdlc_ctx** out) {
-    if (!p || !out) return set_error("mdlc_create: NULL argument");
-    *out = nullptr;
-    if (check_params(p)) return -1;
+namespace {
+
+// mdlc_create (one point, its njobs jobs) and mdlc_create_sweep (the caller has validated the points)
+int create(const mdlc_params* p, int npoints, bool sweep, mdlc_ctx** out) {
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev < 1) return set_error("no HIP device available (%s)", hipGetErrorString(e));
     std::unique_ptr<mdlc_ctx, void (*)(mdlc_ctx*)> guard(new mdlc_ctx(), mdlc_destroy);
     mdlc_ctx* c = guard.get();
-    c->p = *p;
-    c->p.saveDirectory[sizeof(c->p.saveDirectory) - 1] = 0;
+    c->pts.assign(p, p + npoints);
+    for (auto& q : c->pts) q.saveDirectory[sizeof(q.saveDirectory) - 1] = 0;
+    c->p = c->pts[0];
+    c->npoints = npoints;
+    c->sweep = sweep;
     if (p->device >= 0) {
         if (p->device >= ndev) return set_error("device %d >= device count %d", p->device, ndev);
         c->dev = p->device;
@@ -171,12 +260,20 @@ extern "C" int mdlc_create(const mdlc_params* p, mdlc_ctx** out) {
     if (hipSetDevice(c->dev) != hipSuccess || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess)
         return set_error("cannot create a HIP stream on device %d", p->device);
     c->N0 = p->N0;
-    c->J = p->njobs;
+    c->R = p->njobs;
+    c->J = npoints * c->R;
     c->B = (p->N0 + kLCBlock - 1) / kLCBlock;
     c->S = c->B * kLCBlock;
     const size_t n = (size_t)c->J * c->S, sz = n * sizeof(double);
     bool ok = c->dVx.alloc(n) == hipSuccess && c->dPsi.alloc(6 * n) == hipSuccess && c->dTp.alloc(n) == hipSuccess &&
               c->dPart.alloc((size_t)c->J * c->B) == hipSuccess && c->dEk.alloc((size_t)kChunk * c->J) == hipSuccess;
+    if (sweep) {
+        std::vector<LCPoint> l;
+        for (const auto& q : c->pts) l.push_back(laser_point(q));
+        ok = ok && c->dPts.alloc((size_t)npoints) == hipSuccess &&
+             hipMemcpyAsync(c->dPts, l.data(), l.size() * sizeof(LCPoint), hipMemcpyHostToDevice, c->st) == hipSuccess &&
+             hipStreamSynchronize(c->st) == hipSuccess;
+    }
     if (!ok) return set_error("mdlc_create: device allocation failed");
     // the reference's globals start at zero (V, tPart, LC3:84, :91); psi gets its value in init()
     ok = hipMemsetAsync(c->dVx, 0, sz, c->st) == hipSuccess && hipMemsetAsync(c->dPsi, 0, 6 * sz, c->st) == hipSuccess &&
@@ -188,17 +285,48 @@ extern "C" int mdlc_create(const mdlc_params* p, mdlc_ctx** out) {
     c->dirs.resize(c->J);
     for (int k = 0; k < c->J; ++k) {
         std::string lv[4];
-        directory_levels(&c->p, c->p.job + (uint32_t)k, lv);
+        directory_levels(&member_point(c, k), member_job(c, k), lv);
         c->dirs[k] = lv[3];
     }
     *out = guard.release();
     return 0;
 }
 
+}  // namespace
+
+extern "C" int mdlc_create(const mdlc_params* p, mdlc_ctx** out) {
+    if (!p || !out) return set_error("mdlc_create: NULL argument");
+    *out = nullptr;
+    if (check_params(p)) return -1;
+    return create(p, 1, false, out);
+}
+
+// member k of a scan: point k / R, replica k % R (R = points[0].njobs), as the single job job + r
+extern "C" int mdlc_sweep_params(const mdlc_params* points, int npoints, int k, mdlc_params* out) {
+    if (!points || !out) return set_error("mdlc_sweep_params: NULL argument");
+    if (sweep_validate(points, npoints, "mdlc_sweep_params")) return -1;
+    const int R = points[0].njobs;
+    if (k < 0 || k >= (long long)npoints * R)
+        return set_error("mdlc_sweep_params: member index %d outside [0, %lld)", k, (long long)npoints * R);
+    *out = points[k / R];
+    out->job += (uint32_t)(k % R);
+    out->njobs = 1;
+    return 0;
+}
+
+extern "C" int mdlc_create_sweep(const mdlc_params* points, int npoints, mdlc_ctx** out) {
+    if (!points || !out) return set_error("mdlc_create_sweep: NULL argument");
+    *out = nullptr;
+    if (sweep_validate(points, npoints, "mdlc_create_sweep")) return -1;
+    return create(points, npoints, true, out);
+}
+
 extern "C" double mdlc_get_const(const mdlc_ctx* c, const char* n) {
     if (!c || !n) return NAN;
     if (!strcmp(n, "N0")) return c->N0;
-    if (!strcmp(n, "njobs")) return c->J;
+    if (!strcmp(n, "njobs")) return c->R;
+    if (!strcmp(n, "npoints")) return c->npoints;
+    if (!strcmp(n, "members")) return c->J;
     if (!strcmp(n, "dt")) return c->p.dt;
     if (!strcmp(n, "stride")) return c->S;
     if (!strcmp(n, "qstep_index")) return (double)c->qidx;
@@ -279,13 +407,15 @@ extern "C" int mdlc_get_state(mdlc_ctx* c, double* V, double* psi, double* tPart
     return 0;
 }
 
-// init() :115-131 for every job: job number j's velocities from mt19937(seed + j), psi = (1, 0, 0), tPart = 0
+// init() :115-131 for every member: job number j's velocities from mt19937(seed + j) at its point's temperature,
+// psi = (1, 0, 0), tPart = 0
 extern "C" int mdlc_init(mdlc_ctx* c) {
     if (!c) return set_error("NULL context");
     const int N0 = c->N0, J = c->J;
     std::vector<double> V((size_t)J * 3 * N0), psi((size_t)J * N0 * 6, 0.), tp((size_t)J * N0, 0.);
     for (int k = 0; k < J; ++k)
-        if (mdlc_sample_velocities(c->p.seed + (c->p.job + (uint32_t)k), N0, c->p.temperature, &V[(size_t)k * 3 * N0])) return -1;
+        if (mdlc_sample_velocities(c->p.seed + member_job(c, k), N0, member_point(c, k).temperature, &V[(size_t)k * 3 * N0]))
+            return -1;
     for (size_t i = 0; i < (size_t)J * N0; ++i) psi[6 * i] = 1.;          // :125
     const uint64_t q0 = 0;
     return mdlc_set_state(c, V.data(), psi.data(), tp.data(), &q0);
@@ -311,7 +441,7 @@ extern "C" int mdlc_time_qsteps(mdlc_ctx* c, int nsteps, int warmup, int launche
     for (auto& e : ev)
         if (hipEventCreate(&e) != hipSuccess) rc = set_error("mdlc_time_qsteps: cannot create an event");
     for (int l = 0; l < launches && !rc; ++l) {
-        if (launch_lc_steps(make_args(c, nsteps), c->J, c->st, ev[2 * l], ev[2 * l + 1]) != hipSuccess)
+        if (launch_steps(c, nsteps, ev[2 * l], ev[2 * l + 1]) != hipSuccess)
             rc = set_error("mdlc_time_qsteps: launch failed");
         else
             c->qidx += (uint64_t)nsteps;
@@ -341,7 +471,7 @@ extern "C" int mdlc_setup_directories(mdlc_ctx* c) {            // main() :364-3
     if (!c) return set_error("NULL context");
     for (int k = 0; k < c->J; ++k) {
         std::string lv[4];
-        directory_levels(&c->p, c->p.job + (uint32_t)k, lv);
+        directory_levels(&member_point(c, k), member_job(c, k), lv);
         for (int l = 0; l < 4; ++l) (void)mkdir(lv[l].c_str(), 0777);   // the reference ignores mkdir's result
         struct stat sb;
         if (stat(lv[3].c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))

@@ -591,6 +591,14 @@ struct LCArgs {
     double vKick;       // LC3:88, :279-284
 };
 hipError_t launch_lc_steps(const LCArgs& a, int J, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// A parameter scan (mdlc_create_sweep; mdlc_sweep_kernels.hip): what differs between the points in LCArgs.  The J
+// members are npoints x R, point-major: member m is point m / R, its Philox key (seed, job0 + m % R); a's mi0, cim
+// and ks are not read
+struct LCPoint {
+    double mi0, cim, ks;
+};
+hipError_t launch_lc_steps_sweep(const LCArgs& a, const LCPoint* pts, int R, int J, hipStream_t s,
+                                 hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // out[k] = (fixed-order sum of job k's B workgroup partials) / N0: output()'s EkinX (LC3:309-316)
 hipError_t launch_lc_ekin(const double* part, int J, int B, int N0, double* out, hipStream_t s);
 // pumping-model QT tables for another engine (mdqt_engine.cpp; used by the MC + MD tagging programs)

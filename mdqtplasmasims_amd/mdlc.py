@@ -6,6 +6,7 @@ no CPU fallback.  Method names follow the reference's functions.
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 
 import numpy as np
 
@@ -41,17 +42,78 @@ def format_directory(params: MdlcParams | None = None, job: int | None = None, *
     return buf.value.decode()
 
 
+SWEEP_FIELDS = ("detuning", "Om", "temperature")
+
+
+def _sweep_points(base: MdlcParams, sweep):
+    """(the points' swept values as dicts, the points as a C array): the Cartesian product of the lists of
+    `sweep` ({name: values}), the first-named axis slowest — or, where `sweep` is a list of {name: value} dicts,
+    those points as they stand; every other field from `base`"""
+    if isinstance(sweep, dict):
+        names = list(sweep)
+        for name in names:
+            if len(sweep[name]) < 1:
+                raise ValueError(f"sweep: no values for {name!r}")
+        values = [dict(zip(names, v)) for v in itertools.product(*(sweep[n] for n in names))]
+    else:
+        values = [dict(point) for point in sweep]
+        if not values:
+            raise ValueError("sweep: no points")
+    for name in {n for point in values for n in point}:
+        if name not in SWEEP_FIELDS:
+            raise ValueError(f"sweep: {name!r} is not one of {', '.join(SWEEP_FIELDS)}")
+    arr = (MdlcParams * len(values))()
+    for q, point in enumerate(values):
+        C.memmove(C.byref(arr[q]), C.byref(base), C.sizeof(MdlcParams))
+        for name, v in point.items():
+            setattr(arr[q], name, float(v))
+    return values, arr
+
+
+def sweep_params(points, k: int) -> MdlcParams:
+    """member k's parameters of a scan over `points` (a sequence of MdlcParams, each with njobs = R replicas) as a
+    single job: point k // R, replica k % R (job + r, njobs = 1), after the checks mdlc_create_sweep makes of
+    the points.  Runs without a GPU."""
+    arr = (MdlcParams * len(points))(*points) if len(points) else (MdlcParams * 1)()
+    out = MdlcParams()
+    check(lib().mdlc_sweep_params(arr, len(points), int(k), C.byref(out)), "mdlc_sweep_params")
+    return out
+
+
 class LaserCooling:
     """An ensemble of LC3 jobs resident on a GPU (vx, psi and tPart in HBM).  Arrays are
-    job-major: V (njobs, 3, N0), psi (njobs, N0, 3) complex, tPart (njobs, N0)."""
+    job-major: V (njobs, 3, N0), psi (njobs, N0, 3) complex, tPart (njobs, N0).
 
-    def __init__(self, params: MdlcParams | None = None, **over):
+    ``sweep={"detuning": [-0.5, -1.0], "Om": [0.5, 1.0]}`` makes it a parameter scan (mdlc_create_sweep): the
+    points are the product of the lists (the first name slowest) — or, given as a list of dicts, those points —
+    each with ``njobs`` replicas.  ``members`` = ``npoints`` x ``njobs`` and the arrays are member-major (member
+    k: point k // njobs, replica k % njobs); ``points`` lists the swept values, ``member_params(k)`` is member k
+    as a single job.  The points share seed and job: replica r of every point sees the same random numbers."""
+
+    def __init__(self, params: MdlcParams | None = None, sweep=None, **over):
         self.p = params if params is not None else default_params(**over)
         h = C.c_void_p()
-        check(lib().mdlc_create(C.byref(self.p), C.byref(h)), "mdlc_create")
+        if sweep is None:
+            self.points, self._points = [{}], (MdlcParams * 1)(self.p)
+            check(lib().mdlc_create(C.byref(self.p), C.byref(h)), "mdlc_create")
+        else:
+            self.points, self._points = _sweep_points(self.p, sweep)
+            check(lib().mdlc_create_sweep(self._points, len(self._points), C.byref(h)), "mdlc_create_sweep")
         self._h = h
         self.N0 = int(self.p.N0)
         self.njobs = int(self.p.njobs)
+        self.npoints = len(self._points)
+        self.members = self.npoints * self.njobs
+
+    def member_params(self, k: int) -> MdlcParams:
+        """member k as a single job: its point's parameters, job + k % njobs, njobs = 1"""
+        if not 0 <= int(k) < self.members:
+            raise IndexError(f"member index {k} outside [0, {self.members})")
+        out = MdlcParams()
+        C.memmove(C.byref(out), C.byref(self._points[int(k) // self.njobs]), C.sizeof(MdlcParams))
+        out.job += int(k) % self.njobs
+        out.njobs = 1
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -79,14 +141,14 @@ class LaserCooling:
         check(lib().mdlc_qsteps(self._h, int(n)), "mdlc_qsteps")
 
     def get_state(self) -> dict:
-        J, N = self.njobs, self.N0
+        J, N = self.members, self.N0
         V = np.zeros((J, 3, N)); a = np.zeros((J, N, 3, 2)); tp = np.zeros((J, N))
         q = C.c_uint64(0)
         check(lib().mdlc_get_state(self._h, dptr(V), dptr(a), dptr(tp), C.byref(q)), "mdlc_get_state")
         return {"V": V, "psi": a[..., 0] + 1j * a[..., 1], "tPart": tp, "q": int(q.value)}
 
     def set_state(self, V=None, psi=None, tPart=None, q=None):
-        J, N = self.njobs, self.N0
+        J, N = self.members, self.N0
 
         def arr(x, shape, what):
             if x is None:
@@ -104,19 +166,19 @@ class LaserCooling:
         check(lib().mdlc_set_state(self._h, dptr(V), dptr(psi), dptr(tPart), qq), "mdlc_set_state")
 
     def ekin_x(self) -> np.ndarray:                   # output()'s EkinX :309-316, per job
-        out = np.zeros(self.njobs)
+        out = np.zeros(self.members)
         check(lib().mdlc_ekin_x(self._h, dptr(out)), "mdlc_ekin_x")
         return out
 
     def save_directory(self, k: int = 0) -> str:
         d = lib().mdlc_save_directory(self._h, int(k))
         if d is None:
-            raise IndexError(f"job index {k} outside [0, {self.njobs})")
+            raise IndexError(f"job index {k} outside [0, {self.members})")
         return d.decode()
 
     def setup_directories(self) -> list:              # main() :364-380
         check(lib().mdlc_setup_directories(self._h), "mdlc_setup_directories")
-        return [self.save_directory(k) for k in range(self.njobs)]
+        return [self.save_directory(k) for k in range(self.members)]
 
     def run(self, verbose: bool = False):             # main() :356-408
         check(lib().mdlc_run(self._h, int(bool(verbose))), "mdlc_run")

@@ -11,6 +11,10 @@ For N0 = 1000 and njobs = 1, 8 and 64: 5 warm-up launches of 1000 steps, then 20
              instruction and two FLOP
   roof_fraction: ion-steps/s x FP64 FLOP per ion-step / 78.6e12 (the FP64 vector peak)
 
+--sweep NAME:v1,v2,... (NAME one of detuning, Om, temperature; once per name) times a parameter scan instead
+(k_lc_steps_sweep, mdlc_sweep_kernels.hip): each njobs value J is then the members in all, the points (the
+product of the lists) x J / points replicas.  One value runs the scan's kernel on the uniform ensemble's own jobs.
+
 There is no CPU fallback: without a GPU the tool fails.
 """
 import argparse
@@ -60,6 +64,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--sweep", action="append", default=[], metavar="NAME:v1,v2,...",
+                    help="time a scan of J members in all: the points are the product of the axes")
     ap.add_argument("--asm", default=ASM, help="assembly of mdlc_kernels.hip (made with `make asm` if missing)")
     a = ap.parse_args()
 
@@ -70,10 +76,20 @@ def main():
         subprocess.run(["make", "-C", os.path.join(ROOT, "mdqtplasmasims_amd", "csrc"), "asm"], check=True,
                        stdout=subprocess.DEVNULL)
     n64, flop, valu = count_loop_fp64(a.asm)
+    sweep = {}
+    for ax in a.sweep:
+        name, _, vals = ax.partition(":")
+        if name in sweep or not vals:
+            ap.error(f"--sweep {ax}: NAME:v1,v2,... with each NAME once")
+        sweep[name] = [float(v) for v in vals.split(",")]
+    npoints = int(np.prod([len(v) for v in sweep.values()])) if sweep else 1
     rows = {}
     base = None
     for J in a.njobs:
-        with LaserCooling(N0=a.N0, njobs=J, seed=12345, job=1, device=a.device) as s:
+        if J % npoints:
+            ap.error(f"--njobs {J} is not a multiple of the scan's {npoints} points")
+        with LaserCooling(N0=a.N0, njobs=J // npoints, seed=12345, job=1, device=a.device, sweep=sweep or None) as s:
+            assert s.members == J
             s.init()
             ms = s.time_qsteps(a.steps, a.warmup, a.launches)
         med = float(np.median(ms))
@@ -88,7 +104,7 @@ def main():
         tree = ""
     print(json.dumps(dict(tool="mdlc_rate", N0=a.N0, steps=a.steps, warmup=a.warmup, launches=a.launches,
                           fp64_per_ion_step=n64, fp64_flop_per_ion_step=flop, valu_per_ion_step=valu,
-                          fp64_peak=FP64_PEAK, tree=tree or None, njobs=rows)))
+                          fp64_peak=FP64_PEAK, tree=tree or None, sweep=sweep or None, njobs=rows)))
 
 
 if __name__ == "__main__":
