@@ -15,10 +15,9 @@
 #include <string.h>
 #include <time.h>
 
-#include <vector>
-
 #include "mdlc.h"
 #include "mdqt.h"
+#include "mdqt_cli_args.hpp"
 
 static void usage(void) {
     fprintf(stderr,
@@ -31,35 +30,9 @@ static void usage(void) {
             "                  product of the lists (the first NAME slowest; each NAME once), --njobs replicas of each\n");
 }
 
-// --sweep: one axis of the scan
-enum { kSweepNames = 3, kSweepMax = 1024 };
-static const char* const sweep_names[kSweepNames] = {"detuning", "Om", "temperature"};
-struct SweepAxis {
-    int field, n;
-    double v[kSweepMax];
-};
-static double* sweep_field(mdlc_params* p, int field) {
-    double* const f[kSweepNames] = {&p->detuning, &p->Om, &p->temperature};
-    return f[field];
-}
-// "NAME:v1,v2,..." -> the axis; 0 if it is one (a sweepable NAME, a non-empty list of numbers)
-static int parse_sweep(const char* v, SweepAxis* ax) {
-    const char* colon = strchr(v, ':');
-    if (!colon) return -1;
-    ax->field = -1;
-    for (int f = 0; f < kSweepNames; ++f)
-        if (strlen(sweep_names[f]) == (size_t)(colon - v) && !strncmp(v, sweep_names[f], (size_t)(colon - v))) ax->field = f;
-    if (ax->field < 0) return -1;
-    ax->n = 0;
-    for (const char* s = colon + 1;;) {
-        char* end = NULL;
-        const double x = strtod(s, &end);
-        if (end == s || (*end != ',' && *end != 0) || ax->n >= kSweepMax) return -1;
-        ax->v[ax->n++] = x;
-        if (!*end) return 0;
-        s = end + 1;
-    }
-}
+// --sweep: the NAMEs and their fields (mdqt_cli_args.hpp)
+static const char* const sweep_names[] = {"detuning", "Om", "temperature"};
+static double mdlc_params::*const sweep_fields[] = {&mdlc_params::detuning, &mdlc_params::Om, &mdlc_params::temperature};
 
 int main(int argc, char** argv) {
     if (argc < 2) { usage(); return 2; }
@@ -68,18 +41,11 @@ int main(int argc, char** argv) {
     const double job = atof(argv[1]);                       // LC3:362
     p.job = (uint32_t)job;
     int seed_given = 0, quiet = 0, print_dir = 0;
-    static SweepAxis axes[kSweepNames];                     // --sweep: the axes in the order given
-    int naxes = 0;
+    SweepAxes axes;                                         // --sweep: the axes in the order given
     for (int i = 2; i < argc; ++i) {
-        const char* a = argv[i];
-        if (strncmp(a, "--", 2) != 0 || !strchr(a, '=')) { usage(); return 2; }
         char key[64];
-        const char* eq = strchr(a, '=');
-        size_t kl = (size_t)(eq - a - 2);
-        if (kl >= sizeof key) { usage(); return 2; }
-        memcpy(key, a + 2, kl);
-        key[kl] = 0;
-        const char* v = eq + 1;
+        const char* v;
+        if (!cli_key_value(argv[i], key, sizeof key, &v)) { usage(); return 2; }
 #define DPAR(name) if (!strcmp(key, #name)) { p.name = atof(v); continue; }
 #define IPAR(name) if (!strcmp(key, #name)) { p.name = atoi(v); continue; }
         DPAR(detuning) DPAR(Om) DPAR(tmax) DPAR(temperature) DPAR(vKick) DPAR(dt)
@@ -89,11 +55,7 @@ int main(int argc, char** argv) {
         if (!strcmp(key, "quiet")) { quiet = atoi(v); continue; }
         if (!strcmp(key, "print-directory")) { print_dir = atoi(v); continue; }
         if (!strcmp(key, "sweep")) {
-            SweepAxis* ax = &axes[naxes < kSweepNames ? naxes : 0];
-            if (naxes >= kSweepNames || parse_sweep(v, ax)) { usage(); return 2; }
-            for (int o = 0; o < naxes; ++o)
-                if (axes[o].field == ax->field) { usage(); return 2; }     // a NAME given twice
-            ++naxes;
+            if (!axes.add(v, sweep_names)) { usage(); return 2; }
             continue;
         }
         if (!strcmp(key, "seed")) { p.seed = (uint32_t)strtoul(v, NULL, 10); seed_given = 1; continue; }
@@ -104,20 +66,10 @@ int main(int argc, char** argv) {
         fprintf(stderr, "mdlc: unknown parameter %s\n", key);
         return 2;
     }
-    std::vector<mdlc_params> points;                        // the axes' product, the first axis slowest
-    if (naxes > 0) {
-        long npoints = 1;
-        for (int o = 0; o < naxes; ++o) npoints *= axes[o].n;
-        points.assign((size_t)npoints, p);
-        for (long q = 0; q < npoints; ++q) {
-            long rest = q;
-            for (int o = naxes - 1; o >= 0; --o) {
-                *sweep_field(&points[q], axes[o].field) = axes[o].v[rest % axes[o].n];
-                rest /= axes[o].n;
-            }
-        }
-    }
-    if (print_dir && naxes > 0) {                           // every member's directory, in member order: no GPU needed
+    const bool scan = !axes.empty();
+    std::vector<mdlc_params> points;                        // of a scan (their number is the library's to refuse)
+    if (scan) axes.points(p, sweep_fields, 0, &points);
+    if (print_dir && scan) {                                // every member's directory, in member order: no GPU needed
         const long members = (long)points.size() * (p.njobs > 0 ? p.njobs : 1);
         for (long k = 0; k < members; ++k) {
             mdlc_params pk;
@@ -145,7 +97,7 @@ int main(int argc, char** argv) {
     if (!seed_given) p.seed = (uint32_t)(time(NULL) + job); // the reference: random_device (:45), srand48(time + job) (:389)
     mdlc_ctx* c = NULL;
     for (auto& q : points) q.seed = p.seed;
-    if ((naxes > 0 ? mdlc_create_sweep(points.data(), (int)points.size(), &c) : mdlc_create(&p, &c)) != 0) {
+    if ((scan ? mdlc_create_sweep(points.data(), (int)points.size(), &c) : mdlc_create(&p, &c)) != 0) {
         fprintf(stderr, "mdlc: %s\n", mdqt_last_error());
         return 1;
     }

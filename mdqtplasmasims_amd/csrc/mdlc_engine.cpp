@@ -17,6 +17,7 @@
 #include "../../include/mdlc.h"
 #include "mdqt_ctx.hpp"   // HIPCHK, mdqt::set_error
 #include "mdqt_mt32.hpp"
+#include "mdqt_sweep.hpp"
 
 using namespace mdqt;
 
@@ -60,16 +61,12 @@ int check_params(const mdlc_params* p) {
     return r ? set_error("%s", r) : 0;
 }
 
-// The swept fields (the reference's directory name has a level for each, LC3:371-375, with these scales), and
-// the name of the first other field in which b differs from a (nullptr: none).  Field by field: the struct has
-// padding.
-constexpr int kSweepFields = 3;
-const char* const kSweepName[kSweepFields] = {"detuning", "Om", "temperature"};
-const double kSweepScale[kSweepFields] = {100, 100, 1000000};
-double sweep_field(const mdlc_params& p, int f) {
-    const double v[kSweepFields] = {p.detuning, p.Om, p.temperature};
-    return v[f];
-}
+// The swept fields (mdqt_sweep.hpp; the reference's directory name has a level for each, LC3:371-375, with these
+// scales: directory_levels), and the name of the first other field in which b differs from a (nullptr: none).
+// Field by field: the struct has padding.
+const SweepField<mdlc_params> kSweep[] = {{"detuning", &mdlc_params::detuning, 100},
+                                          {"Om", &mdlc_params::Om, 100},
+                                          {"temperature", &mdlc_params::temperature, 1000000}};
 const char* fixed_field_differs(const mdlc_params& a, const mdlc_params& b) {
 #define FIXED(name) if (memcmp(&a.name, &b.name, sizeof a.name)) return #name;
     FIXED(N0) FIXED(tmax) FIXED(applyForce) FIXED(sampleFreq) FIXED(vKick) FIXED(dt) FIXED(seed) FIXED(job)
@@ -85,29 +82,12 @@ int sweep_validate(const mdlc_params* pts, int npoints, const char* what) {
     if (npoints < 1) return set_error("%s: npoints must be >= 1", what);
     for (int q = 0; q < npoints; ++q) {
         if (const char* r = params_refusal(pts + q)) return set_error("%s: point %d: %s", what, q, r);
-        if (const char* f = fixed_field_differs(pts[0], pts[q]))
-            return set_error("%s: point %d differs from point 0 in %s: only detuning, Om and temperature may differ between "
-                             "the points (the others fix the stride, the loop counts, the outputs and the Philox keys of "
-                             "every member; the directory name has no level for vKick)", what, q, f);
+        if (sweep_refuse_fixed(kSweep, q, fixed_field_differs(pts[0], pts[q]),
+                               "the others fix the stride, the loop counts, the outputs and the Philox keys of every member; "
+                               "the directory name has no level for vKick", what))
+            return -1;
     }
-    for (int q = 1; q < npoints; ++q)
-        for (int o = 0; o < q; ++o) {
-            int same = 0, collide = 0, first = -1;
-            for (int f = 0; f < kSweepFields; ++f) {
-                const double a = sweep_field(pts[o], f), b = sweep_field(pts[q], f);
-                const bool eq = !memcmp(&a, &b, sizeof a) || a == b;
-                same += eq;
-                collide += ref_udcast(a * kSweepScale[f]) == ref_udcast(b * kSweepScale[f]);   // directory_levels' name
-                if (first < 0 && !eq) first = f;
-            }
-            if (same == kSweepFields)
-                return set_error("%s: point %d is identical to point %d (detuning, Om and temperature all equal): both would "
-                                 "write the same run directories", what, q, o);
-            if (collide == kSweepFields)
-                return set_error("%s: point %d and point %d give the same run directory name: %s %.17g and %.17g print alike "
-                                 "(the name holds Om x 100, detuning x 100 and temperature x 1000000 as integers)", what, q, o,
-                                 kSweepName[first], sweep_field(pts[q], first), sweep_field(pts[o], first));
-        }
+    if (sweep_refuse_same(kSweep, pts, npoints, what)) return -1;
     const long long B = ((long long)pts[0].N0 + kLCBlock - 1) / kLCBlock;
     if (B * pts[0].njobs * npoints > kMaxGrid)
         return set_error("%s: npoints x njobs x workgroups per job = %d x %d x %lld is too large for one launch grid", what,
@@ -305,11 +285,10 @@ extern "C" int mdlc_create(const mdlc_params* p, mdlc_ctx** out) {
 extern "C" int mdlc_sweep_params(const mdlc_params* points, int npoints, int k, mdlc_params* out) {
     if (!points || !out) return set_error("mdlc_sweep_params: NULL argument");
     if (sweep_validate(points, npoints, "mdlc_sweep_params")) return -1;
-    const int R = points[0].njobs;
-    if (k < 0 || k >= (long long)npoints * R)
-        return set_error("mdlc_sweep_params: member index %d outside [0, %lld)", k, (long long)npoints * R);
-    *out = points[k / R];
-    out->job += (uint32_t)(k % R);
+    int q, r;
+    if (sweep_member(npoints, points[0].njobs, k, "member", "mdlc_sweep_params", &q, &r)) return -1;
+    *out = points[q];
+    out->job += (uint32_t)r;
     out->njobs = 1;
     return 0;
 }

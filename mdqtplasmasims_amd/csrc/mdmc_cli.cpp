@@ -19,6 +19,7 @@
 
 #include "mdmc.h"
 #include "mdqt.h"
+#include "mdqt_cli_args.hpp"
 
 static void usage(void) {
     fprintf(stderr,
@@ -54,15 +55,9 @@ int main(int argc, char** argv) {
     long njobs = -1;                                        // --njobs: the jobs of an ensemble (-1: not given)
     int md_batch = -1;                                      // --md_batch (-1: not given)
     for (int i = 2; i < argc; ++i) {
-        const char* a = argv[i];
-        if (strncmp(a, "--", 2) != 0 || !strchr(a, '=')) { usage(); return 2; }
         char key[64];
-        const char* eq = strchr(a, '=');
-        size_t kl = (size_t)(eq - a - 2);
-        if (kl >= sizeof key) { usage(); return 2; }
-        memcpy(key, a + 2, kl);
-        key[kl] = 0;
-        const char* v = eq + 1;
+        const char* v;
+        if (!cli_key_value(argv[i], key, sizeof key, &v)) { usage(); return 2; }
 #define DPAR(name) if (!strcmp(key, #name)) { p.name = atof(v); continue; }
 #define IPAR(name) if (!strcmp(key, #name)) { p.name = atoi(v); continue; }
         DPAR(kappa) DPAR(Gamma) DPAR(n) DPAR(collisionFreq) DPAR(maxRStep) DPAR(pairPairStep) DPAR(timeStep)

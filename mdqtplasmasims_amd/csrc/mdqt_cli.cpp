@@ -32,6 +32,7 @@
 #include <time.h>
 
 #include "mdqt.h"
+#include "mdqt_cli_args.hpp"
 
 static void usage(void) {
     fprintf(stderr,
@@ -52,35 +53,10 @@ static void usage(void) {
             "                  ensemble (1 <= J <= 1024; seeds seed .. seed+J-1; not with --njobs)\n");
 }
 
-// --sweep: one axis of the scan
-enum { kSweepNames = 5, kSweepMax = 1024 };
-static const char* const sweep_names[kSweepNames] = {"detuning", "detuningDP", "Om", "OmDP", "fracOfSig"};
-struct SweepAxis {
-    int field, n;
-    double v[kSweepMax];
-};
-static double* sweep_field(mdqt_params* p, int field) {
-    double* const f[kSweepNames] = {&p->detuning, &p->detuningDP, &p->Om, &p->OmDP, &p->fracOfSig};
-    return f[field];
-}
-// "NAME:v1,v2,..." -> the axis; 0 if it is one (a sweepable NAME, a non-empty list of numbers)
-static int parse_sweep(const char* v, SweepAxis* ax) {
-    const char* colon = strchr(v, ':');
-    if (!colon) return -1;
-    ax->field = -1;
-    for (int f = 0; f < kSweepNames; ++f)
-        if (strlen(sweep_names[f]) == (size_t)(colon - v) && !strncmp(v, sweep_names[f], (size_t)(colon - v))) ax->field = f;
-    if (ax->field < 0) return -1;
-    ax->n = 0;
-    for (const char* s = colon + 1;;) {
-        char* end = NULL;
-        const double x = strtod(s, &end);
-        if (end == s || (*end != ',' && *end != 0) || ax->n >= kSweepMax) return -1;
-        ax->v[ax->n++] = x;
-        if (!*end) return 0;
-        s = end + 1;
-    }
-}
+// --sweep: the NAMEs and their fields (mdqt_cli_args.hpp)
+static const char* const sweep_names[] = {"detuning", "detuningDP", "Om", "OmDP", "fracOfSig"};
+static double mdqt_params::*const sweep_fields[] = {&mdqt_params::detuning, &mdqt_params::detuningDP, &mdqt_params::Om,
+                                                    &mdqt_params::OmDP, &mdqt_params::fracOfSig};
 
 int main(int argc, char** argv) {
     if (argc < 2) { usage(); return 2; }
@@ -97,18 +73,11 @@ int main(int argc, char** argv) {
     long njobs = -1;                                        // --njobs: the jobs of an ensemble (-1: not given)
     long pump_jobs = -1;                                    // --pump_jobs: the jobs of a pump ensemble
     long output_batch = -1;                                 // --output_batch: the ensemble's option (-1: its default)
-    static SweepAxis axes[kSweepNames];                     // --sweep: the axes in the order given
-    int naxes = 0;
+    SweepAxes axes;                                         // --sweep: the axes in the order given
     for (int i = 2; i < argc; ++i) {
-        const char* a = argv[i];
-        if (strncmp(a, "--", 2) != 0 || !strchr(a, '=')) { usage(); return 2; }
         char key[64];
-        const char* eq = strchr(a, '=');
-        size_t kl = (size_t)(eq - a - 2);
-        if (kl >= sizeof key) { usage(); return 2; }
-        memcpy(key, a + 2, kl);
-        key[kl] = 0;
-        const char* v = eq + 1;
+        const char* v;
+        if (!cli_key_value(argv[i], key, sizeof key, &v)) { usage(); return 2; }
 #define DPAR(name) if (!strcmp(key, #name)) { p.name = atof(v); continue; }
 #define IPAR(name) if (!strcmp(key, #name)) { p.name = atoi(v); continue; }
         DPAR(Ge) DPAR(tmax) DPAR(density) DPAR(sig0) DPAR(Te) DPAR(fracOfSig) DPAR(detuning)
@@ -131,11 +100,7 @@ int main(int argc, char** argv) {
             continue;
         }
         if (!strcmp(key, "sweep")) {
-            SweepAxis* ax = &axes[naxes < kSweepNames ? naxes : 0];
-            if (naxes >= kSweepNames || parse_sweep(v, ax)) { usage(); return 2; }
-            for (int o = 0; o < naxes; ++o)
-                if (axes[o].field == ax->field) { usage(); return 2; }     // a NAME given twice
-            ++naxes;
+            if (!axes.add(v, sweep_names)) { usage(); return 2; }
             continue;
         }
         if (!strcmp(key, "pump_jobs")) {
@@ -155,31 +120,19 @@ int main(int argc, char** argv) {
     if (njobs > 0 && pump) { usage(); return 2; }
     if (pump_jobs > 0 && (!pump || njobs > 0)) { usage(); return 2; }
     if (output_batch >= 0 && njobs < 1) { usage(); return 2; }
-    if (naxes > 0 && (njobs < 1 || pump)) { usage(); return 2; }
-    long npoints = 1;
-    for (int o = 0; o < naxes; ++o) {
-        npoints *= axes[o].n;
-        if (npoints * njobs > kSweepMax) { usage(); return 2; }
-    }
+    if (!axes.empty() && (njobs < 1 || pump)) { usage(); return 2; }
     if (!seed_given) p.seed = (uint32_t)(time(NULL) + job);   // SpeedUp:1219
+    std::vector<mdqt_params> points;                        // of a scan: at most kSweepMax members in all
+    if (!axes.empty() && !axes.points(p, sweep_fields, kSweepMax / njobs, &points)) { usage(); return 2; }
     if (njobs > 0) {
         mdqt_ensemble* e = NULL;
         int rc_create;
-        if (naxes > 0) {                                    // the points: the axes' product, the first axis slowest
-            static mdqt_params points[kSweepMax];
-            for (long q = 0; q < npoints; ++q) {
-                points[q] = p;
-                long rest = q;
-                for (int o = naxes - 1; o >= 0; --o) {
-                    *sweep_field(&points[q], axes[o].field) = axes[o].v[rest % axes[o].n];
-                    rest /= axes[o].n;
-                }
-            }
-            rc_create = mdqt_ensemble_create_sweep(points, (int)npoints, (int)njobs, &e);
+        if (!axes.empty()) {
+            rc_create = mdqt_ensemble_create_sweep(points.data(), (int)points.size(), (int)njobs, &e);
+            njobs *= (long)points.size();                   // the members
         } else {
             rc_create = mdqt_ensemble_create(&p, (int)njobs, &e);
         }
-        njobs *= npoints;                                   // the members
         if (rc_create) {
             fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
             return 1;

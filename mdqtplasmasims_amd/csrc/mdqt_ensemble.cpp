@@ -18,6 +18,8 @@
 #include <algorithm>
 
 #include "mdqt_ctx.hpp"
+#include "mdqt_qtfast.hpp"   // sweep_choice_differs (the host part)
+#include "mdqt_sweep.hpp"
 
 using namespace mdqt;
 
@@ -307,14 +309,13 @@ int refuse_params(const mdqt_params* p, const char* what, bool pump) {
     return 0;
 }
 
-// The swept fields, and the name of the first other field in which b differs from a (nullptr: none).  Field by
-// field: the struct has padding.
-constexpr int kSweepFields = 5;
-const char* const kSweepName[kSweepFields] = {"detuning", "detuningDP", "Om", "OmDP", "fracOfSig"};
-double sweep_field(const mdqt_params& p, int f) {
-    const double v[kSweepFields] = {p.detuning, p.detuningDP, p.Om, p.OmDP, p.fracOfSig};
-    return v[f];
-}
+// The swept fields (mdqt_sweep.hpp; mdqt_setup_directories' name holds each x 100), and the name of the first
+// other field in which b differs from a (nullptr: none).  Field by field: the struct has padding.
+const SweepField<mdqt_params> kSweep[] = {{"detuning", &mdqt_params::detuning, 100},
+                                          {"detuningDP", &mdqt_params::detuningDP, 100},
+                                          {"Om", &mdqt_params::Om, 100},
+                                          {"OmDP", &mdqt_params::OmDP, 100},
+                                          {"fracOfSig", &mdqt_params::fracOfSig, 100}};
 const char* fixed_field_differs(const mdqt_params& a, const mdqt_params& b) {
 #define FIXED(name) if (memcmp(&a.name, &b.name, sizeof a.name)) return #name;
     FIXED(Ge) FIXED(tmax) FIXED(density) FIXED(sig0) FIXED(Te) FIXED(N0) FIXED(newRun) FIXED(c0) FIXED(sampleFreq)
@@ -334,34 +335,16 @@ int sweep_validate(const mdqt_params* pts, int npoints, int njobs, const char* w
         return set_error("%s: npoints x njobs = %lld members, more than %d", what, (long long)npoints * njobs, kEnsembleMaxJobs);
     if (refuse_params(pts, what, false)) return -1;
     for (int q = 1; q < npoints; ++q) {
-        if (const char* f = fixed_field_differs(pts[0], pts[q]))
-            return set_error("%s: point %d differs from point 0 in %s: only detuning, detuningDP, Om, OmDP and fracOfSig "
-                             "may differ between the points (the others fix the box, the substep ratio, t and the outputs "
-                             "of every member)", what, q, f);
+        if (sweep_refuse_fixed(kSweep, q, fixed_field_differs(pts[0], pts[q]),
+                               "the others fix the box, the substep ratio, t and the outputs of every member", what))
+            return -1;
         if ((pts[q].fracOfSig == 0.) != (pts[0].fracOfSig == 0.))
             return set_error("%s: point %d has fracOfSig %g and point 0 has %g: a point with fracOfSig == 0 runs the QT kernel "
                              "instance without the expansion detuning, one with fracOfSig != 0 cannot, and one launch is one "
                              "instance (splitting a launch by instance is not supported: run the two groups as two ensembles)",
                              what, q, pts[q].fracOfSig, pts[0].fracOfSig);
     }
-    for (int q = 1; q < npoints; ++q)
-        for (int o = 0; o < q; ++o) {
-            int same = 0, collide = 0, first = -1;
-            for (int f = 0; f < kSweepFields; ++f) {
-                const double a = sweep_field(pts[o], f), b = sweep_field(pts[q], f);
-                same += !memcmp(&a, &b, sizeof a) || a == b;
-                collide += ref_udcast(a * 100) == ref_udcast(b * 100);     // mdqt_setup_directories' name
-                if (first < 0 && !(!memcmp(&a, &b, sizeof a) || a == b)) first = f;
-            }
-            if (same == kSweepFields)
-                return set_error("%s: point %d is identical to point %d (detuning, detuningDP, Om, OmDP and fracOfSig all equal): "
-                                 "both would write the same run directories", what, q, o);
-            if (collide == kSweepFields)
-                return set_error("%s: point %d and point %d give the same run directory name: %s %.17g and %.17g print alike "
-                                 "(the name holds the fields x 100 as integers)", what, q, o, kSweepName[first],
-                                 sweep_field(pts[q], first), sweep_field(pts[o], first));
-        }
-    return 0;
+    return sweep_refuse_same(kSweep, pts, npoints, what);
 }
 
 // the points' tables and the members' point indices, uploaded when they differ from what the device holds
@@ -446,9 +429,9 @@ extern "C" int mdqt_ensemble_create(const mdqt_params* p, int njobs, mdqt_ensemb
 extern "C" int mdqt_ensemble_sweep_params(const mdqt_params* points, int npoints, int njobs, int k, mdqt_params* out) {
     if (!points || !out) return set_error("mdqt_ensemble_sweep_params: NULL argument");
     if (sweep_validate(points, npoints, njobs, "mdqt_ensemble_sweep_params")) return -1;
-    if (k < 0 || k >= npoints * njobs)
-        return set_error("mdqt_ensemble_sweep_params: job index %d outside [0, %d)", k, npoints * njobs);
-    return mdqt_ensemble_job_params(points + k / njobs, k % njobs, out);
+    int q, r;
+    if (sweep_member(npoints, njobs, k, "job", "mdqt_ensemble_sweep_params", &q, &r)) return -1;
+    return mdqt_ensemble_job_params(points + q, r, out);
 }
 
 extern "C" int mdqt_ensemble_create_sweep(const mdqt_params* points, int npoints, int njobs, mdqt_ensemble** out) {

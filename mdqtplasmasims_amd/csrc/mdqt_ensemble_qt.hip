@@ -38,7 +38,7 @@ LANE_ENS_KERNELS(_w3, __attribute__((amdgpu_waves_per_eu(3, 3))), false)   // (l
 
 // The lane kernels of launch_substeps_r's mode 2, model 0, over an ensemble: `jobs` is the device array of
 // the njobs argument blocks, `a` the host copy of one of them — every job has the same nsub, do_step,
-// do_qt, movmask, expdet_zero and qc, so the instance chosen for it (launch_substeps_r's conditions) is
+// do_qt, movmask, expdet_zero and qc, so the instance chosen for it (lane_qt_instance, mdqt_qtfast.hpp) is
 // every job's.  max_n = the largest a.n; wpe = the production instance's register budget (0, 3:
 // LANE_ENS_KERNELS; the other instances keep the single-job budget).
 hipError_t launch_substeps_r_ens(const SubstepArgs* jobs, const SubstepArgs& a, int njobs, int max_n, const FastTab* tab,
@@ -48,33 +48,18 @@ hipError_t launch_substeps_r_ens(const SubstepArgs* jobs, const SubstepArgs& a, 
     if (wpe != 0 && wpe != 3) return hipErrorInvalidValue;
     const dim3 gl((max_n + kLaneIons - 1) / kLaneIons, njobs), bl(kLaneWG);
     const FastTab* lt = tab + 1;                      // by lane
-    const uint64_t all = (1ull << a.nsub) - 1;
-    const bool allmove = a.do_step && a.do_qt && a.nseg >= 1 && (a.movmask & all) == all;
-    int inst;
-#define LANE_ENS_LAUNCH(KERNEL, ...)                                                                    \
-    do {                                                                                                \
-        if (wpe == 3) launch_timed(KERNEL##_w3<__VA_ARGS__>, gl, bl, s, ev0, ev1, jobs, lt);            \
-        else launch_timed(KERNEL<__VA_ARGS__>, gl, bl, s, ev0, ev1, jobs, lt);                          \
-    } while (0)
-    if (allmove && a.qc.im01) {
-        if (a.expdet_zero && !a.qc.renorm) {   // the production launch
-            LANE_ENS_LAUNCH(k_substeps_lanes_im_ens, true, true, true);
-            inst = QTK_LANES_IM_EDZ;
-        } else if (a.expdet_zero) {
-            launch_timed(k_substeps_lanes_im_ens<true, true>, gl, bl, s, ev0, ev1, jobs, lt);
-            inst = QTK_LANES_IM_EDZ_RN;
-        } else {
-            launch_timed(k_substeps_lanes_im_ens<true, false>, gl, bl, s, ev0, ev1, jobs, lt);
-            inst = QTK_LANES_IM;
-        }
-    } else if (allmove) {
-        launch_timed(k_substeps_lanes_r_ens<true, true>, gl, bl, s, ev0, ev1, jobs, lt);
-        inst = QTK_LANES_R_FAST;
-    } else {
-        launch_timed(k_substeps_lanes_r_ens<true, false>, gl, bl, s, ev0, ev1, jobs, lt);
-        inst = QTK_LANES_R;
+    const QTKernel inst = lane_qt_instance(a);
+    switch (inst) {
+    case QTK_LANES_IM_EDZ:                            // the production launch: the register budget asked for
+        if (wpe == 3) launch_timed(k_substeps_lanes_im_ens_w3<true, true, true>, gl, bl, s, ev0, ev1, jobs, lt);
+        else launch_timed(k_substeps_lanes_im_ens<true, true, true>, gl, bl, s, ev0, ev1, jobs, lt);
+        break;
+    case QTK_LANES_IM_EDZ_RN: launch_timed(k_substeps_lanes_im_ens<true, true>, gl, bl, s, ev0, ev1, jobs, lt); break;
+    case QTK_LANES_IM: launch_timed(k_substeps_lanes_im_ens<true, false>, gl, bl, s, ev0, ev1, jobs, lt); break;
+    case QTK_LANES_R_FAST: launch_timed(k_substeps_lanes_r_ens<true, true>, gl, bl, s, ev0, ev1, jobs, lt); break;
+    case QTK_LANES_R: launch_timed(k_substeps_lanes_r_ens<true, false>, gl, bl, s, ev0, ev1, jobs, lt); break;
+    default: return hipErrorInvalidValue;             // (model 0, checked above: none of the pump instances)
     }
-#undef LANE_ENS_LAUNCH
     if (instance) *instance = inst;
     return hipGetLastError();
 }

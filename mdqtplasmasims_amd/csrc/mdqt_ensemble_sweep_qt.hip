@@ -36,26 +36,10 @@ LANE_SWEEP_KERNELS(, , true)
 LANE_SWEEP_KERNELS(_w3, __attribute__((amdgpu_waves_per_eu(3, 3))), false)   // (lane_substeps: JUNI)
 #undef LANE_SWEEP_KERNELS
 
-// what launch_substeps_r's choice of the instance reads in a block: the first of it in which b differs from a
-// (nullptr: none)
-const char* sweep_choice_differs(const SubstepArgs& a, const SubstepArgs& b) {
-    if (a.nsub != b.nsub) return "nsub";
-    if (a.do_step != b.do_step) return "do_step";
-    if (a.do_qt != b.do_qt) return "do_qt";
-    if (a.movmask != b.movmask) return "movmask (t > 0 per substep)";
-    if (a.expdet_zero != b.expdet_zero) return "expdet_zero (fracOfSig == 0 against != 0)";
-    if (a.qc.im01 != b.qc.im01) return "qt_im01";
-    if (a.qc.renorm != b.qc.renorm) return "reNormalizewvFns";
-    if (a.qc.model != b.qc.model) return "qt_model";
-    if ((a.nseg >= 1) != (b.nseg >= 1)) return "nseg";
-    if (!a.arrive != !b.arrive || !a.U != !b.U) return "arrive / U (another launch scheme)";
-    return nullptr;
-}
-
 // launch_substeps_r_ens for a sweep ensemble: `h` = the host copies of all njobs blocks.  One instance serves
-// the whole launch, so every member's block must agree with member 0's on what the choice reads; where one
-// does not, nothing is launched, *differs = that member's index and the result is hipErrorInvalidValue
-// (*differs = -1 for any other refusal).
+// the whole launch, so every member's block must agree with member 0's on what the choice reads
+// (sweep_choice_differs, beside lane_qt_instance in mdqt_qtfast.hpp); where one does not, nothing is launched,
+// *differs = that member's index and the result is hipErrorInvalidValue (*differs = -1 for any other refusal).
 hipError_t launch_substeps_r_sweep(const SubstepArgs* jobs, const SubstepArgs* h, int njobs, int max_n, const FastTab* tabs,
                                    const int* point, int wpe, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int* instance,
                                    int* differs) {
@@ -72,27 +56,17 @@ hipError_t launch_substeps_r_sweep(const SubstepArgs* jobs, const SubstepArgs* h
             return hipErrorInvalidValue;
         }
     const dim3 gl((max_n + kLaneIons - 1) / kLaneIons, njobs), bl(kLaneWG);
-    const uint64_t all = (1ull << a.nsub) - 1;
-    const bool allmove = a.do_step && a.do_qt && a.nseg >= 1 && (a.movmask & all) == all;
-    int inst;
-    if (allmove && a.qc.im01) {
-        if (a.expdet_zero && !a.qc.renorm) {   // the production launch
-            if (wpe == 3) launch_timed(k_substeps_lanes_im_sweep_w3<true, true, true>, gl, bl, s, ev0, ev1, jobs, tabs, point);
-            else launch_timed(k_substeps_lanes_im_sweep<true, true, true>, gl, bl, s, ev0, ev1, jobs, tabs, point);
-            inst = QTK_LANES_IM_EDZ;
-        } else if (a.expdet_zero) {
-            launch_timed(k_substeps_lanes_im_sweep<true, true>, gl, bl, s, ev0, ev1, jobs, tabs, point);
-            inst = QTK_LANES_IM_EDZ_RN;
-        } else {
-            launch_timed(k_substeps_lanes_im_sweep<true, false>, gl, bl, s, ev0, ev1, jobs, tabs, point);
-            inst = QTK_LANES_IM;
-        }
-    } else if (allmove) {
-        launch_timed(k_substeps_lanes_r_sweep<true, true>, gl, bl, s, ev0, ev1, jobs, tabs, point);
-        inst = QTK_LANES_R_FAST;
-    } else {
-        launch_timed(k_substeps_lanes_r_sweep<true, false>, gl, bl, s, ev0, ev1, jobs, tabs, point);
-        inst = QTK_LANES_R;
+    const QTKernel inst = lane_qt_instance(a);
+    switch (inst) {
+    case QTK_LANES_IM_EDZ:                            // the production launch: the register budget asked for
+        if (wpe == 3) launch_timed(k_substeps_lanes_im_sweep_w3<true, true, true>, gl, bl, s, ev0, ev1, jobs, tabs, point);
+        else launch_timed(k_substeps_lanes_im_sweep<true, true, true>, gl, bl, s, ev0, ev1, jobs, tabs, point);
+        break;
+    case QTK_LANES_IM_EDZ_RN: launch_timed(k_substeps_lanes_im_sweep<true, true>, gl, bl, s, ev0, ev1, jobs, tabs, point); break;
+    case QTK_LANES_IM: launch_timed(k_substeps_lanes_im_sweep<true, false>, gl, bl, s, ev0, ev1, jobs, tabs, point); break;
+    case QTK_LANES_R_FAST: launch_timed(k_substeps_lanes_r_sweep<true, true>, gl, bl, s, ev0, ev1, jobs, tabs, point); break;
+    case QTK_LANES_R: launch_timed(k_substeps_lanes_r_sweep<true, false>, gl, bl, s, ev0, ev1, jobs, tabs, point); break;
+    default: return hipErrorInvalidValue;             // (model 0, checked above: none of the pump instances)
     }
     if (instance) *instance = inst;
     return hipGetLastError();

@@ -721,13 +721,12 @@ hipError_t launch_substeps_r_ens(const SubstepArgs* jobs, const SubstepArgs& a, 
 // A sweep ensemble's substeps (mdqt_ensemble_sweep_qt.hip): members with different laser parameters in one
 // launch.  `h` = the host copies of all njobs blocks, `tabs` the device array of the points' by-lane tables,
 // `point` the device array of the members' point indices.  The instance is launch_substeps_r_ens's choice, made
-// only if every block agrees on what it reads; otherwise nothing is launched, *differs = the first member
-// that differs from member 0 and the result is hipErrorInvalidValue (*differs = -1 for any other refusal).
+// only if every block agrees on what it reads (sweep_choice_differs, defined beside the choice itself in
+// mdqt_qtfast.hpp); otherwise nothing is launched, *differs = the first member that differs from member 0 and the
+// result is hipErrorInvalidValue (*differs = -1 for any other refusal).
 hipError_t launch_substeps_r_sweep(const SubstepArgs* jobs, const SubstepArgs* h, int njobs, int max_n, const FastTab* tabs,
                                    const int* point, int wpe, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int* instance,
                                    int* differs);
-// ... and what it compares: the first of those fields in which b differs from a (nullptr: none).  Host only
-const char* sweep_choice_differs(const SubstepArgs& a, const SubstepArgs& b);
 // An ensemble of optical-pumping jobs in batched launches (mdqt_pump_ensemble_kernels.hip; host:
 // mdqt_pump_ensemble.cpp): `jobs` = device array of the members' argument blocks, grid (largest member's
 // workgroups, njobs); every kernel runs its single-job kernel's body (mdqt_pump_device.hpp, lane_substeps).

@@ -32,11 +32,13 @@ hipError_t launch_substeps_pump_ens(const SubstepArgs* jobs, const SubstepArgs& 
         return hipErrorInvalidValue;
     const dim3 gl((max_n + kLaneIons - 1) / kLaneIons, njobs), bl(kLaneWG);
     const FastTab* lt = tab + 1;                      // by lane
-    const uint64_t all = (1ull << a.nsub) - 1;
-    const bool allmove = a.do_step && a.do_qt && a.nseg >= 1 && (a.movmask & all) == all;   // launch_substeps_r's
-    if (allmove) launch_timed(k_substeps_lanes_pump_ens<true>, gl, bl, s, ev0, ev1, jobs, lt);
-    else launch_timed(k_substeps_lanes_pump_ens<false>, gl, bl, s, ev0, ev1, jobs, lt);
-    if (instance) *instance = allmove ? QTK_LANES_R_PUMP_FAST : QTK_LANES_R_PUMP;
+    const QTKernel inst = lane_qt_instance(a);
+    switch (inst) {
+    case QTK_LANES_R_PUMP_FAST: launch_timed(k_substeps_lanes_pump_ens<true>, gl, bl, s, ev0, ev1, jobs, lt); break;
+    case QTK_LANES_R_PUMP: launch_timed(k_substeps_lanes_pump_ens<false>, gl, bl, s, ev0, ev1, jobs, lt); break;
+    default: return hipErrorInvalidValue;             // (model 1-3, checked above: none of model 0's instances)
+    }
+    if (instance) *instance = inst;
     return hipGetLastError();
 }
 

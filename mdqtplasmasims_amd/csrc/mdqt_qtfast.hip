@@ -263,35 +263,16 @@ hipError_t launch_substeps_r(const SubstepArgs& a, const FastTab* tab, int mode,
     const dim3 gl((a.n + kLaneIons - 1) / kLaneIons), bl(kLaneWG), gt((a.n + 255) / 256), b(256);
     int inst = QTK_THREAD_R + a.qc.model;
     if (mode == 2) {
-        const uint64_t all = (1ull << a.nsub) - 1;
-        const bool allmove = a.do_step && a.do_qt && a.nseg >= 1 && !a.arrive && (a.movmask & all) == all;
-        if (a.qc.model == 0) {
-            if (allmove && a.qc.im01) {
-                if (a.expdet_zero && !a.qc.renorm) {   // the production launch
-                    launch_timed(k_substeps_lanes_im<true, true, true>, gl, bl, s, ev0, ev1, a, tab + 1);
-                    inst = QTK_LANES_IM_EDZ;
-                } else if (a.expdet_zero) {
-                    launch_timed(k_substeps_lanes_im<true, true>, gl, bl, s, ev0, ev1, a, tab + 1);
-                    inst = QTK_LANES_IM_EDZ_RN;
-                } else {
-                    launch_timed(k_substeps_lanes_im<true, false>, gl, bl, s, ev0, ev1, a, tab + 1);
-                    inst = QTK_LANES_IM;
-                }
-            } else if (allmove) {
-                launch_timed(k_substeps_lanes_r<true, true>, gl, bl, s, ev0, ev1, a, tab + 1);
-                inst = QTK_LANES_R_FAST;
-            } else {
-                launch_timed(k_substeps_lanes_r<true, false>, gl, bl, s, ev0, ev1, a, tab + 1);
-                inst = QTK_LANES_R;
-            }
-        } else {
-            if (allmove) {
-                launch_timed(k_substeps_lanes_r<false, true>, gl, bl, s, ev0, ev1, a, tab + 1);
-                inst = QTK_LANES_R_PUMP_FAST;
-            } else {
-                launch_timed(k_substeps_lanes_r<false, false>, gl, bl, s, ev0, ev1, a, tab + 1);
-                inst = QTK_LANES_R_PUMP;
-            }
+        const FastTab* lt = tab + 1;                  // by lane
+        switch (inst = lane_qt_instance(a)) {
+        case QTK_LANES_IM_EDZ: launch_timed(k_substeps_lanes_im<true, true, true>, gl, bl, s, ev0, ev1, a, lt); break;
+        case QTK_LANES_IM_EDZ_RN: launch_timed(k_substeps_lanes_im<true, true>, gl, bl, s, ev0, ev1, a, lt); break;
+        case QTK_LANES_IM: launch_timed(k_substeps_lanes_im<true, false>, gl, bl, s, ev0, ev1, a, lt); break;
+        case QTK_LANES_R_FAST: launch_timed(k_substeps_lanes_r<true, true>, gl, bl, s, ev0, ev1, a, lt); break;
+        case QTK_LANES_R: launch_timed(k_substeps_lanes_r<true, false>, gl, bl, s, ev0, ev1, a, lt); break;
+        case QTK_LANES_R_PUMP_FAST: launch_timed(k_substeps_lanes_r<false, true>, gl, bl, s, ev0, ev1, a, lt); break;
+        case QTK_LANES_R_PUMP: launch_timed(k_substeps_lanes_r<false, false>, gl, bl, s, ev0, ev1, a, lt); break;
+        default: return hipErrorInvalidValue;         // (an instance lane_qt_instance has and this switch has not)
         }
     }
     else if (a.qc.model == 0) launch_timed(k_substeps_r<0>, gt, b, s, ev0, ev1, a, tab);

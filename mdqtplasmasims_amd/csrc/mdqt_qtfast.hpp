@@ -1,7 +1,10 @@
 // lane_substeps — the lane-per-state body of the qt_math 2 substeps — and the device helpers and constants
 // it needs, shared by the single-job kernels (mdqt_qtfast.hip) and the ensemble's batched kernels
-// (mdqt_ensemble_qt.hip).  The arithmetic forms are described at the top of mdqt_qtfast.hip.
+// (mdqt_ensemble_qt.hip).  The arithmetic forms are described at the top of mdqt_qtfast.hip.  At the end, for
+// the host: which instance of it a launch runs (lane_qt_instance) — the one part a .cpp file may include.
 #pragma once
+#include "mdqt_internal.hpp"
+#if defined(__HIP__)
 #include "mdqt_device.hpp"
 #include "mdqt_pairs.hpp"
 
@@ -628,6 +631,42 @@ __device__ __forceinline__ void lane_substeps(const SubstepArgs& a, const FastTa
         g_qt_stamps[16 * wv + q] = v;
     }
 #endif
+}
+
+}  // namespace mdqt
+#endif  // __HIP__
+
+namespace mdqt {
+
+// ------------------------------------------------------------------------------------------
+// Host: the lane_substeps instance of a launch with the block `a` (every launcher of the lane kernels:
+// launch_substeps_r's mode 2, launch_substeps_r_ens, launch_substeps_r_sweep, launch_substeps_pump_ens), and
+// beside it what that choice reads.  A sweep launch runs ONE instance for members with different parameters, so
+// it is issued only where sweep_choice_differs finds no difference between the members' blocks.  CHANGE THE TWO
+// TOGETHER: lane_qt_instance may read nothing of `a` that sweep_choice_differs does not compare.
+// ------------------------------------------------------------------------------------------
+inline QTKernel lane_qt_instance(const SubstepArgs& a) {
+    const uint64_t all = (1ull << a.nsub) - 1;
+    const bool allmove = a.do_step && a.do_qt && a.nseg >= 1 && !a.arrive && (a.movmask & all) == all;
+    if (a.qc.model != 0) return allmove ? QTK_LANES_R_PUMP_FAST : QTK_LANES_R_PUMP;
+    if (!allmove) return QTK_LANES_R;
+    if (!a.qc.im01) return QTK_LANES_R_FAST;
+    if (!a.expdet_zero) return QTK_LANES_IM;
+    return a.qc.renorm ? QTK_LANES_IM_EDZ_RN : QTK_LANES_IM_EDZ;   // (without renormalisation: the production launch)
+}
+// the first of what the choice reads in which b differs from a (nullptr: none)
+inline const char* sweep_choice_differs(const SubstepArgs& a, const SubstepArgs& b) {
+    if (a.nsub != b.nsub) return "nsub";
+    if (a.do_step != b.do_step) return "do_step";
+    if (a.do_qt != b.do_qt) return "do_qt";
+    if (a.movmask != b.movmask) return "movmask (t > 0 per substep)";
+    if (a.expdet_zero != b.expdet_zero) return "expdet_zero (fracOfSig == 0 against != 0)";
+    if (a.qc.im01 != b.qc.im01) return "qt_im01";
+    if (a.qc.renorm != b.qc.renorm) return "reNormalizewvFns";
+    if (a.qc.model != b.qc.model) return "qt_model";
+    if ((a.nseg >= 1) != (b.nseg >= 1)) return "nseg";
+    if (!a.arrive != !b.arrive || !a.U != !b.U) return "arrive / U (another launch scheme)";
+    return nullptr;
 }
 
 }  // namespace mdqt

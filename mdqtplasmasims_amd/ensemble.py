@@ -22,12 +22,12 @@ state is bit for bit what :class:`~mdqtplasmasims_amd.engine.Simulation` gives f
 from __future__ import annotations
 
 import ctypes as C
-import itertools
 
 import numpy as np
 
 from ._ensemble_base import _EnsembleBase
 from ._lib import MdqtParams, check, dptr, lib
+from ._sweep import sweep_points
 from .engine import NBINS, Simulation, default_params
 
 
@@ -41,35 +41,10 @@ def job_params(base: MdqtParams, k: int) -> MdqtParams:
 SWEEP_FIELDS = ("detuning", "detuningDP", "Om", "OmDP", "fracOfSig")
 
 
-def _sweep_points(base: MdqtParams, sweep):
-    """(the points' swept values as dicts, the points as a C array): the Cartesian product of the lists of
-    `sweep` ({name: values}), the first-named axis slowest — or, where `sweep` is a list of {name: value} dicts,
-    those points as they stand; every other field from `base`"""
-    if isinstance(sweep, dict):
-        names = list(sweep)
-        for name in names:
-            if len(sweep[name]) < 1:
-                raise ValueError(f"sweep: no values for {name!r}")
-        values = [dict(zip(names, v)) for v in itertools.product(*(sweep[n] for n in names))]
-    else:
-        values = [dict(point) for point in sweep]
-        if not values:
-            raise ValueError("sweep: no points")
-    for name in {n for point in values for n in point}:
-        if name not in SWEEP_FIELDS:
-            raise ValueError(f"sweep: {name!r} is not one of {', '.join(SWEEP_FIELDS)}")
-    arr = (MdqtParams * len(values))()
-    for q, point in enumerate(values):
-        C.memmove(C.byref(arr[q]), C.byref(base), C.sizeof(MdqtParams))
-        for name, v in point.items():
-            setattr(arr[q], name, float(v))
-    return values, arr
-
-
 def sweep_params(base: MdqtParams, sweep, njobs: int, k: int) -> MdqtParams:
     """member k's parameters of a sweep ensemble of `njobs` replicas per point (point k // njobs, replica k % njobs:
     job + r, seed + r), after the checks mdqt_ensemble_create_sweep makes of the points (host only)"""
-    _, arr = _sweep_points(base, sweep)
+    _, arr = sweep_points(base, sweep, SWEEP_FIELDS)
     out = MdqtParams()
     check(lib().mdqt_ensemble_sweep_params(arr, len(arr), int(njobs), int(k), C.byref(out)), "ensemble_sweep_params")
     return out
@@ -107,7 +82,7 @@ class Ensemble(_EnsembleBase):
             check(lib().mdqt_ensemble_create(C.byref(self.params), self.njobs, C.byref(h)), "mdqt_ensemble_create")
             member = [job_params(self.params, k) for k in range(lib().mdqt_ensemble_size(h))]
         else:
-            self.points, arr = _sweep_points(self.params, sweep)
+            self.points, arr = sweep_points(self.params, sweep, SWEEP_FIELDS)
             check(lib().mdqt_ensemble_create_sweep(arr, len(arr), self.njobs, C.byref(h)), "mdqt_ensemble_create_sweep")
             member = [job_params(arr[k // self.njobs], k % self.njobs) for k in range(lib().mdqt_ensemble_size(h))]
         self.h = h

@@ -6,11 +6,11 @@ no CPU fallback.  Method names follow the reference's functions.
 from __future__ import annotations
 
 import ctypes as C
-import itertools
 
 import numpy as np
 
 from ._lib import MdlcParams, check, dptr, lib
+from ._sweep import sweep_points
 
 
 def default_params(**over) -> MdlcParams:
@@ -45,31 +45,6 @@ def format_directory(params: MdlcParams | None = None, job: int | None = None, *
 SWEEP_FIELDS = ("detuning", "Om", "temperature")
 
 
-def _sweep_points(base: MdlcParams, sweep):
-    """(the points' swept values as dicts, the points as a C array): the Cartesian product of the lists of
-    `sweep` ({name: values}), the first-named axis slowest — or, where `sweep` is a list of {name: value} dicts,
-    those points as they stand; every other field from `base`"""
-    if isinstance(sweep, dict):
-        names = list(sweep)
-        for name in names:
-            if len(sweep[name]) < 1:
-                raise ValueError(f"sweep: no values for {name!r}")
-        values = [dict(zip(names, v)) for v in itertools.product(*(sweep[n] for n in names))]
-    else:
-        values = [dict(point) for point in sweep]
-        if not values:
-            raise ValueError("sweep: no points")
-    for name in {n for point in values for n in point}:
-        if name not in SWEEP_FIELDS:
-            raise ValueError(f"sweep: {name!r} is not one of {', '.join(SWEEP_FIELDS)}")
-    arr = (MdlcParams * len(values))()
-    for q, point in enumerate(values):
-        C.memmove(C.byref(arr[q]), C.byref(base), C.sizeof(MdlcParams))
-        for name, v in point.items():
-            setattr(arr[q], name, float(v))
-    return values, arr
-
-
 def sweep_params(points, k: int) -> MdlcParams:
     """member k's parameters of a scan over `points` (a sequence of MdlcParams, each with njobs = R replicas) as a
     single job: point k // R, replica k % R (job + r, njobs = 1), after the checks mdlc_create_sweep makes of
@@ -97,7 +72,7 @@ class LaserCooling:
             self.points, self._points = [{}], (MdlcParams * 1)(self.p)
             check(lib().mdlc_create(C.byref(self.p), C.byref(h)), "mdlc_create")
         else:
-            self.points, self._points = _sweep_points(self.p, sweep)
+            self.points, self._points = sweep_points(self.p, sweep, SWEEP_FIELDS)
             check(lib().mdlc_create_sweep(self._points, len(self._points), C.byref(h)), "mdlc_create_sweep")
         self._h = h
         self.N0 = int(self.p.N0)

@@ -109,6 +109,52 @@ def test_refuses_a_fixed_field_that_differs(L, field, value):
     assert "point 2 differs from point 0" in msg and re.search(rf"\bin {field}\b", msg), msg
 
 
+def test_every_field_is_swept_or_fixed(L):
+    """no field of mdqt_params is in neither list: a second point that differs from point 0 in one field alone is
+    accepted where the field is swept and refused by that field's name where it is not"""
+    from mdqtplasmasims_amd._lib import MdqtParams
+    from mdqtplasmasims_amd.ensemble import SWEEP_FIELDS
+    assert SWEEP_FIELDS == SWEPT
+    swept = fixed = 0
+    for name, ctype in MdqtParams._fields_:
+        arr = points_of({}, {}, fracOfSig=1.0)                         # (non-zero: fracOfSig + 0.5 stays on its side of 0)
+        old = getattr(arr[0], name)
+        setattr(arr[1], name, b"elsewhere/" if isinstance(old, bytes) else old + (0.5 if ctype is C.c_double else 1))
+        if name in SWEEP_FIELDS:                                       # + 0.5: x 100 another integer
+            out = MdqtParams()
+            assert L.mdqt_ensemble_sweep_params(arr, 2, 1, 1, C.byref(out)) == 0, (name, L.mdqt_last_error())
+            assert getattr(out, name) == old + 0.5
+            swept += 1
+        else:
+            msg = refused(L, arr, 2, 1)
+            assert re.search(rf"point 1 differs from point 0 in {name}\b", msg), (name, msg)
+            fixed += 1
+    assert (fixed, swept) == (22, 5) and fixed + swept == len(MdqtParams._fields_)
+
+
+def test_sweep_params_three_axes_against_itertools(L):
+    import itertools
+    from mdqtplasmasims_amd import sweep_params
+    sweep = {"detuningDP": [0.0, 1.0], "Om": [0.5, 0.75, 1.0], "detuning": [-1.0, -2.0]}   # lengths 2, 3, 2
+    want = list(itertools.product(*sweep.values()))
+    assert len(want) == 12
+    for k in range(24):
+        p = sweep_params(base_params(), sweep, 2, k)
+        assert (p.detuningDP, p.Om, p.detuning) == want[k // 2] and p.job == 7 + k % 2, k
+
+
+def test_parse_sweep_args():
+    from mdqtplasmasims_amd._sweep import parse_sweep_args
+    assert parse_sweep_args([]) == {}
+    got = parse_sweep_args(["Om:0.5,1", "detuning:-1"])
+    assert got == {"Om": [0.5, 1.0], "detuning": [-1.0]} and list(got) == ["Om", "detuning"]   # the order given
+    for bad in (["Om:0.5", "Om:1"], ["Om:"], ["Om"]):                  # a NAME twice, an empty list, no list
+        with pytest.raises(ValueError, match="each NAME once"):
+            parse_sweep_args(bad)
+    with pytest.raises(ValueError):
+        parse_sweep_args(["Om:1,x"])
+
+
 @pytest.mark.parametrize("field, value, word", [("world_size", 2, "world_size"), ("rng_mode", 0, "rng_mode"),
                                                  ("qt_model", 1, "qt_model")])
 def test_refuses_what_the_ensemble_refuses(L, field, value, word):

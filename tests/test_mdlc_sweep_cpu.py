@@ -93,6 +93,26 @@ def test_refuses_a_fixed_field_that_differs(L):
     assert "point 2 differs from point 0 in vKick" in msg and "no level for vKick" in msg
 
 
+def test_every_field_is_swept_or_fixed(L):
+    """no field of mdlc_params is in neither list: a second point that differs from point 0 in one field alone is
+    accepted where the field is swept and refused by that field's name where it is not"""
+    import ctypes as C
+    from mdqtplasmasims_amd._lib import MdlcParams
+    from mdqtplasmasims_amd.mdlc import SWEEP_FIELDS, sweep_params
+    swept = fixed = 0
+    for name, ctype in MdlcParams._fields_:
+        pts = points([{}, {}], njobs=2)
+        old = getattr(pts[0], name)
+        setattr(pts[1], name, b"elsewhere/" if isinstance(old, bytes) else old + (0.5 if ctype is C.c_double else 1))
+        if name in SWEEP_FIELDS:                              # + 0.5: x 100 (x 1000000) another integer
+            assert getattr(sweep_params(pts, 2), name) == old + 0.5, name
+            swept += 1
+        else:
+            assert re.search(rf"point 1 differs from point 0 in {name}\b", refusal(pts)), name
+            fixed += 1
+    assert (fixed, swept) == (11, 3) and fixed + swept == len(MdlcParams._fields_)
+
+
 def test_refuses_identical_points(L):
     pts = points([dict(detuning=-0.5), dict(detuning=-1.0), dict(detuning=-0.5)])
     msg = refusal(pts)
@@ -163,11 +183,37 @@ def test_cli_print_directory_of_a_scan(L):
     assert got[4] == "dataLaserCoolTestDoppShift/Om50/Det-100NumIons1000InitialTemp10000uK/job3/"
 
 
-@pytest.mark.parametrize("arg", ["--sweep=vKick:1,2", "--sweep=Om:", "--sweep=Om", "--sweep=Om:0.5,x"])
+def test_cli_print_directory_of_three_axes(L):
+    """axis lengths 2, 3 and 2: the command line's product against Python's, the first-given NAME slowest"""
+    import itertools
+    from mdqtplasmasims_amd._lib import MDLC_CLI_PATH
+    from mdqtplasmasims_amd.mdlc import format_directory, sweep_params
+    axes = {"Om": (0.5, 1), "temperature": (0.01, 0.02, 0.03), "detuning": (-0.5, -1)}
+    r = subprocess.run([MDLC_CLI_PATH, "3", "--print-directory=1", "--njobs=2",
+                        *(f"--sweep={n}:{','.join(map(str, v))}" for n, v in axes.items())], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = r.stdout.splitlines()
+    pts = points([dict(zip(axes, v)) for v in itertools.product(*axes.values())], njobs=2, job=3)
+    assert got == [format_directory(sweep_params(pts, k)) for k in range(24)]
+    assert len(set(got)) == 24
+    assert got[2] == "dataLaserCoolTestDoppShift/Om50/Det-100NumIons1000InitialTemp10000uK/job3/"   # last NAME fastest
+    assert got[4] == "dataLaserCoolTestDoppShift/Om50/Det-50NumIons1000InitialTemp20000uK/job3/"
+    assert got[12] == "dataLaserCoolTestDoppShift/Om100/Det-50NumIons1000InitialTemp10000uK/job3/"
+
+
+@pytest.mark.parametrize("arg", [
+    "--sweep=vKick:1,2", "--sweep=Om:", "--sweep=Om", "--sweep=Om:0.5,x",
+    "--sweep=nothing:1,2", "--sweep=Omx:1,2",                          # unknown NAME, a NAME and more
+    "--sweep=Om:1,,2", "--sweep=Om:1,2,", "--sweep=Om:1e",
+    pytest.param(("--sweep=Om:0.5,1", "--sweep=Om:2,3"), id="a-NAME-twice"),
+    pytest.param("--sweep=Om:" + ",".join(str(0.01 * i) for i in range(1025)), id="1025-values"),
+])
 def test_cli_bad_axis_is_usage(L, arg):
     from mdqtplasmasims_amd._lib import MDLC_CLI_PATH
-    r = subprocess.run([MDLC_CLI_PATH, "1", "--print-directory=1", arg], capture_output=True, text=True)
+    args = (arg,) if isinstance(arg, str) else arg
+    r = subprocess.run([MDLC_CLI_PATH, "1", "--print-directory=1", *args], capture_output=True, text=True)
     assert r.returncode == 2 and r.stderr.startswith("usage: mdlc <job>") and "--sweep=NAME:v1,v2" in r.stderr
+    assert r.stdout == ""
 
 
 def test_cli_axis_given_twice_is_usage(L):

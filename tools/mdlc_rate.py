@@ -71,17 +71,16 @@ def main():
 
     import numpy as np
     from mdqtplasmasims_amd import LaserCooling
+    from mdqtplasmasims_amd._sweep import parse_sweep_args
 
     if not os.path.exists(a.asm):
         subprocess.run(["make", "-C", os.path.join(ROOT, "mdqtplasmasims_amd", "csrc"), "asm"], check=True,
                        stdout=subprocess.DEVNULL)
     n64, flop, valu = count_loop_fp64(a.asm)
-    sweep = {}
-    for ax in a.sweep:
-        name, _, vals = ax.partition(":")
-        if name in sweep or not vals:
-            ap.error(f"--sweep {ax}: NAME:v1,v2,... with each NAME once")
-        sweep[name] = [float(v) for v in vals.split(",")]
+    try:
+        sweep = parse_sweep_args(a.sweep)
+    except ValueError as e:
+        ap.error(str(e))
     npoints = int(np.prod([len(v) for v in sweep.values()])) if sweep else 1
     rows = {}
     base = None

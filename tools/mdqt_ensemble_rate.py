@@ -128,15 +128,14 @@ def main():
     a = ap.parse_args()
 
     import mdqtplasmasims_amd as M
+    from mdqtplasmasims_amd._sweep import parse_sweep_args
     params = dict(CONFIGS[a.config], device=a.device)
     jobs = [int(x) for x in a.jobs.split(",") if x]
     streams = [int(x) for x in a.streams.split(",") if x]
-    sweep = {}
-    for item in a.sweep:
-        name, _, values = item.partition(":")
-        if name in sweep or not values:
-            ap.error(f"--sweep {item}: NAME:v1,v2,..., each NAME once")
-        sweep[name] = [float(v) for v in values.split(",")]
+    try:
+        sweep = parse_sweep_args(a.sweep)
+    except ValueError as e:
+        ap.error(str(e))
     npoints = 1
     for values in sweep.values():
         npoints *= len(values)
