@@ -5,6 +5,7 @@
 // bit for bit as the single job with its parameters.  The arithmetic and its limits: mdlc_kernels.hip.
 #pragma once
 
+#include "mdlc_kernels.hpp"
 #include "mdqt_device.hpp"
 
 namespace mdqt {

@@ -10,12 +10,17 @@
 #include <string.h>
 #include <sys/stat.h>
 
+#include <memory>
 #include <random>
 #include <string>
 #include <vector>
 
 #include "../../include/mdlc.h"
-#include "mdqt_ctx.hpp"   // HIPCHK, mdqt::set_error
+#include "mdlc_kernels.hpp"
+#include "mdqt_batch.hpp"    // LaunchTimer
+#include "mdqt_devbuf.hpp"
+#include "mdqt_error.hpp"    // HIPCHK, mdqt::set_error
+#include "mdqt_lgtext.hpp"   // LgText: energies.dat's "%lg" rows
 #include "mdqt_mt32.hpp"
 #include "mdqt_sweep.hpp"
 

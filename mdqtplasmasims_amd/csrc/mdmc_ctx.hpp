@@ -8,7 +8,11 @@
 #include <vector>
 
 #include "../../include/mdmc.h"
-#include "mdqt_ctx.hpp"    // HIPCHK, mdqt::set_error, mdqt_batch.hpp's PinRing and LaunchTimer
+#include "mdmc_kernels.hpp"
+#include "mdqt_batch.hpp"    // PinRing, LaunchTimer
+#include "mdqt_devbuf.hpp"
+#include "mdqt_error.hpp"    // HIPCHK, mdqt::set_error
+#include "mdqt_internal.hpp" // QTConst, FastTab, N3Args, SubstepArgs: shared with MDQT
 #include "mdqt_mt32.hpp"   // Mt32: the reference's std::mt19937 with the state in plain view
 
 struct mdmc_ctx {

@@ -4,7 +4,8 @@
 // of its own launch — one body, inlined into both (as mc_lds_chain and lane_substeps are).
 #pragma once
 
-#include "mdqt_internal.hpp"
+#include "mdmc_kernels.hpp"
+#include "mdqt_math.hpp"
 
 namespace mdqt {
 

@@ -12,6 +12,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <memory>
 #include <random>
 #include <string>
 #include <vector>

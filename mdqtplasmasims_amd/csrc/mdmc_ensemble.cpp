@@ -16,7 +16,9 @@
 #include <algorithm>
 #include <memory>
 
+#include "../../include/mdqt.h"   // mdqt_last_error
 #include "mdmc_ctx.hpp"
+#include "mdqt_ens_args.hpp"      // the QT tagging ensemble's QT and tag launches are the pump ensemble's
 
 using namespace mdqt;
 

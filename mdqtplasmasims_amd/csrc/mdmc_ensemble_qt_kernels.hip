@@ -10,6 +10,7 @@
 //
 // The argument blocks are per member, in device memory, and are copied to registers at entry; a workgroup
 // past its member's last chunk returns before any barrier or LDS use (a condition on blockIdx and the block).
+#include "mdmc_kernels.hpp"
 #include "mdqt_pump_device.hpp"
 
 namespace mdqt {

@@ -3,7 +3,7 @@
 
 #include <algorithm>
 
-#include "mdqt_ctx.hpp"   // HIPCHK, mdqt::set_error, kTimingEventFlags
+#include "mdqt_error.hpp"   // HIPCHK, mdqt::set_error, kTimingEventFlags
 
 using namespace mdqt;
 

@@ -1,7 +1,8 @@
-// The host engine's private header: the context of one simulation (struct mdqt_ctx), the ensemble over
-// several of them (struct mdqt_ensemble), the error plumbing every host source shares, and the host
-// functions that cross a file boundary (namespace mdqt, as the kernel launchers of mdqt_internal.hpp).
-// Not installed: the C ABI of include/mdqt.h sees both structs as opaque.  The host engine by file: DESIGN.md §1.
+// The host engine's private header: the context of one simulation (struct mdqt_ctx) and the host functions of
+// one context that cross a file boundary (namespace mdqt, as the kernel launchers of mdqt_internal.hpp and
+// mdqt_n3b_args.hpp).  The ensembles over several contexts: mdqt_ensemble.hpp; the error plumbing every host
+// source shares: mdqt_error.hpp.
+// Not installed: the C ABI of include/mdqt.h sees the struct as opaque.  The host engine by file: DESIGN.md §1.
 #pragma once
 
 #include <stdint.h>
@@ -16,23 +17,16 @@
 #include "../../include/mdqt.h"
 #include "mdqt_batch.hpp"
 #include "mdqt_devbuf.hpp"
+#include "mdqt_error.hpp"
 #include "mdqt_internal.hpp"
 #include "mdqt_main_loops.hpp"
+#include "mdqt_n3b_args.hpp"
 #include "mdqt_writer.hpp"
 
 // rccl.h is included only where a collective is issued (mdqt_step.cpp, mdqt_comm.cpp); the context
 // just holds the handle
 struct ncclComm;
 typedef struct ncclComm* ncclComm_t;
-
-// mdqt::set_error (mdqt_engine.cpp) records the calling thread's message for mdqt_last_error, mdmc_last_error
-// and mdlc_last_error, and returns -1
-#define HIPCHK(expr)                                                                  \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess)                                                         \
-            return mdqt::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 #define NCCLCHK(expr)                                                                   \
     do {                                                                                \
@@ -221,67 +215,11 @@ struct mdqt_ctx {
     hipEvent_t bd_ag[2] = {nullptr, nullptr};   // the all-gather just before the next timed force call
 };
 
-// J independent jobs stepped in batched launches (mdqt_ensemble.cpp)
-struct mdqt_ensemble {
-    std::vector<mdqt_ctx*> jobs;
-    int dev = 0;
-    hipStream_t stream = nullptr;                  // jobs[0]'s own stream, shared by every member
-    std::unique_ptr<mdqt::FileWriter> writer;            // the members' output files (<= 16 threads in all)
-    mdqt::DevBuf<mdqt::N3Args> dForce;                   // [J] the batched force launch's blocks (Newton-3 members, packed)
-    mdqt::DevBuf<mdqt::SubstepArgs> dSub;                // [sub_blocks] the batched QT launches' blocks: [launch][J]
-    int sub_blocks = 0;                            // max(J, 1024): mdqt_ensemble_md_steps builds launches ahead
-    std::vector<mdqt::N3Args> force_held;                // what dForce holds
-    mdqt::PinRing ring;                            // 8 slots: a launch's blocks of either kind, or md_steps' blocks ahead
-    int qt_waves = 0;                              // option "qt_waves": register budget of the production QT instance
-    bool timing = false;
-    mdqt::LaunchTimer timers[2];                   // 0 = force launches, 1 = QT launches
-    unsigned long long force_launches = 0;         // force launches issued by ens_forces (batched + the row members' own)
-    // a sweep ensemble (mdqt_ensemble_create_sweep): npoints parameter points x replicas, member k = point
-    // k / replicas; its QT launches are mdqt_ensemble_sweep_qt.hip's, which take the table per member
-    int npoints = 1;
-    bool sweep = false;                            // created through the sweep entry (one point included)
-    mdqt::DevBuf<mdqt::FastTab> dTabs;             // [npoints] the points' by-lane tables (their first replica's ftabL)
-    mdqt::DevBuf<int> dPoint;                      // [J] every member's point
-    std::vector<mdqt::FastTab> tabs_held;          // what they hold
-    std::vector<int> point_held;
-    // the batched output() (mdqt_ensemble_output.cpp): the members' blocks, their results on the device (rows
-    // [J][kObsRow] in dScr's layout, the packed columns [sum 4 N_k]) and the pinned slot they come back to
-    int output_batch = 0;                          // option "output_batch": 1 = one pass for all members, 0 = member by member
-                                                   // (the default: docs/PROGRAMS.md "Batched output()" has the measurement)
-    mdqt::DevBuf<mdqt::N3Args> dPot;               // [J] the potential launch's blocks (batched members, packed)
-    mdqt::DevBuf<mdqt::EnsObsArgs> dObs;           // [J] the observables' blocks (the same members)
-    std::vector<mdqt::N3Args> pot_held;            // what they hold
-    std::vector<mdqt::EnsObsArgs> obs_held;
-    mdqt::DevBuf<double> dObsRows;                 // [J][kObsRow]
-    mdqt::DevBuf<double> dObsCols;                 // [sum 4 N_k]
-    mdqt::PinRing obs_ring;                        // one slot: the rows, then the columns
-    unsigned long long output_launches = 0;        // kernel launches of the batched output path
-    mdqt::LaunchTimer obs_timers[2];               // 0 = the batched potential launches, 1 = the batched KDE launches
-};
-
-// J independent jobs of an optical-pumping program stepped in batched launches (mdqt_pump_ensemble.cpp): an
-// mdqt_ensemble's members, stream, argument ring, force launch and writer pool, and the pump kernels' blocks
-struct mdqt_pump_ensemble {
-    mdqt_ensemble* base = nullptr;
-    mdqt::DevBuf<mdqt::PumpStepArgs> dStep[2];           // [J] the leading drift's blocks, the kick launch's blocks
-    std::vector<mdqt::PumpStepArgs> step_held[2];        // what they hold
-    mdqt::DevBuf<mdqt::PumpTagArgs> dTag;                // [J]
-    mdqt::DevBuf<mdqt::PumpKdeArgs> dKde;                // [J]
-    unsigned long long launches = 0;                     // the pump kernels' launches (the force launches: base)
-    mdqt::LaunchTimer kick_timer;                        // the kick launches' timestamps
-};
-
 namespace mdqt {
 
 constexpr double TIMESTEP = 0.002;   // SpeedUp:80
 constexpr int NINTERVALV = 13;       // numberOfIntervalV, SpeedUp:105
 inline double u64_as_double(unsigned long long u) { double d; memcpy(&d, &u, sizeof d); return d; }
-
-// Timing events only measure: no system-scope release/acquire when they complete.  With the
-// default flags every timed launch ended in an L2 write-back + invalidate that cost the MD step
-// ~20 us (kernel trace of the driver's bench command: gaps of 6.5 / 8.9 / 4.8 us around each
-// timed pair of launches, none elsewhere).
-constexpr unsigned kTimingEventFlags = hipEventDisableSystemFence;
 
 // is this launch of timing kind k (0 = force, 1 = substeps) one of the timed ones?  Advances the kind's count.
 inline bool launch_timed(mdqt_ctx* s, int k) {
@@ -357,28 +295,7 @@ int pump_vaf_host(mdqt_ctx* s, const std::vector<double>& V, int c1V);
 int pump_write_conditions(mdqt_ctx* s, int c0);
 int pump_read_conditions(mdqt_ctx* s, int c0);
 PumpSchedule pump_schedule(const mdqt_ctx* s);   // the pump time loop's, of a context or of an ensemble's member 0
-
-// mdqt_ensemble.cpp: the ensemble's machinery the pump ensemble reuses
-// members: npoints parameter points (mdqt_ensemble_create and the pump ensemble: one) x njobs replicas, point-major;
-// sweep: the ensemble owns the points' tables and launches the sweep QT kernels
-int ensemble_create(const mdqt_params* points, int npoints, int njobs, mdqt_ensemble** out, const char* what, bool pump,
-                    bool sweep = false);
 inline bool tagged(const mdqt_ctx* s) { return !s->spinUp.empty(); }   // measureSpinUps() has run (pump programs)
-int ens_check(const mdqt_ensemble* e, const char* what, bool pump = false);
-int ens_forces(mdqt_ensemble* e);
-// the fused step();qstep() (do_step 1) or qstep() (0) launches of every member: `launch` issues one (blocks:
-// the host copies of the launch's blocks, member by member; 0 or, after set_error, -1)
-using EnsQtLaunch = std::function<int(const SubstepArgs* blocks, int maxn, hipEvent_t e0, hipEvent_t e1, int* inst)>;
-int ens_qt_chunks(mdqt_ensemble* e, int n, int do_step, const EnsQtLaunch& launch);
-int ens_range_flags(mdqt_ensemble* e, bool drain = true);
-
-// mdqt_ensemble_output.cpp: output() of every member in one device pass
-int ens_output(mdqt_ensemble* e);
-int ens_epotential(mdqt_ensemble* e, double* Epot);
-// the same queued without a synchronisation (the pump ensemble's output, which has one of its own): after it,
-// batched member member[q]'s Epotential() is ens_epot_of(job, rows + 64 q)
-int ens_epotential_queue(mdqt_ensemble* e, std::vector<int>& member, const double** rows);
-double ens_epot_of(const mdqt_ctx* s, const double* row);
 
 // mdqt_options.cpp (timing events)
 int mark(mdqt_ctx* s, int k);

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "mdqt_internal.hpp"
+#include "mdqt_math.hpp"
 
 #include <math.h>
 

@@ -5,6 +5,7 @@
 // values in LDS).
 #include "mdqt_devbuf.hpp"
 #include "mdqt_device.hpp"
+#include "mdqt_error.hpp"
 #include "mdqt_pairs.hpp"
 
 #include "mdqt.h"

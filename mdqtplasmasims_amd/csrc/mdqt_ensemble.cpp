@@ -17,7 +17,7 @@
 
 #include <algorithm>
 
-#include "mdqt_ctx.hpp"
+#include "mdqt_ensemble.hpp"
 #include "mdqt_qtfast.hpp"   // sweep_choice_differs (the host part)
 #include "mdqt_sweep.hpp"
 

@@ -3,6 +3,7 @@
 // it is without the ensemble (a larger code object cost the single-job QT launch 0.2 us of 18.5, measured).
 // Built with mdqt_forces.hip's flags (Makefile FORCESFLAGS).  The kernel template is mdqt_pairs_ens.hpp's;
 // this unit holds the SpeedUp ensemble's instances (variants 0 and 1).
+#include "mdqt_ens_args.hpp"
 #include "mdqt_pairs_ens.hpp"
 
 namespace mdqt {

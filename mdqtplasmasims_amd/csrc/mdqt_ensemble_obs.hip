@@ -11,6 +11,7 @@
 // barrier, LDS use or cross-lane operation.  The blocks' pointers come from memory, so the accesses are flat.
 // Built with mdqt_forces.hip's flags (Makefile FORCESFLAGS: the pair kernel's), and, as everything here,
 // -ffp-contract=off; the flag only keeps the vectorizer from packing operations and changes no value.
+#include "mdqt_ens_args.hpp"
 #include "mdqt_obs_device.hpp"
 #include "mdqt_pairs.hpp"
 

@@ -20,7 +20,7 @@
 
 #include <algorithm>
 
-#include "mdqt_ctx.hpp"
+#include "mdqt_ensemble.hpp"
 
 using namespace mdqt;
 

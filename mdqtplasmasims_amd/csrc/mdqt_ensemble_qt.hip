@@ -3,6 +3,7 @@
 // what it is without the ensemble (a larger code object cost the single-job QT launch 0.2 us of 18.5,
 // measured).  The kernels wrap lane_substeps (mdqt_qtfast.hpp).  Built with mdqt_qtfast.hip's flags
 // (Makefile QTSCHED).
+#include "mdqt_ens_args.hpp"
 #include "mdqt_qtfast.hpp"
 
 namespace mdqt {

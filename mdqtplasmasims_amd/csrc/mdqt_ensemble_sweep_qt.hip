@@ -2,6 +2,7 @@
 // translation unit — hence a code object — of their own: mdqt_ensemble_qt.hip's and mdqt_qtfast.hip's stay
 // byte for byte what they are without the sweep.  The kernels wrap lane_substeps (mdqt_qtfast.hpp).  Built
 // with mdqt_qtfast.hip's flags (Makefile QTSCHED).
+#include "mdqt_ens_args.hpp"
 #include "mdqt_qtfast.hpp"
 
 namespace mdqt {

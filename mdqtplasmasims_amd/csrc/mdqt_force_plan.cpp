@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "mdqt_ctx.hpp"
+#include "mdqt_math.hpp"   // the pair forms' error constants
 
 using namespace mdqt;
 

@@ -95,7 +95,7 @@ __device__ __forceinline__ float row_rol1f(float v) {   // lane 16 a + m <- lane
 }
 
 // An ultra-far tile pair (boxes >= r_ufar32 apart) with a uniform image, pair terms in f32
-// (error analysis and bound in mdqt_internal.hpp kUfar32A/B).  Round 5: the staging wave
+// (error analysis and bound in mdqt_math.hpp kUfar32A/B).  Round 5: the staging wave
 // also holds the J tile in f32 relative to its first ion c_J (pj32 = fl32(xj - c_J)), the wave takes
 // xi32 = fl32(xi - n L - c_J) once per tile pair and dx = fl32(xi32 - pj32) — no f64 subtraction and
 // f32 conversion per pair — and runs two rotation steps t, t + 1 through each packed

@@ -4,6 +4,8 @@
 // of an unplanned call agree bit for bit.
 #pragma once
 #include "mdqt_internal.hpp"
+#include "mdqt_math.hpp"
+#include "mdqt_n3b_args.hpp"
 
 #include <math.h>
 

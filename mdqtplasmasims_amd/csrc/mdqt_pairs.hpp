@@ -2,6 +2,7 @@
 // kernels (mdqt_forces.hip) and the fused MD-step kernel (mdqt_qtfast.hip).
 #pragma once
 #include "mdqt_internal.hpp"
+#include "mdqt_math.hpp"
 
 #include <math.h>
 
@@ -184,7 +185,7 @@ __device__ __forceinline__ double pair_ft_cut_far(double dx, double dy, double d
     return ((ri + c.invlDeb) * exp2_neg_cut6(dr * (c.invlDeb * kNegLog2e), dr < c.Rcut)) * (ri * ri);
 }
 
-// pair_ft_cut of a very far tile pair: the raw v_rsq_f64 and the degree-5 2^f (mdqt_internal.hpp);
+// pair_ft_cut of a very far tile pair: the raw v_rsq_f64 and the degree-5 2^f (mdqt_math.hpp);
 // the cutoff on r^2 (c.rc2 = Rcut^2), not on the raw rsq's r (2^-23: pairs at L/2 would flip)
 __device__ __forceinline__ double pair_ft_cut_vfar(double dx, double dy, double dz, const PairC& c) {
     const double r2 = fma(dx, dx, fma(dy, dy, dz * dz));

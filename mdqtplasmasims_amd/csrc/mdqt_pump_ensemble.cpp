@@ -19,7 +19,7 @@
 
 #include <algorithm>
 
-#include "mdqt_ctx.hpp"
+#include "mdqt_ensemble.hpp"
 
 using namespace mdqt;
 

@@ -3,13 +3,14 @@
 // of their own, so that the single-job kernels' code objects stay what they are.  Every kernel takes a
 // device array of per-member argument blocks indexed by a grid axis and runs its single-job kernel's body
 // (lane_substeps of mdqt_qtfast.hpp; leapfrog_kick, leapfrog_drift, tag_spin_up_ion, tagged_kde_chunk and
-// tagged_kde_reduce_1 of mdqt_pump_device.hpp; the canonical slot sum of mdqt_internal.hpp — slot_sum16's
+// tagged_kde_reduce_1 of mdqt_pump_device.hpp; the canonical slot sum of mdqt_math.hpp — slot_sum16's
 // chains and tree16_sum, loaded in rounds: pump_settled_forces) on the member's own arguments: bit-identical
 // to the member on its own.  Workgroups past a member's last ion, 16-ion group
 // or chunk leave at once — a condition on blockIdx and the block, uniform over the workgroup, before any
 // barrier or cross-lane operation.  The blocks' pointers come from memory, so the accesses are flat.
 // Built with mdqt_qtfast.hip's flags (Makefile QTSCHED) and, as everything here, -ffp-contract=off:
 // v += kick * f stays a product and a sum.
+#include "mdqt_ens_args.hpp"
 #include "mdqt_qtfast.hpp"
 #include "mdqt_pump_device.hpp"
 

@@ -21,7 +21,7 @@ static_assert(kLaneWG % 64 == 0 && kLaneWG >= 128, "whole waves; the first 128 t
 constexpr int kRows = 4;                             // ions per wave of the lane kernels: one per row of 16 lanes
 constexpr int kLaneIons = kLaneWG / 64 * kRows;      // ions per workgroup
 
-__device__ __forceinline__ double rsq_nr(double x) { return rsq3(x); }   // 1/sqrt(x), mdqt_internal.hpp
+__device__ __forceinline__ double rsq_nr(double x) { return rsq3(x); }   // 1/sqrt(x), mdqt_math.hpp
 __device__ __forceinline__ double nrm2(cxd y) { return fma(y.re, y.re, y.im * y.im); }
 __device__ __forceinline__ double rho_im_r(cxd a, cxd b) { return fma(a.im, b.re, -(a.re * b.im)); }
 

@@ -16,7 +16,7 @@
 //                    16-ion sub-tile
 // Skipped pairs would have added exact zeros, so the forces are bit-identical with and without
 // the skipping for a given order (tests/test_gpu_large.py checks it).
-#include "mdqt_internal.hpp"
+#include "mdqt_n3b_args.hpp"
 
 #include <hipcub/hipcub.hpp>
 

@@ -11,7 +11,7 @@
 
 #include <string>
 
-#include "mdqt_internal.hpp"   // set_error, ref_udcast
+#include "mdqt_error.hpp"   // set_error, ref_udcast
 
 namespace mdqt {
 

@@ -3,7 +3,7 @@
 // The reference formats every number with fprintf("%lg") on the simulation thread, so at the
 // reference cadence (output() every sampleFreq MD steps, writeConditions at the end) text
 // formatting is most of an MD interval at N = 3.5k.  Here:
-//   * LgText formats with std::to_chars(general, precision 6), which is specified to produce
+//   * LgText (mdqt_lgtext.hpp) formats with std::to_chars(general, precision 6), which is specified to produce
 //     exactly printf("%.6g") in the C locale (= "%lg") — same bytes, several times faster; non-
 //     finite values go through snprintf so "inf"/"-nan" spellings stay glibc's;
 //   * FileWriter formats and writes whole files on a few background threads from snapshots the
@@ -29,45 +29,9 @@
 #include <thread>
 #include <vector>
 
+#include "mdqt_lgtext.hpp"
+
 namespace mdqt {
-
-// "%lg" text into a growing buffer, spilled to the FILE every ~1 MB (bounded memory at N = 1M)
-class LgText {
-  public:
-    explicit LgText(FILE* f = nullptr) : f_(f) { s_.reserve(kSpill + 4096); }
-    ~LgText() { spill(); }
-    void num(double x) {
-        char b[40];
-        if (std::isfinite(x)) {
-            auto r = std::to_chars(b, b + sizeof b, x, std::chars_format::general, 6);
-            s_.append(b, r.ptr - b);
-        } else {
-            int n = snprintf(b, sizeof b, "%lg", x);
-            s_.append(b, n);
-        }
-        if (s_.size() >= kSpill) spill();
-    }
-    void integer(long long v) {
-        char b[24];
-        auto r = std::to_chars(b, b + sizeof b, v);
-        s_.append(b, r.ptr - b);
-    }
-    void ch(char c) { s_.push_back(c); }
-    void str(const char* p) { s_.append(p); }
-    const std::string& text() const { return s_; }   // (no FILE: the whole text, for tests)
-    bool ok() const { return ok_; }
-    void spill() {
-        if (!f_ || s_.empty()) return;
-        if (fwrite(s_.data(), 1, s_.size(), f_) != s_.size()) ok_ = false;
-        s_.clear();
-    }
-
-  private:
-    static constexpr size_t kSpill = 1 << 20;
-    FILE* f_;
-    std::string s_;
-    bool ok_ = true;
-};
 
 class FileWriter {
   public:

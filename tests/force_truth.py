@@ -43,7 +43,7 @@ and U_i to the same with Gu_i, U_i, Eu_i, Hu_i.  Every term is derived, none is 
   larger half-ulps: geom_roundings() counts them from the state.
 * Per term.  In units of u, relative to the term g d_k / r:
     the scaled form (n3_terms SC): r2 by two FMAs and a product (3, all terms positive) -> 1.5 on r;
-    rsq3 <= 2 (1.7e-16 measured, mdqt_internal.hpp), so ri carries 3.5 and enters cubed: 10.5;
+    rsq3 <= 2 (1.7e-16 measured, mdqt_math.hpp), so ri carries 3.5 and enters cubed: 10.5;
     fma(ri, sA, sB) with sA = fl(1/L)^2 and sB = fl(1/lDeb) fl(1/L), three roundings each: 3 + 1;
     the table's 2^t, <= 2 ulp: 4;  the products (.) 2^t, ri ri, (.)(ri ri), d ft: 4  -> 22.5 <= KF = 24.
     The exponent t = dr sT: sT = L (fl(1/lDeb) (64 fl(-log2 e))) carries 4, dr = r2 ri carries
@@ -71,7 +71,7 @@ The Newton-3 blocks (force_scheme 3: k_pairs_n3b, k_pairs_n3b_pw, k_n3b_reduce, 
     gate_i = [the gate above with D = depth_blocks(N)]  +  Form_i  +  Tail_i,
 
 and U_i to the same with FormU_i, TailU_i.  The three block terms come from the truth's separations and
-the constants the engine publishes (the radii of the call, mdqt_internal.hpp's kFormErrA/B); none from a
+the constants the engine publishes (the radii of the call, mdqt_math.hpp's kFormErrA/B); none from a
 device result.
 
 * Summation (depth_blocks).  T = ceil(N/64) tiles, NB = ceil(T/8) blocks, nd = NB/2 + 1 block distances
@@ -109,7 +109,7 @@ device result.
   through mdqt_tier_radius_model on the CPU.
   With a-priori radii (force_form_mode 0, or no measured tail) the f32 tier decides the cutoff on its f32
   r^2: fl32 relative coordinates and three f32 operations put r^2 within 11 x 2^-24 of itself
-  (mdqt_internal.hpp, kUfar32A/B's derivation: r within 5.5 x 2^-24, and fl32(rc2) another half), so a pair
+  (mdqt_math.hpp, kUfar32A/B's derivation: r within 5.5 x 2^-24, and fl32(rc2) another half), so a pair
   within F32CUT 2^-24 L/2 of L/2, F32CUT = 6, inside the reference's pair set or not, may be decided either
   way: a whole term g (u) each, added to Form_i — the analogue of H_i.  (far_radius_l's comment still
   says 3 x 2^-24, the round-3 form's count; its term (N - 1) g(L/2 (1 - 2^-20)) covers a shell 16 x 2^-24
@@ -288,7 +288,7 @@ def depth_blocks(N):
     return min(max(64 + BLOCK_TILES + runlen, 128 + 1 + 3) + nd + R + 8, N + 8)
 
 
-# mdqt_internal.hpp: kRsq1RelErr, kTab4RelErr, kFarRelErr, kRsqRawErr, kExp5RelErr, kExp2fRelErr, kUfar32A/B
+# mdqt_math.hpp: kRsq1RelErr, kTab4RelErr, kFarRelErr, kRsqRawErr, kExp5RelErr, kExp2fRelErr, kUfar32A/B
 _RSQ1, _TAB4, _FAR, _RSQRAW, _EXP5, _EXP2F = 2.2e-14, 4e-15, 3e-9, 2.0 ** -23, 1.1e-7, 2.0 ** -22
 # kFormErrA/B by plan level (n3b_level): 0 exact, 1 mid, 2 far, 3 very far, 4 ultra far, 5 ultra far in f32
 FORM_A = (0.0, _RSQ1 + 2.0 ** -52, 0.0, _RSQRAW, _RSQRAW + 2.0 ** -24, 22 * 2.0 ** -24)

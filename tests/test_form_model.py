@@ -10,7 +10,7 @@ import pytest
 
 from mdqtplasmasims_amd.engine import tier_radius_model
 
-# far_err's constants (mdqt_internal.hpp)
+# far_err's constants (mdqt_math.hpp)
 K_RSQ1, K_TAB4, K_FAR = 2.2e-14, 4e-15, 3e-9
 K_RAW, K_EXP5, K_EXP2F = 2.0 ** -23, 1.1e-7, 2.0 ** -22
 K_U32A, K_U32B = 22 * 2.0 ** -24, 52 * 2.0 ** -24

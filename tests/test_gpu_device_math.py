@@ -2,7 +2,7 @@
 
 mdqt_device_math (mdqtplasmasims_amd/csrc/mdqt_devmath.hip) evaluates, one element per thread and
 through the very inline functions the kernels call, sincos_tab / sincos_fast / sincos_q2
-(mdqt_device.hpp), rsq3 and exp_neg (mdqt_internal.hpp) and the pair kernels' table 2^t
+(mdqt_device.hpp), rsq3 and exp_neg (mdqt_math.hpp) and the pair kernels' table 2^t
 (mdqt_pairs.hpp exp2_neg_cut_tab).  Every other test of these functions compares one kernel that
 calls them with another kernel that calls them too.
 

@@ -670,7 +670,7 @@ def test_epotential_newton3_blocks_match_rows(sort):
 @pytest.mark.gpu
 def test_raw_rsq_error_within_the_very_far_bound():
     """The very-far pair form's bound assumes v_rsq_f64 is within kRsqRawErr = 2^-23 of 1/sqrt(x)
-    (mdqt_internal.hpp): tools/rsq_precision (built by __graft_entry__.build()) measures it on 4M
+    (mdqt_math.hpp): tools/rsq_precision (built by __graft_entry__.build()) measures it on 4M
     inputs over r^2 in [1e-4, 1e6] against a long-double reference"""
     import re
     import subprocess
@@ -687,7 +687,7 @@ def test_raw_rsq_error_within_the_very_far_bound():
 @pytest.mark.gpu
 def test_exp2f_error_within_the_ultra_far_bound():
     """The ultra-far pair form's bound assumes v_exp_f32 is within kExp2fRelErr = 2^-22 of 2^x
-    (mdqt_internal.hpp): tools/exp2f_precision measures it on 16M inputs over x in [-70, 0]"""
+    (mdqt_math.hpp): tools/exp2f_precision measures it on 16M inputs over x in [-70, 0]"""
     import re
     import subprocess
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "exp2f_precision")

@@ -1,4 +1,4 @@
-// v_exp_f32 precision probe (the ultra-far pair form's bound assumes it, mdqt_internal.hpp
+// v_exp_f32 precision probe (the ultra-far pair form's bound assumes it, mdqt_math.hpp
 // kExp2fRelErr): max relative error of __builtin_amdgcn_exp2f(x) over x in [-70, 0] (2^-70 ~ 8e-22,
 // inside f32's normal range) against a long-double reference of 2^x at the same float x.
 //   hipcc --offload-arch=gfx950 -O3 tools/exp2f_precision.hip -o tools/exp2f_precision

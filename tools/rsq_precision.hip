@@ -1,6 +1,6 @@
 // v_rsq_f64 precision probe: max relative error of the raw instruction and after one and two
 // Newton steps, against a long-double reference computed on the host; and v_rsq_f32 on the same
-// inputs rounded to float (the f32 ultra-far pair form's kRsqF32RelErr, mdqt_internal.hpp).
+// inputs rounded to float (the f32 ultra-far pair form's kRsqF32RelErr, mdqt_math.hpp).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
