@@ -414,7 +414,7 @@ mdqt_ctx*   mdqt_ensemble_job(mdqt_ensemble* e, int k);
 /* "qt_waves": register budget of the batched production QT instance in waves per SIMD: 0 (default) = the
  * single-job kernel's, no scratch; 3 = 168 VGPRs, 20 bytes of scratch per lane, the launch 7 % shorter at
  * 8 jobs of N0 = 3500 (bit-identical; A/B in docs/PROGRAMS.md).  Any other name: mdqt_set_option on every
- * member */
+ * member.  "output_batch", "pool" and "member_files" are the ensemble's own too (below) */
 int         mdqt_ensemble_set_option(mdqt_ensemble* e, const char* name, int value);
 int         mdqt_ensemble_init(mdqt_ensemble* e);              /* init() of every job, SpeedUp:289-348    */
 int         mdqt_ensemble_forces(mdqt_ensemble* e);            /* forces() of every job, :192-236: one launch */
@@ -448,11 +448,53 @@ int         mdqt_ensemble_epotential(mdqt_ensemble* e, double* Epot);
 /* kernel launches the batched output path has issued since creation (6 per output with every per-ion column,
  * 5 without the populations, 3 per mdqt_ensemble_epotential; a member's own fallback calls are not counted) */
 unsigned long long mdqt_ensemble_output_launches(const mdqt_ensemble* e);
+/* Pooled output(): the observables of each parameter point over its replicas (an ordinary ensemble is one point;
+ * point q of a sweep has the replicas r = 0 .. R-1 = the members q R .. q R + R - 1).  What the users of the
+ * reference's job array look at is the average over the jobs of a laser setting: the energies.dat columns
+ * averaged, the velocity distributions added up, and the P population binned against velocity (README III,
+ * statePopulationsVsVTime: "bin column 3 vs column 1").
+ * Ensemble options (mdqt_ensemble_set_option; both default to the behaviour without them):
+ *   "pool" (0): 1 = every output() of the ensemble (mdqt_ensemble_output, the outputs inside mdqt_ensemble_run)
+ *     also computes the pooled observables and writes them to <saveDirectory>/<run name>/pool_job<first>to<last>/,
+ *     beside the replicas' job<k>/ (first = job, last = job + R - 1).  8 launches per output instead of 6, still
+ *     two copies and one synchronisation.
+ *   "member_files" (1): 0 = output() writes no energies.dat, vel_dist* and statePopulationsVsVTime* of the
+ *     members, and the per-ion columns are not copied to the host; Epot, Epot0, the counter, the state and the
+ *     conditions files at the end of a run are unchanged, so the run can be resumed.
+ * Refused at the output call, before any launch or file, naming the first offending job index (the options may be
+ * set in any order, and the ensemble works again once the cause is fixed): pool 1 with output_batch 0; pool 1
+ * with a member the batched pass does not take (on the owner-computes rows: set force_scheme 2; potential_n3 0;
+ * another force_kernel than job index 0's); member_files 0 with pool 0.  Either option on the base of a pump
+ * ensemble is refused when it is set.
+ * The pooled observables, all in terms of the members' published values (mdqt_ensemble_observables):
+ *   mean7[7]: [0] = the first replica's t; [c] = (sum_r out7[r][c]) / R, summed in replica order onto 0;
+ *   sem6[6]:  sqrt(sum_r (out7[r][c] - mean7[c])^2 / (R (R - 1))), the same order; 0 for R = 1;
+ *   Pvel[3][2001]: sum_r Pvel_r, in replica order onto 0 (the members' normalised bins);
+ *   count[1002], spd[3][1002]: ion i of a replica goes to slot 500 + (int)rint(vx * 100.0) when
+ *     fabs(rint(vx * 100.0)) <= 500 (centre (slot - 500) * 0.01) and to slot 1001 ("outside") otherwise, NaN
+ *     included; per slot the number of ions and the sums of their S, P and D populations (the members' pops, the
+ *     same bits).  The order of every sum is fixed and there are no atomics: within a member, each KDE chunk
+ *     (nch = clamp(N / 32, 1, 512) chunks of ceil(N / nch) ions) sums its matching ions in ascending order onto
+ *     0; the member's chunks are summed in ascending order onto 0; the replicas' sums in ascending order onto 0.
+ * Files (tab-separated %lg; %06d = the first replica's counter): energies.dat (mean7, appended),
+ * energies_sem.dat (t, sem6; appended), populations.dat (t, S, P, D as (sum over the 1,002 slots, ascending, of
+ * the slot's sum) / (total count), the total count, the outside count; appended), vel_dist{X,Y,Z}_time%06d.dat
+ * (vel[j] + mean7[6] for X, vel[j] for Y and Z; the pooled bin), statePopulationsVsV_time%06d.dat (1,001 rows:
+ * centre, count, S, P, D as the slot's sum / count, 0 where the count is 0).
+ * mdqt_pool_rows: host only — mean7 and sem6 of R rows out7 [R][7].
+ * mdqt_ensemble_pool_directory: host only — the pooled directory of point `point` of an ensemble of npoints x
+ * njobs members (npoints 1: mdqt_ensemble_create's), into buf.
+ * mdqt_ensemble_pool_observables: one pooled pass, no files, whatever "pool" is set to, with the same refusals:
+ * mean7 [P][7], sem6 [P][6], Pvel [P][3 * 2001] or NULL, count [P][1002] or NULL, spd [P][3][1002] or NULL. */
+int         mdqt_pool_rows(const double* out7, int R, double* mean7, double* sem6);
+int         mdqt_ensemble_pool_directory(const mdqt_params* points, int npoints, int njobs, int point, char* buf, size_t cap);
+int         mdqt_ensemble_pool_observables(mdqt_ensemble* e, double* mean7, double* sem6, double* Pvel, long long* count, double* spd);
 /* the two batched kernels' own durations from their dispatch timestamps (on > 0: every launch):
  * out[6] = force ms (sum), force launches, QT ms (sum), QT launches, median force launch ms, median
  * QT launch ms — since the last call; synchronises and resets.  With n >= 12 also the batched output's
  * potential and KDE launches: out[6..11] = potential ms (sum), launches, KDE ms (sum), launches, and the two
- * medians.  Replaces no reference function */
+ * medians; with n >= 18 also the pooled pass's two launches (the slot partials, their sum over replicas) in the
+ * same layout: out[12..17].  Replaces no reference function */
 int         mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on);
 int         mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n);
 /* Parameter sweeps: npoints parameter points x njobs replicas in one ensemble (the thesis data are scans of the

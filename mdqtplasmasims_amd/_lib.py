@@ -233,6 +233,10 @@ SIGNATURES = [
     ("mdqt_ensemble_create_sweep", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("mdqt_ensemble_sweep_params", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.c_int, C.c_int, C.POINTER(MdqtParams)]),
     ("mdqt_ensemble_points", C.c_int, [C.c_void_p]),
+    # the pooled output(): each point's observables over its replicas
+    ("mdqt_pool_rows", C.c_int, [_dp, C.c_int, _dp, _dp]),
+    ("mdqt_ensemble_pool_directory", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    ("mdqt_ensemble_pool_observables", C.c_int, [C.c_void_p, _dp, _dp, _dp, C.POINTER(C.c_longlong), _dp]),
     # ensembles of the optical-pumping programs, and the single context's stepwise MD step
     ("mdqt_pump_md_steps", C.c_int, [C.c_void_p, C.c_int]),
     ("mdqt_pump_ensemble_create", C.c_int, [C.POINTER(MdqtParams), C.c_int, C.POINTER(C.c_void_p)]),

@@ -16,6 +16,11 @@
 //   seeded seed + k; each job's files are those of `mdqt <job>+k --seed=<seed>+k`; prints every N.
 //   --output_batch=0|1 (with --njobs): output() of all jobs in one device pass (1) or job after job (0, the
 //   default); the same files either way.
+//   --pool=0|1 (with --njobs): 1 = every output() also writes the observables pooled over the jobs of each parameter
+//   point — the energies averaged with their standard errors, the velocity distributions added up, the S / P / D
+//   populations binned against vx — into pool_job<first>to<last>/ beside the jobs' directories; implies
+//   --output_batch=1.  --member_files=0|1 (with --pool=1): 0 = the jobs' energies.dat, vel_dist* and
+//   statePopulationsVsVTime* are not written (their conditions files still are: the run can be resumed).
 //
 //   --sweep=NAME:v1,v2,... (with --njobs=R; NAME one of detuning, detuningDP, Om, OmDP, fracOfSig; may be given
 //   for several names) runs a parameter scan as one ensemble (mdqt_ensemble_create_sweep): the points are the
@@ -46,6 +51,10 @@ static void usage(void) {
             "       mdqt <job> --njobs=J [... as above]   jobs <job> .. <job>+J-1 as one ensemble (J >= 1;\n"
             "                  seeds seed .. seed+J-1; not with --pump_program: --pump_jobs)\n"
             "                  [--output_batch=0|1]   output() of all jobs in one device pass (1) or job after job (0)\n"
+            "                  [--pool=0|1]   1: every output() also writes each point's observables pooled over its jobs\n"
+            "                  to pool_job<first>to<last>/ (implies --output_batch=1; not with --output_batch=0)\n"
+            "                  [--member_files=0|1]   0 (with --pool=1): no energies.dat, vel_dist*, statePopulationsVsVTime*\n"
+            "                  of the jobs themselves\n"
             "                  [--sweep=NAME:v1,v2,... ...]   with --njobs=R: a scan of detuning | detuningDP | Om | OmDP |\n"
             "                  fracOfSig, R jobs per point, as one ensemble (points: the product of the lists, the first\n"
             "                  NAME slowest; points x R <= 1024; each NAME once)\n"
@@ -73,6 +82,7 @@ int main(int argc, char** argv) {
     long njobs = -1;                                        // --njobs: the jobs of an ensemble (-1: not given)
     long pump_jobs = -1;                                    // --pump_jobs: the jobs of a pump ensemble
     long output_batch = -1;                                 // --output_batch: the ensemble's option (-1: its default)
+    long pool = -1, member_files = -1;                      // --pool, --member_files: the ensemble's options
     SweepAxes axes;                                         // --sweep: the axes in the order given
     for (int i = 2; i < argc; ++i) {
         char key[64];
@@ -99,6 +109,14 @@ int main(int argc, char** argv) {
             if (end == v || *end || output_batch < 0 || output_batch > 1) { usage(); return 2; }
             continue;
         }
+        if (!strcmp(key, "pool")) {
+            if (!cli_switch(v, &pool)) { usage(); return 2; }
+            continue;
+        }
+        if (!strcmp(key, "member_files")) {
+            if (!cli_switch(v, &member_files)) { usage(); return 2; }
+            continue;
+        }
         if (!strcmp(key, "sweep")) {
             if (!axes.add(v, sweep_names)) { usage(); return 2; }
             continue;
@@ -121,6 +139,10 @@ int main(int argc, char** argv) {
     if (pump_jobs > 0 && (!pump || njobs > 0)) { usage(); return 2; }
     if (output_batch >= 0 && njobs < 1) { usage(); return 2; }
     if (!axes.empty() && (njobs < 1 || pump)) { usage(); return 2; }
+    if ((pool >= 0 || member_files >= 0) && (njobs < 1 || pump)) { usage(); return 2; }
+    if (pool == 1 && output_batch == 0) { usage(); return 2; }
+    if (member_files == 0 && pool != 1) { usage(); return 2; }
+    if (pool == 1) output_batch = 1;
     if (!seed_given) p.seed = (uint32_t)(time(NULL) + job);   // SpeedUp:1219
     std::vector<mdqt_params> points;                        // of a scan: at most kSweepMax members in all
     if (!axes.empty() && !axes.points(p, sweep_fields, kSweepMax / njobs, &points)) { usage(); return 2; }
@@ -137,7 +159,9 @@ int main(int argc, char** argv) {
             fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
             return 1;
         }
-        if (output_batch >= 0 && mdqt_ensemble_set_option(e, "output_batch", (int)output_batch)) {
+        if ((output_batch >= 0 && mdqt_ensemble_set_option(e, "output_batch", (int)output_batch)) ||
+            (pool >= 0 && mdqt_ensemble_set_option(e, "pool", (int)pool)) ||
+            (member_files >= 0 && mdqt_ensemble_set_option(e, "member_files", (int)member_files))) {
             fprintf(stderr, "mdqt: %s\n", mdqt_last_error());
             mdqt_ensemble_destroy(e);
             return 1;

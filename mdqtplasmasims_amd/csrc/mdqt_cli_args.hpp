@@ -1,5 +1,5 @@
-// What the command lines (mdqt_cli.cpp, mdmc_cli.cpp, mdlc_cli.cpp) parse alike: an argument "--key=value", and
-// the axes of a parameter scan, --sweep=NAME:v1,v2,... once per NAME, with the points they span.  Nothing here
+// What the command lines (mdqt_cli.cpp, mdmc_cli.cpp, mdlc_cli.cpp) parse alike: an argument "--key=value", a 0 | 1
+// switch, and the axes of a parameter scan, --sweep=NAME:v1,v2,... once per NAME, with the points they span.  Nothing here
 // prints or exits: a false result is the caller's usage() and exit 2.
 #pragma once
 #include <stdlib.h>
@@ -16,6 +16,13 @@ inline bool cli_key_value(const char* a, char* key, size_t cap, const char** val
     memcpy(key, a + 2, kl);
     key[kl] = 0;
     *value = eq + 1;
+    return true;
+}
+
+// a 0 | 1 switch's value: false for anything else (empty, signs, trailing text)
+inline bool cli_switch(const char* v, long* out) {
+    if ((v[0] != '0' && v[0] != '1') || v[1]) return false;
+    *out = v[0] - '0';
     return true;
 }
 

@@ -272,6 +272,7 @@ void observables_from_rows(mdqt_ctx* s, const double* h, const double* col, doub
 
 // mdqt_io.cpp
 FILE* open_in(const mdqt_ctx* s, const char* name, const char* mode);
+void speedup_run_name(const mdqt_params* p, char* name, size_t cap);
 int finish_directories(mdqt_ctx* s, const char* name);
 int flush_files(mdqt_ctx* s);
 int output_async(mdqt_ctx* s);

@@ -92,5 +92,18 @@ hipError_t launch_potential_sums_ens(const EnsObsArgs* jobs, int njobs, int max_
 hipError_t launch_kde_ens(const EnsObsArgs* jobs, int njobs, int max_nch, hipStream_t s, hipEvent_t ev0 = nullptr,
                           hipEvent_t ev1 = nullptr);
 hipError_t launch_output_pack_ens(const EnsObsArgs* jobs, int njobs, int max_N, hipStream_t s);
+// The pooled output() of an ensemble (mdqt_ensemble_pool.hip; option "pool"): the velocity-resolved populations of
+// each parameter point over all ions of its replicas.  kPopSlots slots: 0 .. 1000 have the centres (slot - 500) *
+// 0.01 (the KDE's +-5 range), 1001 is "outside"; kPopPlanes planes per slot: the count (a 64-bit integer in the
+// double's place), sum S, sum P, sum D.
+constexpr int kPopSlots = 1002;
+constexpr int kPopPlanes = 4;
+static_assert(kPopPlanes * kPopSlots <= 3 * NBINS, "a chunk's slot partials fit its spent KDE partials (EnsObsArgs::kde)");
+// k_popv_ens over the npoints x R blocks at `jobs` (point-major; after launch_kde_ens and launch_output_pack_ens:
+// it reads pack and overwrites kde), then k_popv_pool into out [npoints][kPopPlanes][kPopSlots]; the launches'
+// timestamps to (ev0, ev1) and (ev2, ev3)
+hipError_t launch_popv_ens(const EnsObsArgs* jobs, int npoints, int R, int max_nch, double* out, hipStream_t s,
+                           hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, hipEvent_t ev2 = nullptr,
+                           hipEvent_t ev3 = nullptr);
 
 }  // namespace mdqt

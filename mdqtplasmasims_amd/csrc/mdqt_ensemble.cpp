@@ -388,6 +388,7 @@ int mdqt::ensemble_create(const mdqt_params* p, int npoints, int replicas, mdqt_
     if (!e) return set_error("%s: out of memory", what);
     e->npoints = npoints;
     e->sweep = sweep;
+    e->pump = pump;
     try {
         e->jobs.reserve((size_t)njobs);
         e->writer.reset(new FileWriter(std::min(16, 4 * njobs)));
@@ -465,6 +466,14 @@ extern "C" int mdqt_ensemble_set_option(mdqt_ensemble* e, const char* name, int 
         e->output_batch = value;
         return 0;
     }
+    if (!strcmp(name, "pool") || !strcmp(name, "member_files")) {    // the ensemble's own: never forwarded to the members
+        if (e->pump) return set_error("%s is an option of the SpeedUp ensemble: the pump programs' output() has no pooled pass", name);
+        if (value != 0 && value != 1)
+            return set_error(name[0] == 'p' ? "pool must be 0 (the members' files only) or 1 (also each point's pooled files)"
+                                            : "member_files must be 1 (the members' output files) or 0 (the pooled files only)");
+        (name[0] == 'p' ? e->pool : e->member_files) = value;
+        return 0;
+    }
     for (mdqt_ctx* s : e->jobs)
         if (mdqt_set_option(s, name, value)) return -1;
     if (e->sweep) {                                 // an option may rebuild the members' tables: the points' copies follow
@@ -517,6 +526,8 @@ extern "C" int mdqt_ensemble_run(mdqt_ensemble* e) {
         if (fresh ? mdqt_init(s) : mdqt_read_conditions(s, s->p.c0)) return -1;
     if (ens_check(e, "mdqt_ensemble_run")) return -1;
     if (e->sweep && sweep_check(e, std::min(e->jobs[0]->ratio, MAXSUB), "mdqt_ensemble_run")) return -1;
+    if (!e->pool && !e->member_files) return set_error("mdqt_ensemble_run: member_files 0 with pool 0 would write nothing: set pool 1");
+    if (e->pool && ens_pool_check(e, "mdqt_ensemble_run with pool 1")) return -1;      // before the first step, not at the first output
     HIPCHK(hipSetDevice(e->dev));
     struct {                                            // the loop's driver: one batched call over the members
         mdqt_ensemble* e;
@@ -548,7 +559,8 @@ extern "C" int mdqt_ensemble_enable_timing(mdqt_ensemble* e, int on) {
 // the two batched kernels' own durations (their dispatch timestamps) since the last call: out[6] = force
 // ms (sum), force launches, QT ms (sum), QT launches, median force launch (ms), median QT launch (ms); with
 // n >= 12 also the batched output's potential and KDE launches: out[6..11] = potential ms (sum), launches, KDE
-// ms (sum), launches, median potential launch (ms), median KDE launch (ms); resets
+// ms (sum), launches, median potential launch (ms), median KDE launch (ms); with n >= 18 also the pooled pass's two
+// launches (k_popv_ens, k_popv_pool) in the same layout: out[12..17]; resets
 extern "C" int mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n) {
     if (!e || !out) return set_error("mdqt_ensemble_kernel_times: NULL argument");
     if (n < 6) return set_error("mdqt_ensemble_kernel_times: need 6 doubles");
@@ -561,13 +573,14 @@ extern "C" int mdqt_ensemble_kernel_times(mdqt_ensemble* e, double* out, int n) 
         out[2 * k + 1] = v[1];
         out[4 + k] = v[2];
     }
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < 4; ++k) {                       // 0, 1: out[6..11]; the pooled pass's 2, 3: out[12..17]
         double v[5];
         if (e->obs_timers[k].stats(v)) return -1;
-        if (n < 12) continue;
-        out[6 + 2 * k] = v[0];
-        out[7 + 2 * k] = v[1];
-        out[10 + k] = v[2];
+        const int at = k < 2 ? 6 : 12, j = k % 2;
+        if (n < at + 6) continue;
+        out[at + 2 * j] = v[0];
+        out[at + 1 + 2 * j] = v[1];
+        out[at + 4 + j] = v[2];
     }
     return 0;
 }

@@ -42,7 +42,14 @@ struct mdqt_ensemble {
     mdqt::DevBuf<double> dObsCols;                 // [sum 4 N_k]
     mdqt::PinRing obs_ring;                        // one slot: the rows, then the columns
     unsigned long long output_launches = 0;        // kernel launches of the batched output path
-    mdqt::LaunchTimer obs_timers[2];               // 0 = the batched potential launches, 1 = the batched KDE launches
+    mdqt::LaunchTimer obs_timers[4];               // 0 = the batched potential launches, 1 = the batched KDE launches,
+                                                   // 2 = the pooled pass's slot partials, 3 = its sum over replicas
+    // the pooled output() (options "pool" and "member_files"; mdqt_ensemble_output.cpp, mdqt_ensemble_pool.hip): each
+    // point's observables over its replicas, written to a directory beside the replicas'.  The points' slot sums
+    // [npoints][kPopPlanes][kPopSlots] follow the rows in dObsRows and come back with them in one copy.
+    bool pump = false;                             // the base of an mdqt_pump_ensemble: neither option applies
+    int pool = 0;                                  // option "pool": 1 = every output() also pools each point
+    int member_files = 1;                          // option "member_files": 0 = output() writes the pooled files only
 };
 
 // J independent jobs of an optical-pumping program stepped in batched launches (mdqt_pump_ensemble.cpp): an
@@ -79,5 +86,8 @@ int ens_epotential(mdqt_ensemble* e, double* Epot);
 // batched member member[q]'s Epotential() is ens_epot_of(job, rows + 64 q)
 int ens_epotential_queue(mdqt_ensemble* e, std::vector<int>& member, const double** rows);
 double ens_epot_of(const mdqt_ctx* s, const double* row);
+// what a pooled output() needs of the options and of every member, checked at the call (the options may be set in
+// any order): 0, or -1 after set_error naming the first offending job index; nothing is launched or written
+int ens_pool_check(const mdqt_ensemble* e, const char* what);
 
 }  // namespace mdqt

@@ -39,13 +39,18 @@ int mdqt::finish_directories(mdqt_ctx* s, const char* name) {
     return 0;
 }
 
-extern "C" int mdqt_setup_directories(mdqt_ctx* s) {       // SpeedUp:1145-1160
-    const mdqt_params* p = &s->p;
-    char name[256];
-    snprintf(name, sizeof name, "Ge%dDensity%dE+11Sig0%dTe%dSigFrac%dDetSP%dDetDP%dOmSP%dOmDP%dNumIons%d",
+// the SpeedUp program's name of a run, SpeedUp:1145-1160 (the jobs' job<k>/ and an ensemble's pooled directory
+// lie below it)
+void mdqt::speedup_run_name(const mdqt_params* p, char* name, size_t cap) {
+    snprintf(name, cap, "Ge%dDensity%dE+11Sig0%dTe%dSigFrac%dDetSP%dDetDP%dOmSP%dOmDP%dNumIons%d",
              ref_udcast(100 * p->Ge), ref_udcast(p->density * 1000), ref_udcast(10 * p->sig0), ref_udcast(p->Te),
              ref_udcast(p->fracOfSig * 100), ref_udcast(p->detuning * 100), ref_udcast(p->detuningDP * 100),
              ref_udcast(p->Om * 100), ref_udcast(p->OmDP * 100), ref_udcast((double)p->N0));
+}
+
+extern "C" int mdqt_setup_directories(mdqt_ctx* s) {       // SpeedUp:1145-1160
+    char name[256];
+    speedup_run_name(&s->p, name, sizeof name);
     return finish_directories(s, name);
 }
 

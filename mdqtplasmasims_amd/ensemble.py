@@ -17,6 +17,7 @@ state is bit for bit what :class:`~mdqtplasmasims_amd.engine.Simulation` gives f
     output()          :917-1032        Ensemble.output()            mdqt_ensemble_output
     output()'s numbers                 Ensemble.observables()       mdqt_ensemble_observables
     Epotential()      :244-281         Ensemble.epotential()        mdqt_ensemble_epotential
+    the job array's averages           Ensemble.pool_observables()  mdqt_ensemble_pool_observables
     =================================  ===========================  ==========================
 """
 from __future__ import annotations
@@ -50,6 +51,18 @@ def sweep_params(base: MdqtParams, sweep, njobs: int, k: int) -> MdqtParams:
     return out
 
 
+POOL_SLOTS = 1002   # the velocity-resolved populations' slots: 1,001 of width 0.01 centred on -5 .. 5, and "outside"
+
+
+def pool_directory(points, njobs: int, p: int = 0) -> str:
+    """the pooled directory of point p of an ensemble of len(points) x njobs members (points: MdqtParams, one or
+    an array; host only)"""
+    arr = (MdqtParams * 1)(points) if isinstance(points, MdqtParams) else points
+    buf = C.create_string_buffer(1400)
+    check(lib().mdqt_ensemble_pool_directory(arr, len(arr), int(njobs), int(p), buf, len(buf)), "ensemble_pool_directory")
+    return buf.value.decode()
+
+
 class _Member(Simulation):
     """a job of an ensemble: the whole Simulation interface on a context the ensemble owns"""
 
@@ -79,10 +92,12 @@ class Ensemble(_EnsembleBase):
         h = C.c_void_p()
         if sweep is None:
             self.points = [{}]
+            self._point_params = (MdqtParams * 1)(self.params)
             check(lib().mdqt_ensemble_create(C.byref(self.params), self.njobs, C.byref(h)), "mdqt_ensemble_create")
             member = [job_params(self.params, k) for k in range(lib().mdqt_ensemble_size(h))]
         else:
             self.points, arr = sweep_points(self.params, sweep, SWEEP_FIELDS)
+            self._point_params = arr
             check(lib().mdqt_ensemble_create_sweep(arr, len(arr), self.njobs, C.byref(h)), "mdqt_ensemble_create_sweep")
             member = [job_params(arr[k // self.njobs], k % self.njobs) for k in range(lib().mdqt_ensemble_size(h))]
         self.h = h
@@ -101,7 +116,9 @@ class Ensemble(_EnsembleBase):
 
     def set_option(self, name: str, value: int):
         """"qt_waves" (the batched QT kernel's register budget), "output_batch" (1: output() of all jobs in one
-        device pass, 0: job after job, the default) or any Simulation option, on every job"""
+        device pass, 0: job after job, the default), "pool" (1: every output() also writes each point's pooled
+        observables; needs output_batch 1), "member_files" (0: output() writes the pooled files only) or any
+        Simulation option, on every job"""
         check(lib().mdqt_ensemble_set_option(self.h, name.encode(), int(value)), "ensemble_set_option")
 
     # ---- the reference's function seam, for every job at once ----
@@ -145,6 +162,22 @@ class Ensemble(_EnsembleBase):
         check(lib().mdqt_ensemble_epotential(self.h, dptr(out)), "ensemble_epotential")
         return out
 
+    # ---- the pooled output(): each point's observables over its replicas (option "pool") ----
+    def pool_observables(self):
+        """one pooled pass, no files: {mean7 [P, 7], sem6 [P, 6], Pvel [P, 3, NBINS], count [P, 1002] (int64), spd
+        [P, 3, 1002] (the slots' sums of S, P, D)} for the P points (include/mdqt.h has the definitions)"""
+        P = len(self.points)
+        out = dict(mean7=np.zeros((P, 7)), sem6=np.zeros((P, 6)), Pvel=np.zeros((P, 3, NBINS)),
+                   count=np.zeros((P, POOL_SLOTS), dtype=np.int64), spd=np.zeros((P, 3, POOL_SLOTS)))
+        check(lib().mdqt_ensemble_pool_observables(self.h, dptr(out["mean7"]), dptr(out["sem6"]), dptr(out["Pvel"]),
+                                                   out["count"].ctypes.data_as(C.POINTER(C.c_longlong)), dptr(out["spd"])),
+              "ensemble_pool_observables")
+        return out
+
+    def pool_directory(self, p: int = 0) -> str:
+        """the directory of point p's pooled files (host only): beside its replicas' job<k>/"""
+        return pool_directory(self._point_params, self.njobs, p)
+
     @property
     def output_launches(self):
         """kernel launches the batched output path has issued (a member's own fallback calls are not counted)"""
@@ -158,15 +191,17 @@ class Ensemble(_EnsembleBase):
     def kernel_times(self):
         """{force_ms, n_force, substep_ms, n_substep, force_median_ms, substep_median_ms} of the batched
         launches since the last call (synchronises and resets)"""
-        return {k: v for k, v in self.output_kernel_times().items() if "potential" not in k and "kde" not in k}
+        return {k: v for k, v in self.output_kernel_times().items() if "force" in k or "substep" in k}
 
     def output_kernel_times(self):
         """kernel_times() and the batched output's potential and KDE launches: potential_ms, n_potential, kde_ms,
-        n_kde, potential_median_ms, kde_median_ms"""
-        out = (C.c_double * 12)()
-        check(lib().mdqt_ensemble_kernel_times(self.h, out, 12), "ensemble_kernel_times")
+        n_kde, potential_median_ms, kde_median_ms; then the pooled pass's two launches: popv_ms, n_popv, pool_ms,
+        n_pool, popv_median_ms, pool_median_ms"""
+        out = (C.c_double * 18)()
+        check(lib().mdqt_ensemble_kernel_times(self.h, out, 18), "ensemble_kernel_times")
         return self._times(out, ("force_ms", "n_force", "substep_ms", "n_substep", "force_median_ms", "substep_median_ms",
-                                 "potential_ms", "n_potential", "kde_ms", "n_kde", "potential_median_ms", "kde_median_ms"))
+                                 "potential_ms", "n_potential", "kde_ms", "n_kde", "potential_median_ms", "kde_median_ms",
+                                 "popv_ms", "n_popv", "pool_ms", "n_pool", "popv_median_ms", "pool_median_ms"))
 
 
-__all__ = ["Ensemble", "job_params", "sweep_params", "SWEEP_FIELDS"]
+__all__ = ["Ensemble", "job_params", "sweep_params", "pool_directory", "SWEEP_FIELDS", "POOL_SLOTS"]

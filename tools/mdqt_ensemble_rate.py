@@ -27,7 +27,11 @@ apart after --skip uncounted ones, the wall time (ms, median / min / max over th
 and, where the library has the batched output (this is skipped under MDQT_LIB with an older build), for
 output_batch 0 and 1: e.observables() and e.output() (files flushed inside), with the batched potential and
 KDE launches' own median durations.  The observables / output pairs split an output into the device pass with
-its synchronisations and the files' formatting.
+its synchronisations and the files' formatting.  --pool adds the pooled output (ensemble option pool 1 on the batched
+pass): pool_observables (e.pool_observables(): the pooled pass, no files) and output_pool_files<m> (e.output() with
+pool 1 and member_files m, for each m of --member-files), with the two pooled launches' own median durations beside
+the KDE launch's.  --sweep applies here too (J members in all, J / points per point: the pooled pass pools each
+point), and --paths keeps only the named paths.
 """
 import argparse
 import json
@@ -62,7 +66,7 @@ def stats_ms(xs):
     return dict(median=xs[len(xs) // 2] * 1e3, min=xs[0] * 1e3, max=xs[-1] * 1e3)
 
 
-def output_mode(M, a, params, jobs, out):
+def output_mode(M, a, params, jobs, out, sweep=None, npoints=1):
     """the wall time of one output() of all members, by path (see the module docstring)"""
     from mdqtplasmasims_amd._lib import lib
     batched = hasattr(lib(), "mdqt_ensemble_output")
@@ -76,13 +80,27 @@ def output_mode(M, a, params, jobs, out):
             for ob in (0, 1):
                 paths[f"observables_batch{ob}"] = (ob, lambda e: e.observables())
                 paths[f"output_batch{ob}"] = (ob, lambda e: e.output())
+        options = {}
+        if a.pool:
+            paths["pool_observables"] = (1, lambda e: e.pool_observables())
+            for mf in a.member_files:
+                paths[f"output_pool_files{mf}"] = (1, lambda e: e.output())
+                options[f"output_pool_files{mf}"] = dict(pool=1, member_files=mf)
+        if a.paths:
+            unknown = [n for n in a.paths if n not in paths]
+            if unknown:
+                raise SystemExit(f"--paths: {unknown} not among {sorted(paths)}")
+            paths = {n: paths[n] for n in a.paths}
         row = dict(jobs=J)
         for name, (ob, call) in paths.items():
             base = tempfile.mkdtemp(prefix="mdqt_output_")
             try:
-                with M.Ensemble(njobs=J, seed=12346, job=1, saveDirectory=base + "/", **params) as e:
+                with (M.Ensemble(njobs=J // npoints, sweep=sweep, seed=12346, job=1, saveDirectory=base + "/", **params) if sweep
+                      else M.Ensemble(njobs=J, seed=12346, job=1, saveDirectory=base + "/", **params)) as e:
                     if ob is not None:
                         e.set_option("output_batch", ob)
+                    for option, v in options.get(name, {}).items():
+                        e.set_option(option, v)
                     for j in e.jobs:
                         j.setup_directories()
                     e.init()
@@ -101,6 +119,9 @@ def output_mode(M, a, params, jobs, out):
                         kt = e.output_kernel_times()
                         row[name]["potential_us"] = kt["potential_median_ms"] * 1e3
                         row[name]["kde_us"] = kt["kde_median_ms"] * 1e3
+                        if kt.get("n_popv"):
+                            row[name]["popv_us"] = kt["popv_median_ms"] * 1e3
+                            row[name]["pool_us"] = kt["pool_median_ms"] * 1e3
             finally:
                 shutil.rmtree(base, ignore_errors=True)
         out["output"].append(row)
@@ -116,7 +137,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--qt-waves", type=int, default=0, help="Ensemble option qt_waves (0, 3)")
     ap.add_argument("--sweep", action="append", default=[], metavar="NAME:v1,v2",
-                    help="--mode rate: the ensembles are sweep ensembles (Ensemble(sweep=...)) of J members in all: the\n"
+                    help="the ensembles are sweep ensembles (Ensemble(sweep=...)) of J members in all: the\n"
                     "points are the product of the lists (may be given per NAME), J / points jobs each; one value\n"
                     "= the sweep kernels on the uniform ensemble's jobs")
     ap.add_argument("--device", type=int, default=0)
@@ -124,6 +145,9 @@ def main():
     ap.add_argument("--outputs", type=int, default=25, help="--mode output: timed outputs")
     ap.add_argument("--every", type=int, default=40, help="--mode output: MD steps between outputs (sampleFreq)")
     ap.add_argument("--skip", type=int, default=5, help="--mode output: uncounted outputs first")
+    ap.add_argument("--pool", action="store_true", help="--mode output: also the pooled output (option pool 1)")
+    ap.add_argument("--member-files", default="1,0", help="--mode output --pool: the member_files values to measure")
+    ap.add_argument("--paths", default="", help="--mode output: only these paths (comma-separated names of the result's keys)")
     ap.add_argument("--json", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
 
@@ -139,14 +163,16 @@ def main():
     npoints = 1
     for values in sweep.values():
         npoints *= len(values)
-    if any(J % npoints for J in jobs) and sweep and a.mode == "rate":
+    a.member_files = [int(x) for x in a.member_files.split(",") if x]
+    a.paths = [x for x in a.paths.split(",") if x]
+    if any(J % npoints for J in jobs) and sweep:
         ap.error(f"--sweep: every J of --jobs must be a multiple of the {npoints} points")
     out = dict(tool="mdqt_ensemble_rate", config=a.config, steps=a.steps, warmup=a.warmup, qt_waves=a.qt_waves,
                unit="particle-qsteps/s", fp64_peak=FP64_PEAK)
     if sweep:
         out["sweep"] = sweep
     if a.mode == "output":
-        output_mode(M, a, params, jobs, out)
+        output_mode(M, a, params, jobs, out, sweep, npoints)
         out["unit"] = "ms per output of all members"
         line = json.dumps(out)
         print(line)
